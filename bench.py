@@ -10,9 +10,13 @@ is BASELINE configs[1]: batch=1 per GPU, 29 regions, greedy, max_len=128, fp32.
   python bench.py --gpus N ...        (no launcher in the environment: re-executes itself under torch.distributed.run
                                        with N ranks on 127.0.0.1 and a free port)
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  At N = 1 with the default workload the line also carries
-"config2": BASELINE configs[2] (batch 32 under bf16 autocast) timed in the same process after the headline loop, and
-"cpu_baseline": the CPU oracle on a bounded sample.
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  A plain run only sets up, warms up, times the K steps and
+prints the line.  With --full the line also carries what takes runs of its own: the rooflines of the headline workload,
+at N = 1 with the default workload the legs `config1` / `beam4` / `config4`, and `cpu_baseline`, the CPU oracle on a
+bounded sample.
+
+  --dump-outputs DIR   after the timed steps, what the last step returned, as DIR/<name>.npy (float32 / float64): the
+                       inputs are seeded, so two builds can be compared output for output
 """
 from __future__ import annotations
 
@@ -360,7 +364,40 @@ def _bracketed(fn, calls, use_dist, dev):
     return dt, out
 
 
-def config4_line(model, synth, world=1, use_dist=False, dev=None, steps=3, T=64):
+DUMP_BYTES_PER_ARRAY = 12 << 20   # 5 arrays of a generate() call stay under 64 MB in all
+
+
+def dump_outputs(out, out_dir):
+    """--dump-outputs: what the timed path returned in its last step, as out_dir/<name>.npy - generate()'s (output_ids,
+    selected_regions, detections, class_detected), a detections dict entry per key, or the training step's `losses`.
+    Integer ids go to float64 (exact), everything else to float32.  An array above DUMP_BYTES_PER_ARRAY is stored as a
+    fixed, seeded sample of its flattened elements (<name>.npy) with their indices (<name>_index.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if isinstance(out, int):   # generate() returns -1 when no region is selected
+        arrays = {"output_ids": torch.tensor([out])}
+    elif isinstance(out, dict):
+        arrays = out
+    else:
+        arrays = {}
+        for name, v in zip(("output_ids", "selected_regions", "detections", "class_detected"), out):
+            if isinstance(v, dict):
+                arrays.update({f"detections_{k}": t for k, t in v.items()})
+            else:
+                arrays[name] = v
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        a = t.to(torch.float64 if wide else torch.float32).numpy()
+        if a.nbytes > DUMP_BYTES_PER_ARRAY:
+            k = DUMP_BYTES_PER_ARRAY // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def config4_line(model, synth, world=1, use_dist=False, dev=None, steps=3, T=64, with_roofline=True):
     """BASELINE configs[4]: one end-to-end training step per call - 8 images per GPU, object detector frozen (its inference
     branch runs), both region classifiers + the language model's trainable tensors (53.66 M values) - forward under bf16
     autocast, HIP backward, gradients ALL-REDUCED over the ranks in place on flat buckets (rgrg_amd.dist.GradBuckets: RCCL
@@ -404,21 +441,22 @@ def config4_line(model, synth, world=1, use_dist=False, dev=None, steps=3, T=64)
         # own operands and epilogues; `step_frac` = the same flops over the WHOLE step (attention, row kernels, detector,
         # optimizer included)
         roof = None
-        try:
-            eng = model.engine()
-            S_run, T_run = eng.last_train_shape   # the sentences the step really fed (a region that is not detected is dropped)
-            t = eng.time_train_gemms(S_run, T_run, 3)
-            tf = t["gemm_flops"] / (t["ms_gemm"] * 1e-3) / 1e12
-            roof = {"bound": "mfma", "kernel": "gemm_bf16_pp_kernel (256 x 256 ping-pong, all GEMMs of the step at 14 848 rows)",
-                    "achieved": tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": tf / 2500.0, "traffic": None,
-                    "launches_per_step": t["gemm_launches"], "avg_launch_us": 1e3 * t["ms_gemm"] / t["gemm_launches"],
-                    "algorithmic_flops_per_launch": t["gemm_flops"] / t["gemm_launches"], "ms_gemm_per_step": t["ms_gemm"],
-                    "step_frac": t["gemm_flops"] / (dt / steps) / 1e12 / 2500.0,
-                    "token_rows": S_run * T_run,
-                    "note": "achieved = 2 M N K of the frozen-weight GEMMs of one step (forward + activation gradients of 24 blocks, lm_head "
-                            "forward + dgrad; M = token_rows) / their duration between two HIP events on the decoder stream"}
-        except Exception as e:  # noqa: BLE001
-            roof = {"error": str(e)}
+        if with_roofline:   # (--full): a run of its own
+            try:
+                eng = model.engine()
+                S_run, T_run = eng.last_train_shape   # the sentences the step really fed (a region that is not detected is dropped)
+                t = eng.time_train_gemms(S_run, T_run, 3)
+                tf = t["gemm_flops"] / (t["ms_gemm"] * 1e-3) / 1e12
+                roof = {"bound": "mfma", "kernel": "gemm_bf16_pp_kernel (256 x 256 ping-pong, all GEMMs of the step at 14 848 rows)",
+                        "achieved": tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": tf / 2500.0, "traffic": None,
+                        "launches_per_step": t["gemm_launches"], "avg_launch_us": 1e3 * t["ms_gemm"] / t["gemm_launches"],
+                        "algorithmic_flops_per_launch": t["gemm_flops"] / t["gemm_launches"], "ms_gemm_per_step": t["ms_gemm"],
+                        "step_frac": t["gemm_flops"] / (dt / steps) / 1e12 / 2500.0,
+                        "token_rows": S_run * T_run,
+                        "note": "achieved = 2 M N K of the frozen-weight GEMMs of one step (forward + activation gradients of 24 blocks, lm_head "
+                                "forward + dgrad; M = token_rows) / their duration between two HIP events on the decoder stream"}
+            except Exception as e:  # noqa: BLE001
+                roof = {"error": str(e)}
         return {"workload": f"end-to-end training step, detector frozen, LM + binary-classifier heads, per-GPU batch=8 (232 sentences x {T} tokens), "
                             f"bf16 autocast, gradient all-reduce over {world} rank(s) on {n_buckets} flat buckets, HIP AdamW (BASELINE configs[4]"
                             + ("" if world == 8 else ": the 8-GPU shape at this N") + ")",
@@ -440,12 +478,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step (BASELINE configs[2] / configs[3]: 32; configs[1]: --batch 1 --dtype f32)")
     ap.add_argument("--max-length", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: rooflines, the secondary legs (`config1`, `beam4`, `config4`) and cpu_baseline; "
+                         "a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--no-cpu-baseline-all-cores", action="store_true",
-                    help="cpu_baseline skips its ONE full run of the oracle on all physical cores (~2 minutes on a 128-core host)")
+                    help="cpu_baseline (--full) skips its ONE full run of the oracle on all physical cores (~2 minutes on a 128-core host)")
     ap.add_argument("--cpu-baseline-all-cores", action="store_true", help=argparse.SUPPRESS)   # round-5 spelling: now the default
     ap.add_argument("--no-config2", "--no-extra-legs", dest="no_config2", action="store_true",
-                    help="skip the secondary legs of the default run: batch 1 in fp32 (BASELINE configs[1], `config1`), the scripts' beam mode "
+                    help="skip the secondary legs of a --full run: batch 1 in fp32 (BASELINE configs[1], `config1`), the scripts' beam mode "
                          "(`beam4`) and the training step (configs[4], `config4`)")
     ap.add_argument("--train", action="store_true", help="the headline line IS the training step (BASELINE configs[4]) instead of generate()")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="bf16",
@@ -510,8 +553,10 @@ def main():
 
     if args.train and not stub:
         # BASELINE configs[4] as the line itself: `--steps` training steps of 8 images per GPU
-        res4 = config4_line(model, synth, world, use_dist, dev, steps=args.steps)
+        res4 = config4_line(model, synth, world, use_dist, dev, steps=args.steps, with_roofline=args.full)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs({"losses": torch.tensor(res4["losses_last_step"], dtype=torch.float64)}, args.dump_outputs)
             res = {"metric": res4["metric"] + " (BASELINE configs[4]; the headline metric is generate(): run without --train)",
                    "value": res4["value"], "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": 1,
                    "ms_per_step": res4["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
@@ -550,6 +595,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     n_images = args.batch * world * args.steps
     S = 0 if isinstance(out, int) else int(out[0].shape[0])
@@ -574,20 +621,20 @@ def main():
         return
 
     default_workload = args.batch == 32 and args.dtype == "bf16" and args.max_length == 128
-    if default_workload:
+    if default_workload and args.full:
         res["config"]["note"] = ("headline = 32 images per GPU under bf16 autocast at every N: BASELINE configs[2] at N = 1, configs[3] at N = 8, one weak-"
                                  "scaling curve of ONE workload; the bit-exact fp32 batch-1 path (configs[1]) rides along as `config1`, the scripts' "
                                  "beam mode as `beam4`, the training step (configs[4]) as `config4`.  16-bit parity is statistical (README, DESIGN 7.2): "
                                  "token ids are bit-exact against the reference on the fp32 path only")
-    # rooflines of the two kernel families of the decode loop, dominant one first (timed live, HIP events), per rank 0
-    if rank == 0:
+    # --full: rooflines of the two kernel families of the decode loop, dominant one first (timed live, HIP events), per rank 0
+    if rank == 0 and args.full:
         try:
             S_dec = max(S // max(world, 1), 1)
             res["roofline"], res["roofline_secondary"] = rooflines(model.engine(), S_dec, args.dtype, args.max_length)
             res["roofline_detector"], res["roofline_roialign"] = detector_rooflines(model.engine(), images, args.dtype == "bf16")
         except Exception as e:  # noqa: BLE001
             res.setdefault("roofline", {"bound": "mfma", "error": str(e)})
-    extra = default_workload and not args.no_config2
+    extra = args.full and default_workload and not args.no_config2
     if extra and world == 1 and rank == 0:
         try:   # BASELINE configs[1]: batch 1, fp32, greedy, 29 x 128 tokens - the path whose token ids are bit-exact against the reference
             res["config1"] = dict(generate_leg(model, synth, 1, "f32", args.max_length, 5, 1, dev),
@@ -602,7 +649,7 @@ def main():
                                 metric="images/sec full 29-region report gen, 512x512 CXR, beam search num_beams=4 max_len=300")
         except Exception as e:  # noqa: BLE001
             res["beam4"] = {"error": str(e)}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(sd, images_cpu, args.max_length, all_cores_full_run=not args.no_cpu_baseline_all_cores)
     if extra:   # last: it updates the weights; every rank takes part (gradient all-reduce at N > 1)
         try:

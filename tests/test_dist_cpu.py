@@ -236,6 +236,34 @@ def test_bench_self_spawns_n_ranks_when_no_launcher_is_present():
     assert r["value"] > 0 and abs(r["value"] - 6 * 2 / (r["ms_per_step"] * 2e-3)) < 1e-6 * r["value"]
 
 
+def test_bench_dump_outputs_writes_what_the_last_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps, rank 0 writes the arrays generate() returned in the last step as
+    DIR/<name>.npy - token ids in float64, the rest in float32 - and a second run with the same arguments writes the same
+    arrays (seeded inputs).  On the CPU stub through the self-spawned launcher, like the test above."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    dumps = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0",
+                              "--batch", "2", "--max-length", "16", "--stub-cpu", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        r = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in sorted((tmp_path / run).glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"output_ids", "selected_regions", "detections_top_region_boxes", "detections_top_scores", "class_detected"}
+    assert a["output_ids"].dtype == np.float64 and a["output_ids"].shape == (4 * 29, 16)
+    assert all(a[k].dtype == np.float32 for k in a if k != "output_ids")
+    assert a["selected_regions"].shape == (4, 29) and a["detections_top_region_boxes"].shape == (4, 29, 4)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 # ------------------------------------------------------------------------- world 8 at the shape of BASELINE configs[3] (gloo)
 class _FakeModel8(_FakeModel):
     """Rank 5 selects nothing (its generate() is never called: the reference returns -1 there, generate_sharded must still

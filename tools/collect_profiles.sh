@@ -15,9 +15,9 @@ export TMPDIR=/tmp
 cd /tmp
 
 # round 6: the default bench line is batch 32 under bf16 autocast (BASELINE configs[2]); batch 1 in fp32 (configs[1]) is asked for
-B1="python $ROOT/bench.py --no-cpu-baseline --no-extra-legs --batch 1 --dtype f32 --steps 3 --warmup 1"
-B32="python $ROOT/bench.py --no-cpu-baseline --no-extra-legs --steps 2 --warmup 1"
-P1="python $ROOT/bench.py --no-cpu-baseline --no-extra-legs --batch 1 --dtype f32 --steps 1 --warmup 0"
+B1="python $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --batch 1 --dtype f32 --steps 3 --warmup 1"
+B32="python $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --steps 2 --warmup 1"
+P1="python $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --batch 1 --dtype f32 --steps 1 --warmup 0"
 # batch-32 counter passes: the many-sequence decode process alone with its steps launched EAGERLY, the row ranges one after the
 # other on one stream - rocprofv3 --pmc segfaults on the hipGraph replays of that step; on the final round-5 tree it does not
 # survive this form either (profiles/r05_rocprofv3_pmc_crash_reproducer.md), the two passes then leave no CSV and
