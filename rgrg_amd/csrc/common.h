@@ -92,13 +92,6 @@ __device__ __forceinline__ float from16(unsigned h) {
 __device__ __forceinline__ unsigned to16_rt(float f, int f16) { return f16 ? f32_to_f16_bits(f) : f32_to_bf16_bits(f); }
 __device__ __forceinline__ float from16_rt(unsigned h, int f16) { return f16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h); }
 
-// XCD (accelerator complex die, 0..7) this wave runs on: every XCD has its own 4 MiB L2
-__device__ __forceinline__ int xcc_id() {
-    int x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
-    return x;
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

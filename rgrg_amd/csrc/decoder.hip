@@ -511,12 +511,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
                                                           float* __restrict__ kc, float* __restrict__ vc,
                                                           const int* __restrict__ step, float* __restrict__ out,
                                                           int S, int H, int T, const int* __restrict__ src, int frag_out,
-                                                          unsigned long long* __restrict__ stamps,   // stamps: -DRGRG_SKINNY_STAMPS builds, else null
                                                           const float* __restrict__ kmask = nullptr) {
     __shared__ float pm[16], pl[16];
     __shared__ __attribute__((aligned(16))) float pacc[16][64];
-    SKS_DECL;
-    SKS(0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x / H, hd = blockIdx.x - s * H;
     const int t = *step, nkeys = t + 2, slot = t + 1;
@@ -551,7 +548,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
         for (int base = 0; base < nkeys; base += ATT_CHUNK) ATT_CHUNK_CALL(ATT_NI, base);
     }
 #undef ATT_CHUNK_CALL
-    SKS(1);   // stamp 1 (after a read of the running sums: the chunk's loads have landed and its arithmetic is issued)
     if (wave == 0 && g == 0) {
         *reinterpret_cast<f32x4*>(kc + (((size_t)s * H + hd) * T + slot) * 64 + d4 * 4) = k4;
         *reinterpret_cast<f32x4*>(vc + (((size_t)s * H + hd) * T + slot) * 64 + d4 * 4) = v4;
@@ -559,9 +555,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
     const int grp = wave * 4 + g;
     if (d4 == 0) { pm[grp] = m; pl[grp] = l; }
     *reinterpret_cast<f32x4*>(&pacc[grp][d4 * 4]) = acc;
-    SKS(3);   // stamp 3: wave 0's partial sums written to LDS (depends on every key of the wave)
     __syncthreads();
-    SKS(4);
     if (threadIdx.x < 64) {
         float M = pm[0];
 #pragma unroll
@@ -576,8 +570,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
         // fused plan: the attention output is attn_proj's A operand -> fragment-major (skinny_direct.inc)
         out[frag_out ? frag_off(s, hd * 64 + threadIdx.x, D) : (size_t)s * D + hd * 64 + threadIdx.x] = o / L;
     }
-    SKS(5);
-    SKS_FLUSH(stamps, blockIdx.x);
 }
 
 // bf16 helpers for the opt-in bf16 K/V cache (torch.autocast(bf16) in the reference makes c_attn's output,
@@ -783,21 +775,6 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     }   // items
 }
 
-// Measurement hook kernel: where the hardware put every workgroup - HW_ID (wave / SIMD / CU / SH / SE fields) and XCC_ID
-__global__ __launch_bounds__(64) void hw_ids_kernel(unsigned* __restrict__ out) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    __builtin_amdgcn_s_sleep(64);
-    if (threadIdx.x == 0) { out[2 * blockIdx.x] = hwid; out[2 * blockIdx.x + 1] = xcc; }
-}
-extern "C" int rgrg_debug_hw_ids(unsigned* out, int n_wgs, void* stream) {
-    RGRG_CHECK_ARG(out && n_wgs > 0);
-    hipLaunchKernelGGL(hw_ids_kernel, dim3(n_wgs), dim3(64), 0, as_stream(stream), out);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
-}
-
 // image key/value (uk/uv outputs) -> cache slot 0 of every layer
 template <typename KV>  // float, or u16 (bf16 cache)
 __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__ ukv, int ld, KV* __restrict__ kv_all,
@@ -938,8 +915,6 @@ __global__ __launch_bounds__(256) void decode_reset_kernel(long long* __restrict
         if (threadIdx.x < 2) sync[threadIdx.x] = 0;
     }
 }
-
-#include "persistent.inc"
 
 // ------------------------------------------------------------------ beam search kernels
 constexpr int BEAM_K = 32;  // max 2*num_beams candidates per row (num_beams <= 16)
@@ -1713,8 +1688,6 @@ struct rgrg_decoder {
     unsigned* sk_cnt = nullptr;
     int sk_attn = 0, sk_mlp = 0; // K slices of attn_proj / mlp_proj there (RGRG_SK_ATTN / RGRG_SK_MLP; 1 = off; -1 = automatic: 2 / 4 slices for a
                                  // step of <= 256 rows - 32-64 output tiles for 256 CUs - and none above)
-    int sk_cons = 1;             // K slices of c_attn / c_fc in a step of <= 256 rows (RGRG_SK_CONS, opt-in: measured slower, r06_small_rows_splitk.log)
-    size_t sk_slabs = 0;         // 64 x 64 fp32 slabs in sk_ws
     int step_rows = 0;           // token rows of the many-sequence step being enqueued (all row ranges together)
     float* ln_stat = nullptr;   // [rows][16][2]: per-row (sum, sum of squares) slots (one per 64 columns) of the residual stream (folded LayerNorm)
     bool ln_fold = true;        // 16-bit path: LayerNorms folded into the GEMMs around them; RGRG_LN_FOLD=0: ln_rows launches (A/B)
@@ -1734,39 +1707,19 @@ struct rgrg_decoder {
     int gemm_launches_per_step = 0;
     void* a16_scratch = nullptr;   // bf16 copy of an fp32 GEMM input (teacher-forced / training passes under autocast)
     size_t a16_bytes = 0;
-    // persistent decode kernel (persistent.inc), greedy decode of <= 32 rows.  pk_mode: 0 = the launch chain, 1 = c_fc' + mlp_proj
-    // of a layer in one launch, 2 = attn_proj' .. mlp_proj, 3 = attention .. mlp_proj, 4 = one launch per layer, 5 = one
-    // launch per decode step (all layers + lm_head' + arg-max).  RGRG_PERSISTENT overrides the default.
     const int* pos_override_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached: per-row embedding positions
     int* row_pos = nullptr;                  // [rows] buffer behind it
-    int pk_mode = 0;
-    std::vector<PkLayer> pk_layers;   // per-layer pointer table (copied into the kernel arguments)
-    unsigned* pk_bar = nullptr;     // barrier state (persistent.inc), zeroed at creation
-    unsigned long long* pk_dbg = nullptr;   // RGRG_PK_TRACE=<file>: cycle stamps of the last persistent launch, dumped at destruction
-    // -DRGRG_SKINNY_STAMPS builds + RGRG_SKINNY_TRACE=<file> (tools/skinny_stamps.py): phase stamps of every launch of the last
-    // fused decode step, [launch slot][workgroup][8]; null in the product build
     // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
     // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
     int logits_stale_rows = 0;
     bool logits_valid = false;   // d->logits / the retained ln_f rows belong to the last step of a completed generate / beam / cached call (ADVICE r05:
                                  // the timing hooks and a precision change overwrite them - rgrg_decoder_copy_last_logits then refuses)
     // enqueue_step: extra streams + fork / join events of the multi-range many-sequence step (RGRG_DECODE_CHAINS)
-    // free-running row ranges (round 6, rgrg_decoder_generate): every range owns a step counter / done length / ticket word
-    // (range_state [MAX_CHAINS][4] on the device), a step graph and a stream, and never meets the other ranges inside the loop
-    int* range_state = nullptr;
-    int* step_ptr = nullptr;            // the step counter the kernels of the launch being enqueued read (default: step)
-    int* h_rdone = nullptr;             // pinned [3][MAX_CHAINS]: two in-flight polls + the final read
-    hipEvent_t ev_rpoll[2][MAX_CHAINS] = {};
-    bool free_ranges = false;           // RGRG_DECODE_FREE=1 (opt-in, measured: profiles/r06_free_ranges_ab.log); default: the ranges join in
-                                        // front of the lm_head in every step
     hipStream_t streams_x[MAX_CHAINS - 1] = {};
     hipEvent_t ev_fork = nullptr, ev_join[MAX_CHAINS - 1] = {};
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
                       // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
-    unsigned long long* sk_stamps = nullptr;
-    int sk_stamp_next = 0;
-    std::vector<std::pair<const char*, int>> sk_stamp_meta;   // (kernel, workgroups) per slot
 };
 
 namespace rgrg {
@@ -1881,15 +1834,6 @@ static int skinny_max_rows16(bool w16) {
 static int decode_row_limit(const rgrg_decoder* d) { return d->bf16_gemms ? skinny_max_rows16(d->w16_fused) : skinny_max_rows(); }
 static bool kv_is_bf16(const rgrg_decoder* d, int rows) { return d->bf16_gemms && rows > decode_row_limit(d); }
 
-// Measurement builds: the stamp block of the next launch of the fused decode step (null in the product build / without
-// RGRG_SKINNY_TRACE).  The pointers are baked into the captured graph, so a dump holds the LAST replayed step.
-constexpr int SK_STAMP_SLOTS = 128, SK_STAMP_WGS = 512;
-static unsigned long long* stamp_slot(rgrg_decoder* d, const char* kernel, int wgs) {
-    if (!d->sk_stamps || d->sk_stamp_next >= SK_STAMP_SLOTS || wgs > SK_STAMP_WGS) return nullptr;
-    d->sk_stamp_meta.emplace_back(kernel, wgs);
-    return d->sk_stamps + (size_t)(d->sk_stamp_next++) * SK_STAMP_WGS * 8;
-}
-
 // Y[:M] = act(X W^T + b + R).  Prefill GEMMs (packed, <= 128 rows): LDS-staged weight-streaming kernel (+ a small
 // reduce kernel when the layer splits K over workgroups); everything else: tiled MFMA GEMM (fp32, or the bf16-weight
 // kernel in the opt-in bf16 mode, optionally with bf16 activations in / out).
@@ -1923,14 +1867,6 @@ static int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R,
             GemmLnFold f = *ln;
             f.ln_colsum = l.cs16;
             f.kp = (d->kp_gemms == 1 || d->kp_gemms == 3) ? 1 : 0;
-            // opt-in (RGRG_SK_CONS=2), a step of <= 256 rows (no row ranges): c_attn / c_fc on two K slices per tile, the last arriver runs
-            // the folded-LayerNorm epilogue on the sum - 96-128 tiles already keep half the CUs busy and the hand-off costs more than the
-            // 8 K tiles it saves (1 image x 4 beams 500 -> 542 ms)
-            int ks = d->sk_cons;
-            if (ks > 1 && d->sk_ws && d->xn16 && M <= 256 && (size_t)((M + 127) / 128) * 2 * (l.N / 64) * ks <= d->sk_slabs) {
-                const size_t r0 = (size_t)(reinterpret_cast<const unsigned short*>(X16) - d->xn16) / (size_t)d->D;
-                if (r0 == 0) { f.kp = 0; f.ksplit = ks; f.sk_ws = d->sk_ws; f.sk_cnt = d->sk_cnt; }
-            }
             return launch_gemm_bf16w_ex(nullptr, X16, l.wb_ln, l.c2_16, R, Y16 ? nullptr : Y, Y16, M, l.N, l.K, ldy, act, d->stream, d->f16(), &f);
         }
         if (ln && ln->Yb16 && d->sk_ws && M <= d->rows) {
@@ -1991,17 +1927,16 @@ static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsig
         const dim3 wgrid(cap > 0 ? std::min(wgs, cap * 256) : wgs), wblk(256);
         u16* kc16r = kc16 + (size_t)r0 * d->H * d->T * 64;   // cache rows of sequence r0 (layout [sequence][head][slot][64])
 #define KV16_LAUNCH(SRC_, F16_) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<SRC_, F16_>), wgrid, wblk, 0, st, d->qkv + (size_t)r0 * 3 * D, 3 * D, kc16r, \
-                                                  kc16r + d->kv_kv_stride, d->step_ptr, d->att + (size_t)r0 * D, S, d->H, d->T, src, att16)
+                                                  kc16r + d->kv_kv_stride, d->step, d->att + (size_t)r0 * D, S, d->H, d->T, src, att16)
         if (src) { if (d->f16()) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
         else { if (d->f16()) KV16_LAUNCH(false, true); else KV16_LAUNCH(false, false); }
 #undef KV16_LAUNCH
     } else {
         const dim3 grid(S * d->H), blk(256);
-#define ATT_LAUNCH(SRC_, NI_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step_ptr, d->att, S, d->H, d->T, src, frag_out, \
-                                                 stamp_slot(d, "attention", S * d->H))
+#define ATT_LAUNCH(SRC_, NI_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step, d->att, S, d->H, d->T, src, frag_out)
         if (d->key_mask_cur && !src) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
-#define ATT_LAUNCH_MASK(NI_) hipLaunchKernelGGL((attn_decode_kernel<false, NI_, true>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step_ptr, d->att, S, d->H, d->T, \
-                                                  src, frag_out, (unsigned long long*)nullptr, d->key_mask_cur)
+#define ATT_LAUNCH_MASK(NI_) hipLaunchKernelGGL((attn_decode_kernel<false, NI_, true>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step, d->att, S, d->H, d->T, \
+                                                  src, frag_out, d->key_mask_cur)
             if (S * d->H <= 4096) ATT_LAUNCH_MASK(9); else ATT_LAUNCH_MASK(2);
 #undef ATT_LAUNCH_MASK
         } else if (S * d->H <= 4096) { if (src) ATT_LAUNCH(true, 9); else ATT_LAUNCH(false, 9); }
@@ -2027,14 +1962,11 @@ static int direct_linear(rgrg_decoder* d, const Lin& l, DirectArgs a, int mode, 
     const dim3 grid(l.NT, l.KS), blk(64 * SK_WAVES);
     hipStream_t st = d->stream;
     if (l.lnf && mode == DX_COMBINE4 && l.NT > 512 && mt == 1 && l.K == DK_SLICE) {  // lm_head, one row tile: a wave per column tile
-        a.stamps = stamp_slot(d, "lm_head'", 256);
         hipLaunchKernelGGL((rgrg_lm_head_wave_f32<DX_COMBINE4>), dim3(256), blk, LMH_LDS, st, a);
     } else if (!l.lnf && mode == DX_PLAIN && l.KS == 1 && mt == 1 && l.NT <= 64 && M > 16 && !cand) {
         // attn_proj': few column tiles, MFMA bound -> one row half per workgroup (2 x NT workgroups)
-        a.stamps = stamp_slot(d, "attn_proj'", l.NT * 2);
         hipLaunchKernelGGL(rgrg_skinny_direct_half_f32, dim3(l.NT, 2), blk, 0, st, a);
     } else {
-        a.stamps = stamp_slot(d, l.N == 3 * d->D ? "c_attn'" : l.KS > 1 ? "mlp_proj" : l.N == 4 * d->D ? "c_fc'" : "skinny_direct", l.NT * l.KS);
 #define DX_LAUNCH(MT_, MODE_, LNF_)                                                                                          \
     do {                                                                                                                      \
         if constexpr (MT_ > 1) {                                                                                              \
@@ -2073,7 +2005,7 @@ static int direct_linear(rgrg_decoder* d, const Lin& l, DirectArgs a, int mode, 
 // The GEMMs of layer l of the fused plan (everything but the attention); `cur` holds x_mid of the previous layer in
 // fragment-major order with its mlp_proj partial sums pending in d->part, `nxt` receives this layer's residual stream.
 static int enqueue_layer_gemms(rgrg_decoder* d, int l, int S, bool count, const int* tok_override, const float* cur, float* nxt,
-                               int part) {  // part: 0 = c_attn', 1 = attn_proj' .. mlp_proj, 2 = attn_proj' only
+                               int part) {  // part: 0 = c_attn', 1 = attn_proj' .. mlp_proj
     const LayerW& w = d->layers[l];
     const int D = d->D;
     int rc;
@@ -2095,42 +2027,12 @@ static int enqueue_layer_gemms(rgrg_decoder* d, int l, int S, bool count, const 
     p.Xf = d->att; p.Rf = nxt; p.Yf = nxt; p.act = RGRG_ACT_NONE;  // its epilogue also zeroes mlp_proj's accumulators
     p.zero_acc = d->part;
     if ((rc = direct_linear(d, w.attn_proj, p, DX_PLAIN, S, count))) return rc;
-    if (part == 2) return RGRG_OK;   // attn_proj' alone (c_fc' + mlp_proj follow as one persistent launch)
     DirectArgs f{};  // c_fc': gelu_new(ln_2(x) W^T + b)
     f.Xf = nxt; f.Yf = d->ff; f.act = RGRG_ACT_GELU_NEW;
     if ((rc = direct_linear(d, w.c_fc, f, DX_PLAIN, S, count))) return rc;
     DirectArgs m{};  // mlp_proj: 4 K slices accumulate pairwise into d->part (slice 0 carries the bias)
     m.Xf = d->ff; m.act = RGRG_ACT_NONE;
     return direct_linear(d, w.mlp_proj, m, DX_PLAIN, S, count);
-}
-
-static PkArgs pk_args(rgrg_decoder* d, int S, int l0, int l1) {
-    PkArgs a{};
-    for (size_t l = 0; l < d->pk_layers.size(); ++l) a.layers[l] = d->pk_layers[l];
-    a.x = d->x; a.x2 = d->x2; a.qkv = d->qkv; a.att = d->att; a.ff = d->ff; a.part = d->part;
-    a.wte = d->wte; a.ids = d->ids; a.ld_ids = d->max_len; a.step = d->step;
-    a.lm_P = d->lm_head.packed; a.lm_c1 = d->lm_head.c1; a.lm_c2 = d->lm_head.c2;
-    a.logits = d->logits; a.ld_logits = d->ld_logits; a.cand_val = d->cand_val; a.cand_idx = d->cand_idx;
-    a.lm_NT = d->lm_head.NT; a.V = d->V;
-    a.finished = d->finished; a.done_len = d->done_len; a.sync = d->sync;
-    a.bar = d->pk_bar;
-    a.S = S; a.H = d->H; a.T = d->T; a.n_layer = d->n_layer; a.l0 = l0; a.l1 = l1;
-    a.dbg = d->pk_dbg;
-    return a;
-}
-
-template <int K0, bool FULL>
-static int pk_launch(rgrg_decoder* d, int S, int l0, int l1) {
-    const PkArgs a = pk_args(d, S, l0, l1);
-    const size_t lds = FULL ? LMH_LDS : (size_t)(SK_WAVES * 8 * 64 + SK_WAVES * 32 * 2 + 512) * sizeof(float);
-    hipLaunchKernelGGL((rgrg_persistent_decode_f32<K0, 5, FULL>), dim3(PK_WGS), dim3(512), lds, d->stream, a);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
-}
-
-static void pk_count(rgrg_decoder* d, int S, const Lin& l) {   // bookkeeping of the roofline figures (bytes / flops per step)
-    d->gemm_bytes_per_step += (size_t)l.N * l.K * sizeof(float);
-    d->gemm_flops_per_step += 2.0 * S * l.N * l.K;
 }
 
 // One decode step of the fused plan (<= 128 token rows): 24 * 5 + 2 = 122 launches
@@ -2140,57 +2042,14 @@ static void pk_count(rgrg_decoder* d, int S, const Lin& l) {   // bookkeeping of
 // The residual stream ping-pongs between d->x and d->x2; x, att, ff and the partial sums are fragment-major.
 static int enqueue_step_fused(rgrg_decoder* d, int S, bool count, const int* tok_override, const int* src, bool beam) {
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
-    d->sk_stamp_next = 0; d->sk_stamp_meta.clear();
     hipStream_t st = d->stream;
     int rc;
     float* cur = d->x;
     float* nxt = d->x2;
-    const int pk = (S <= PAD_ROWS && !beam && !tok_override && !src && !d->pk_layers.empty()) ? d->pk_mode : 0;
-    if (pk >= 4) {   // persistent.inc: one launch per layer, or one per step
-        if (count) {
-            for (int l = 0; l < d->n_layer; ++l) {
-                const LayerW& w = d->layers[l];
-                pk_count(d, S, w.c_attn); pk_count(d, S, w.attn_proj); pk_count(d, S, w.c_fc); pk_count(d, S, w.mlp_proj);
-            }
-            pk_count(d, S, d->lm_head);
-        }
-        if (pk == 5) {
-            if (count) d->gemm_launches_per_step = 1;
-            return pk_launch<0, true>(d, S, 0, d->n_layer);
-        }
-        for (int l = 0; l < d->n_layer; ++l)
-            if ((rc = pk_launch<0, false>(d, S, l, l + 1))) return rc;
-        if (count) d->gemm_launches_per_step = d->n_layer + 1;
-        cur = (d->n_layer & 1) ? d->x2 : d->x;
-        DirectArgs h{};
-        h.Xf = cur; h.part = d->part; h.Y = d->logits; h.ldy = d->ld_logits; h.act = RGRG_ACT_NONE;
-        if ((rc = direct_linear(d, d->lm_head, h, DX_COMBINE4, S, false, true))) return rc;
-        hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, d->lm_head.NT, d->ids,
-                           d->max_len, d->finished, d->step, d->done_len, d->sync, S);
-        RGRG_LAUNCH_CHECK();
-        return RGRG_OK;
-    }
     for (int l = 0; l < d->n_layer; ++l) {
         if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 0))) return rc;
-        if (pk == 3) {          // attention .. mlp_proj in one launch
-            if ((rc = pk_launch<1, false>(d, S, l, l + 1))) return rc;
-        } else {
-            if ((rc = launch_attention(d, l, S, src, nullptr, 1))) return rc;
-            if (pk == 2) {      // attn_proj' .. mlp_proj
-                if ((rc = pk_launch<2, false>(d, S, l, l + 1))) return rc;
-            } else if (pk == 1) {   // c_fc' + mlp_proj
-                if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 2))) return rc;
-                if ((rc = pk_launch<3, false>(d, S, l, l + 1))) return rc;
-            } else {
-                if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 1))) return rc;
-            }
-        }
-        if (pk && count) {
-            const LayerW& w = d->layers[l];
-            if (pk >= 2) pk_count(d, S, w.attn_proj);
-            pk_count(d, S, w.c_fc); pk_count(d, S, w.mlp_proj);
-            d->gemm_launches_per_step += 1;
-        }
+        if ((rc = launch_attention(d, l, S, src, nullptr, 1))) return rc;
+        if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 1))) return rc;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     DirectArgs h{};
@@ -2266,12 +2125,8 @@ static int trace_mark(rgrg_decoder* d, int r0, int tag) {
 // One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
 //   embed+ln1 | per layer: c_attn, attention, attn_proj (+ residual), ln2, c_fc+gelu, mlp_proj (+ residual),
 //   ln1 of the next layer / ln_f | lm_head, per-32-column arg-max candidates, argmax + bookkeeping
-// `only`: free-running row ranges (rgrg_decoder_generate): enqueue the step of ONE range - rows [only->r0, + rows), its lm_head
-// (arg-max epilogue) and its own arg-max / bookkeeping on the range's state words (d->step_ptr = state, + 1 done length, + 2 ticket)
-// - on d->stream; greedy 16-bit folded step only
-struct RangeSpec { int r0, rows; };
 static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = nullptr, const int* src = nullptr,
-                        bool beam = false, const RangeSpec* only = nullptr) {
+                        bool beam = false) {
     if (S <= decode_row_limit(d)) return enqueue_step_fused(d, S, count, tok_override, src, beam);
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     d->step_rows = S;
@@ -2310,7 +2165,7 @@ static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_overr
         prod_r.Yb16 = xn16r; prod_r.stats_out = statr; cons_r.ln_stats = statr;
         const GemmLnFold* pfr = fold ? &prod_r : nullptr;
         const GemmLnFold* cfr = fold ? &cons_r : nullptr;
-        hipLaunchKernelGGL(embed_ln_kernel, dim3(rows), dim3(256), 0, rs, d->wte, d->ids + (size_t)r0 * d->max_len, d->max_len, d->step_ptr,
+        hipLaunchKernelGGL(embed_ln_kernel, dim3(rows), dim3(256), 0, rs, d->wte, d->ids + (size_t)r0 * d->max_len, d->max_len, d->step,
                            d->layers[0].ln1_g, d->layers[0].ln1_b, x, xn, D, tok_override ? tok_override + r0 : nullptr, xn16r, d->f16(),
                            d->pos_override_cur ? d->pos_override_cur + r0 : nullptr, fold ? statr : (float*)nullptr);
         RGRG_LAUNCH_CHECK();
@@ -2342,19 +2197,6 @@ static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_overr
         }
         return RGRG_OK;
     };
-    if (only) {
-        if (beam || tok_override || src || !fold || !lm_head_cand_path(d, S)) { set_error("decoder: a row-range step needs the greedy 16-bit folded path"); return RGRG_EINVAL; }
-        if ((rc = run_rows(only->r0, only->rows))) return rc;
-        const int nt = (d->lm_head.N + 255) / 256;
-        const size_t o = (size_t)only->r0 * D;
-        GemmLnFold ce{};
-        ce.cand_val = d->cand_val + (size_t)only->r0 * nt; ce.cand_idx = d->cand_idx + (size_t)only->r0 * nt;
-        if ((rc = linear(d, d->lm_head, d->xn + o, nullptr, nullptr, only->rows, d->ld_logits, RGRG_ACT_NONE, count, xn16 + o, nullptr, &ce))) return rc;
-        hipLaunchKernelGGL(argmax_update_kernel, dim3(only->rows), dim3(256), 0, st, ce.cand_val, ce.cand_idx, nt, d->ids + (size_t)only->r0 * d->max_len,
-                           d->max_len, d->finished + only->r0, d->step_ptr, d->step_ptr + 1, d->step_ptr + 2, only->rows);
-        RGRG_LAUNCH_CHECK();
-        return RGRG_OK;
-    }
     if ((rc = run_row_ranges(d, S, step_chains(d, S, !beam && !tok_override && !src, fold), run_rows))) return rc;
     if (!beam && xn16 && lm_head_cand_path(d, S)) {
         // greedy: the 256 x 256 lm_head leaves one (maximum, column) pair per row and column tile; no logits, no candidates pass
@@ -2454,14 +2296,7 @@ extern "C" int rgrg_decoder_create_with_cache(const rgrg_decoder_weights* w, int
         }
     }
     if (hipHostMalloc((void**)&d->h_id_error, sizeof(int), 0) == hipSuccess) *d->h_id_error = 0;
-    if (const char* e = getenv("RGRG_DECODE_FREE")) d->free_ranges = atoi(e) != 0;
-    {
-        bool ok = hipHostMalloc((void**)&d->h_rdone, 3 * MAX_CHAINS * sizeof(int), 0) == hipSuccess;
-        for (int a = 0; ok && a < 2; ++a)
-            for (int i = 0; ok && i < MAX_CHAINS; ++i) ok = hipEventCreateWithFlags(&d->ev_rpoll[a][i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { set_error("decoder: pinned memory / event creation failed"); rgrg_decoder_destroy(d); return RGRG_EHIP; }
-    }
-    if (hipHostMalloc((void**)&d->h_done, 4 * sizeof(int), 0) != hipSuccess ||
+    if (hipHostMalloc((void**)&d->h_done, 3 * sizeof(int), 0) != hipSuccess ||
         hipEventCreateWithFlags(&d->ev_poll[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&d->ev_poll[1], hipEventDisableTiming) != hipSuccess) {
         set_error("decoder: hipHostMalloc failed");
@@ -2513,8 +2348,6 @@ extern "C" int rgrg_decoder_create_with_cache(const rgrg_decoder_weights* w, int
     TRY(dmalloc(d, (void**)&d->next, R * 4, true));
     TRY(dmalloc(d, (void**)&d->finished, R * 4, true));
     TRY(dmalloc(d, (void**)&d->step, 4, true));
-    d->step_ptr = d->step;
-    TRY(dmalloc(d, (void**)&d->range_state, MAX_CHAINS * 4 * sizeof(int), true));
     TRY(dmalloc(d, (void**)&d->done_len, 4, true));
     TRY(dmalloc(d, (void**)&d->sync, 64, true));
     TRY(dmalloc(d, (void**)&d->id_error, 8, true));
@@ -2533,37 +2366,6 @@ extern "C" int rgrg_decoder_create_with_cache(const rgrg_decoder_weights* w, int
     TRY(dmalloc(d, (void**)&d->cand_score, R * BEAM_K * 4, true));
     TRY(dmalloc(d, (void**)&d->cand_tok, R * BEAM_K * 4, true));
     TRY(dmalloc(d, (void**)&d->cand_beam, R * BEAM_K * 4, true));
-    {   // persistent decode kernel (persistent.inc): per-layer pointer table + barrier state
-        std::vector<PkLayer> tab(w->n_layer <= PK_MAX_LAYERS ? w->n_layer : 0);
-        for (int l = 0; l < (int)tab.size(); ++l) {
-            const LayerW& t = d->layers[l];
-            PkLayer& p = tab[l];
-            p.attn_P = t.c_attn.packed; p.attn_c1 = t.c_attn.c1; p.attn_c2 = t.c_attn.c2;
-            p.proj_P = t.attn_proj.packed; p.proj_b = t.attn_proj.b;
-            p.fc_P = t.c_fc.packed; p.fc_c1 = t.c_fc.c1; p.fc_c2 = t.c_fc.c2;
-            p.mlp_P = t.mlp_proj.packed; p.mlp_b = t.mlp_proj.b;
-            p.kc = d->kv + (size_t)l * d->kv_layer_stride;
-            p.vc = p.kc + d->kv_kv_stride;
-        }
-        d->pk_layers = tab;
-        TRY(dmalloc(d, (void**)&d->pk_bar, (size_t)PK_BAR_SLOTS * 16 * sizeof(unsigned), true));
-        hipDeviceProp_t prop;
-        int dev = 0;
-        d->pk_mode = 0;
-        if (const char* e = getenv("RGRG_PERSISTENT")) d->pk_mode = atoi(e);
-        if (getenv("RGRG_PK_TRACE")) TRY(dmalloc(d, (void**)&d->pk_dbg, (size_t)PK_WGS * 64 * sizeof(unsigned long long), true));
-#ifdef RGRG_SKINNY_STAMPS
-        if (getenv("RGRG_SKINNY_TRACE"))
-            TRY(dmalloc(d, (void**)&d->sk_stamps, (size_t)SK_STAMP_SLOTS * SK_STAMP_WGS * 8 * sizeof(unsigned long long), true));
-#endif
-        // one workgroup per CU, all resident: needs the 256 CUs of an MI355X and a D = 1024 / 16-head model
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < PK_WGS ||
-            d->D != DK_SLICE || d->H != 16)
-            d->pk_mode = 0;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rgrg_persistent_decode_f32<0, 5, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LMH_LDS) != hipSuccess)
-            d->pk_mode = d->pk_mode == 5 ? 0 : d->pk_mode;
-    }
     d->gemm_ws_floats = (d->max_seqs > 32) ? (size_t)16 * R * 4 * D : 0;  // split-K partials of the tiled GEMM
     d->gemm_ws = nullptr;
     if (d->gemm_ws_floats) TRY(dmalloc(d, (void**)&d->gemm_ws, d->gemm_ws_floats * 4, false));
@@ -2585,42 +2387,12 @@ static void tr_free(rgrg_decoder* d);
 
 extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
     if (!d) return;
-    if (d->pk_dbg) {   // measurement aid (tools/persistent_trace.py): the stamps of the last persistent launch
-        if (const char* path = getenv("RGRG_PK_TRACE")) {
-            std::vector<unsigned long long> h((size_t)PK_WGS * 64);
-            if (hipDeviceSynchronize() == hipSuccess &&
-                hipMemcpy(h.data(), d->pk_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
-            }
-        }
-    }
-    if (d->sk_stamps) {   // measurement builds (tools/skinny_stamps.py): text dump, one line per workgroup of every launch slot
-        const char* path = getenv("RGRG_SKINNY_TRACE");
-        std::vector<unsigned long long> h((size_t)SK_STAMP_SLOTS * SK_STAMP_WGS * 8);
-        if (path && hipDeviceSynchronize() == hipSuccess &&
-            hipMemcpy(h.data(), d->sk_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE* f = fopen(path, "w")) {
-                for (size_t sl = 0; sl < d->sk_stamp_meta.size(); ++sl) {
-                    fprintf(f, "slot %zu %s %d\n", sl, d->sk_stamp_meta[sl].first, d->sk_stamp_meta[sl].second);
-                    for (int w = 0; w < d->sk_stamp_meta[sl].second; ++w) {
-                        const unsigned long long* r = h.data() + (sl * SK_STAMP_WGS + w) * 8;
-                        fprintf(f, "%llu %llu %llu %llu %llu %llu %llu %llu\n", r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]);
-                    }
-                }
-                fclose(f);
-            }
-        }
-    }
     for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);
     for (void* p : d->allocs) (void)hipFree(p);
     tf_free(d);
     tr_free(d);
     if (d->a16_scratch) (void)hipFree(d->a16_scratch);
     if (d->h_done) (void)hipHostFree(d->h_done);
-    if (d->h_rdone) (void)hipHostFree(d->h_rdone);
-    for (auto& a : d->ev_rpoll)
-        for (hipEvent_t e : a)
-            if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->ev_poll)
         if (e) (void)hipEventDestroy(e);
     if (d->h_id_error) (void)hipHostFree(d->h_id_error);
@@ -2646,94 +2418,6 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
     int rc = enqueue_prefill(d, feats, S);
     if (rc) return rc;
 
-    // Free-running row ranges (round 6, OPT-IN: RGRG_DECODE_FREE=1): in the many-sequence 16-bit greedy mode every kernel of a step
-    // is row-local - embedding, the 24 layers, ln_f, lm_head (arg-max epilogue), arg-max and the EOS bookkeeping - so each row range
-    // can own a step graph, a stream and state words and replay its steps without ever meeting the other ranges (no join in front
-    // of the lm_head, nobody waits for the slowest chain).  Same kernels per row: ids identical (tests).  Measured
-    // (profiles/r06_free_ranges_ab.log): 3 free ranges 2.725 ms per step against 2.764 for 4 joined ranges - the step is bound by
-    // what its kernels consume together, not by the order they run in - and 4 free ranges on this process's 4 hardware queues
-    // 4.08 ms: a HIP stream is bound to one of GPU_MAX_HW_QUEUES (4) hardware queues, a process holds more streams than that
-    // (torch's, the decoder's; RCCL adds its own), and two ranges that land on one queue serialise - the joined step's graph lets
-    // the runtime place its branches.  Not the default for that reason.
-    {
-        int bounds[MAX_CHAINS + 1];
-        const bool xn16 = kv_is_bf16(d, S) && d->xn16;
-        const bool fold = xn16 && d->ln_fold && d->ln_stat && d->layers[0].c_attn.wb_ln && d->D == 1024;
-        const int want = step_chains(d, S, true, fold);
-        const int nr = (use_graph && d->free_ranges && want > 1 && fold && lm_head_cand_path(d, S) && d->h_rdone) ? range_bounds(S, want, bounds) : 1;
-        if (nr > 1) {
-            hipGraphExec_t ex[MAX_CHAINS] = {};
-            hipStream_t rs[MAX_CHAINS];
-            for (int i = 0; i < nr; ++i) rs[i] = i ? d->streams_x[i - 1] : d->stream;
-            for (int i = 0; i < nr; ++i) {
-                for (auto& g : d->graphs)
-                    if (g.S == S && g.key2 == 100 + i && g.key3 == nr) ex[i] = g.exec;
-                if (ex[i]) continue;
-                hipGraph_t graph = nullptr;
-                const RangeSpec spec{bounds[i], bounds[i + 1] - bounds[i]};
-                std::swap(d->stream, rs[i]);       // (i == 0: a swap with itself)
-                d->step_ptr = d->range_state + 4 * i;
-                hipError_t e = hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal);
-                if (e == hipSuccess) {
-                    rc = enqueue_step(d, S, false, nullptr, nullptr, false, &spec);
-                    e = hipStreamEndCapture(d->stream, &graph);
-                }
-                d->step_ptr = d->step;
-                std::swap(d->stream, rs[i]);
-                if (rc) return rc;
-                if (e != hipSuccess) { set_error("range step capture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
-                RGRG_HIP(hipGraphInstantiate(&ex[i], graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-                d->graphs.push_back({S, ex[i], 100 + i, nr});
-            }
-            const int steps = limit - 1;
-            RGRG_HIP(hipMemsetAsync(d->range_state, 0, MAX_CHAINS * 4 * sizeof(int), d->stream));
-            RGRG_HIP(hipEventRecord(d->ev_fork, d->stream));
-            for (int i = 1; i < nr; ++i) RGRG_HIP(hipStreamWaitEvent(rs[i], d->ev_fork, 0));
-            int polls = 0;
-            for (int t = 0; t < steps; ++t) {
-                for (int i = 0; i < nr; ++i) RGRG_HIP(hipGraphLaunch(ex[i], rs[i]));
-                if ((t & 15) == 15 && t + 1 < steps) {   // "every row has emitted EOS", polled 16 steps late (see the joined loop below)
-                    if (polls > 0) {
-                        const int prev = (polls - 1) & 1;
-                        bool all = true;
-                        for (int i = 0; i < nr; ++i) {
-                            RGRG_HIP(hipEventSynchronize(d->ev_rpoll[prev][i]));
-                            all = all && d->h_rdone[prev * MAX_CHAINS + i] != 0;
-                        }
-                        if (all) break;
-                    }
-                    const int cur = polls & 1;
-                    for (int i = 0; i < nr; ++i) {
-                        RGRG_HIP(hipMemcpyAsync(d->h_rdone + cur * MAX_CHAINS + i, d->range_state + 4 * i + 1, sizeof(int), hipMemcpyDeviceToHost, rs[i]));
-                        RGRG_HIP(hipEventRecord(d->ev_rpoll[cur][i], rs[i]));
-                    }
-                    ++polls;
-                }
-            }
-            for (int i = 1; i < nr; ++i) {
-                RGRG_HIP(hipEventRecord(d->ev_join[i - 1], rs[i]));
-                RGRG_HIP(hipStreamWaitEvent(d->stream, d->ev_join[i - 1], 0));
-            }
-            for (int i = 0; i < nr; ++i)
-                RGRG_HIP(hipMemcpyAsync(d->h_rdone + 2 * MAX_CHAINS + i, d->range_state + 4 * i + 1, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-            RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), d->ids, (size_t)d->max_len * sizeof(long long),
-                                      (size_t)limit * sizeof(int64_t), S, hipMemcpyDeviceToDevice, d->stream));
-            RGRG_HIP(hipStreamSynchronize(d->stream));
-            // the single-process done length = the first length at which EVERY row is finished = the latest of the ranges'
-            int done = 0;
-            bool all = true;
-            for (int i = 0; i < nr; ++i) {
-                const int v = d->h_rdone[2 * MAX_CHAINS + i];
-                all = all && v != 0;
-                done = v > done ? v : done;
-            }
-            *out_len = (all && done > 0 && done < limit) ? done : limit;
-            d->logits_stale_rows = S;
-            d->logits_valid = true;
-            return RGRG_OK;
-        }
-    }
     hipGraphExec_t exec = nullptr;
     if (use_graph) {
         for (auto& g : d->graphs)
@@ -2779,17 +2463,9 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
         }
     }
     RGRG_HIP(hipMemcpyAsync(d->h_done, d->done_len, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    d->h_done[3] = 0;
-    if (d->pk_mode && d->pk_bar)   // persistent.inc: a bounded barrier spin gave up (a workgroup was not resident in time)
-        RGRG_HIP(hipMemcpyAsync(d->h_done + 3, d->pk_bar + 16 * PK_BAR_ERR, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), d->ids, (size_t)d->max_len * sizeof(long long),
                               (size_t)limit * sizeof(int64_t), S, hipMemcpyDeviceToDevice, d->stream));
     RGRG_HIP(hipStreamSynchronize(d->stream));
-    if (d->h_done[3]) {
-        (void)hipMemset(d->pk_bar, 0, (size_t)PK_BAR_SLOTS * 16 * sizeof(unsigned));
-        set_error("decoder: the persistent decode kernel's grid barrier timed out (its 256 workgroups were not all resident); results discarded");
-        return RGRG_EHIP;
-    }
     done = *d->h_done;
     *out_len = (done > 0 && done < limit) ? done : limit;
     d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
@@ -3878,8 +3554,6 @@ static int set_precision_impl(rgrg_decoder* d, int mode) {
                 if ((rc2 = dmalloc(d, (void**)&d->sk_ws, slabs * 4096 * sizeof(float), false)) ||
                     (rc2 = dmalloc(d, (void**)&d->sk_cnt, tickets * sizeof(unsigned), true)))
                     return rc2;
-                d->sk_slabs = slabs;
-                if (const char* e3 = getenv("RGRG_SK_CONS")) d->sk_cons = atoi(e3) <= 0 ? 1 : std::min(atoi(e3), 4);
                 const char* e1 = getenv("RGRG_SK_MLP");
                 const char* e2 = getenv("RGRG_SK_ATTN");
                 // measured (profiles/r05_splitk_decode_ab.log): at hundreds of rows the hand-off costs what the shorter K loop saves; unset =

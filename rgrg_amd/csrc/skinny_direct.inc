@@ -55,25 +55,7 @@ struct DirectArgs {
     int M, K, N, NT, KS, act;
     float* cand_val;    // optional per-tile row maxima (fused arg-max of lm_head): [rows][NT]
     int* cand_idx;
-    unsigned long long* stamps;   // measurement builds (-DRGRG_SKINNY_STAMPS, tools/skinny_stamps.py): [workgroup][8] or null
 };
-
-// Phase stamps of thread 0 of every workgroup on the 100 MHz real-time clock (common to all XCDs).  The stamps stay in
-// registers until the kernel's last instruction (a store in the middle would share vmcnt with the loads being timed);
-// SKS_WAIT_VM(n) is an explicit s_waitcnt vmcnt(n) (gfx9 encoding, expcnt / lgkmcnt left open) in front of a stamp.
-// Compiled out of the product build.
-#ifdef RGRG_SKINNY_STAMPS
-#define SKS_DECL unsigned long long sks_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define SKS(i) do { __builtin_amdgcn_sched_barrier(0); sks_t[i] = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define SKS_WAIT_VM(n) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0F70 | ((n) & 15) | (((n) >> 4) << 14)); } while (0)
-#define SKS_FLUSH(ptr_, wg_) do { SKS_WAIT_VM(0); SKS(7); if ((ptr_) && threadIdx.x == 0) {                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) (ptr_)[(size_t)(wg_) * 8 + i_] = sks_t[i_]; } } while (0)
-#else
-#define SKS_DECL do { } while (0)
-#define SKS(i) do { } while (0)
-#define SKS_WAIT_VM(n) do { } while (0)
-#define SKS_FLUSH(ptr_, wg_) do { } while (0)
-#endif
 
 __device__ __forceinline__ f32x4 dx_ldb(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
@@ -246,8 +228,6 @@ template <int MT, int MODE, bool LNF, int W16 = 0>
 __global__ __launch_bounds__(512) void rgrg_skinny_direct_f32(const DirectArgs a) {
     __shared__ __attribute__((aligned(16))) float red[SK_WAVES * 8 * 64];
     __shared__ float st[MT][SK_WAVES][32][2];
-    SKS_DECL;
-    SKS(0);   // stamp 0: first instruction
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: scalar offsets for the buffer loads
     const int nt = blockIdx.x, ks = blockIdx.y;
@@ -272,8 +252,6 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_f32(const DirectArgs a
         f32x4 xa[2][DK_PW];
         if (mt == 0) {
             dx_load_frags<MODE>(xa, a, mt, kc0, lane, issue_weights);
-            SKS_WAIT_VM(DK_PW);     SKS(1);   // stamp 1: every activation stream of the wave has landed (the 8 weight chunks are behind them)
-            SKS_WAIT_VM(DK_PW - 1); SKS(2);   // stamp 2: first weight chunk (HBM) has landed
             if (e_col < a.N) {
                 if (a.bias && (a.KS == 1 || ks == 0)) e_bias = a.bias[e_col];
                 if constexpr (LNF) e_c1 = a.c1[e_col];
@@ -318,9 +296,7 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_f32(const DirectArgs a
         if (mt > 0) __syncthreads();
 #pragma unroll
         for (int r = 0; r < 8; ++r) red[(wave * 8 + r) * 64 + lane] = acc[mt][r];
-        if (mt == 0) SKS(3);   // stamp 3: wave 0's MFMA chain is complete (the LDS writes above depend on it)
         __syncthreads();
-        if (mt == 0) SKS(4);   // stamp 4: every wave's partial sums are in LDS
         // 32 rows x 16 cols = 512 outputs, one per thread.  C/D map of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + reg
         const int half = tid >> 8, rr = (tid >> 6) & 3, l = tid & 63;
         float v = red[(half * 4 + rr) * 64 + l];
@@ -364,8 +340,6 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_f32(const DirectArgs a
             }
         }
     }
-    SKS(5);   // stamp 5: reduction + epilogue done, stores issued; stamp 7 (SKS_FLUSH): stores acknowledged
-    SKS_FLUSH(a.stamps, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // attn_proj' (N = 1024, K = 1024: 64 column tiles, no K split) with ONE ROW HALF per workgroup: grid (64 tiles, 2 halves) =
@@ -375,8 +349,6 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_f32(const DirectArgs a
 // DX_PLAIN, no LayerNorm fold, <= 32 rows, KS == 1: bias + residual (in place) + the accumulator reset of the main kernel.
 __global__ __launch_bounds__(512) void rgrg_skinny_direct_half_f32(const DirectArgs a) {
     __shared__ __attribute__((aligned(16))) float red[SK_WAVES * 4 * 64];
-    SKS_DECL;
-    SKS(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nt = blockIdx.x, half = blockIdx.y;
@@ -390,8 +362,6 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_half_f32(const DirectA
 #pragma unroll
     for (int c = 0; c < DK_PW; ++c) w[c] = dx_ldb_nt(rw, (unsigned)lane * 16u, (unsigned)((nt * kchunks + kc0 + c) * 1024));
     __builtin_amdgcn_sched_barrier(0);
-    SKS_WAIT_VM(DK_PW);     SKS(1);
-    SKS_WAIT_VM(DK_PW - 1); SKS(2);
     // epilogue operands of this thread (threads 0..255: one output each), requested behind the weight stream
     const int e_rr = (tid >> 6) & 3, e_l = tid & 63;
     const int e_col = nt * 16 + (e_l & 15);
@@ -410,9 +380,7 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_half_f32(const DirectA
         for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[c][j], w[c][j], acc, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[(wave * 4 + r) * 64 + lane] = acc[r];
-    SKS(3);
     __syncthreads();
-    SKS(4);
     if (tid >= 256) return;
     // 16 rows x 16 cols = 256 outputs.  C/D map of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + reg
     float v = red[e_rr * 64 + e_l];
@@ -426,8 +394,6 @@ __global__ __launch_bounds__(512) void rgrg_skinny_direct_half_f32(const DirectA
     v = apply_act(v + e_bias + e_rf, a.act);
     if (a.Y && row < a.M && e_col < a.N) a.Y[(size_t)row * a.ldy + e_col] = v;
     if (a.Yf) a.Yf[fo] = row < a.M ? v : 0.f;
-    SKS(5);
-    SKS_FLUSH(a.stamps, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // lm_head' for <= 32 rows, round 3: ONE WAVE PER COLUMN TILE, the whole K in one accumulation chain.
@@ -445,8 +411,6 @@ __global__ __launch_bounds__(512) void rgrg_lm_head_wave_f32(const DirectArgs a)
     extern __shared__ __attribute__((aligned(16))) float lmh_smem[];
     float* xs = lmh_smem;                                                   // [2 halves][64 chunks][64 lanes][4]
     float (*st)[32][2] = reinterpret_cast<float (*)[32][2]>(lmh_smem + 32 * DK_SLICE);  // [8 waves][32 rows][sum, sum of squares]
-    SKS_DECL;
-    SKS(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int KCH = DK_SLICE / 16;  // 64 chunks of 16 k
@@ -493,7 +457,6 @@ __global__ __launch_bounds__(512) void rgrg_lm_head_wave_f32(const DirectArgs a)
         dx_row_stats(xa, st[wave], lane);
     }
     __syncthreads();
-    SKS(1);   // stamp 1: activation rows staged, statistics done (the first 16 KiB of weights were requested before)
     if (ngl == 0) return;
     // mean / rstd of the 8 rows this lane owns in the C/D map (row = half * 16 + (lane >> 4) * 4 + r)
     float mean[2][4], rstd[2][4];
@@ -526,7 +489,6 @@ __global__ __launch_bounds__(512) void rgrg_lm_head_wave_f32(const DirectArgs a)
                     acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[j], wa[c][j], acc1, 0, 0, 0);
                 }
             }
-            if (ti == 0 && gg == 0) SKS(2);      // stamp 2: the first weight group has been consumed (its MFMAs are issued)
             __builtin_amdgcn_sched_barrier(0);   // the 8 refill loads go out together, right behind the buffer's last MFMA
             load_group(wa, ti * 8 + gg + 2);
             __builtin_amdgcn_sched_barrier(0);
@@ -571,10 +533,7 @@ __global__ __launch_bounds__(512) void rgrg_lm_head_wave_f32(const DirectArgs a)
                     }
                 }
             }
-        if (ti == 0) SKS(3);   // stamp 3: first tile finished (512 MFMAs + epilogue)
     }
-    SKS(5);   // stamp 5: wave 0's last tile finished
-    SKS_FLUSH(a.stamps, blockIdx.x);
 }
 constexpr size_t LMH_LDS = (size_t)(32 * DK_SLICE + SK_WAVES * 32 * 2) * sizeof(float);
 

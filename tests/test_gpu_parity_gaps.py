@@ -222,11 +222,10 @@ def test_opt_in_split_k_of_the_decode_projections_matches_the_default_path(S):
         "torch.save((ids.cpu(), lg.cpu()), sys.argv[1])\n" % (repo, os.path.join(repo, "tests"), S, S))
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
-        off = {"RGRG_SK_MLP": "1", "RGRG_SK_ATTN": "1", "RGRG_SK_CONS": "1"}
-        # "auto": nothing set - a step of <= 256 rows splits mlp_proj 4 ways and attn_proj 2 ways by itself (round 6), larger ones do not;
-        # "cons2": c_attn / c_fc on two K slices as well (opt-in, <= 256 rows; measured slower)
+        off = {"RGRG_SK_MLP": "1", "RGRG_SK_ATTN": "1"}
+        # "auto": nothing set - a step of <= 256 rows splits mlp_proj 4 ways and attn_proj 2 ways by itself (round 6), larger ones do not
         variants = [("off", off), ("auto", {})]
-        variants += ([("mlp4", dict(off, RGRG_SK_MLP="4")), ("cons2", {"RGRG_SK_CONS": "2"})] if S <= 256 else
+        variants += ([("mlp4", dict(off, RGRG_SK_MLP="4"))] if S <= 256 else
                      [("mlp2", dict(off, RGRG_SK_MLP="2", RGRG_SK_ATTN="2"))])   # (one child process each: ~10 s of start-up)
         for name, env_add in variants:
             path = os.path.join(tmp, name + ".pt")
@@ -313,14 +312,13 @@ def test_many_sequence_step_in_row_ranges_is_bit_identical_to_one_range():
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         # (default = 4 requested ranges since round 6, which 700 rows turn into 3: see above)
-        for name, env_add in (("one", {"RGRG_DECODE_CHAINS": "1"}), ("default", {}), ("two", {"RGRG_DECODE_CHAINS": "2"}),
-                              ("free", {"RGRG_DECODE_FREE": "1", "RGRG_DECODE_CHAINS": "3"})):
+        for name, env_add in (("one", {"RGRG_DECODE_CHAINS": "1"}), ("default", {}), ("two", {"RGRG_DECODE_CHAINS": "2"})):
             path = os.path.join(tmp, name + ".pt")
             env = {k: v for k, v in os.environ.items() if k != "RGRG_DECODE_CHAINS"}
             r = subprocess.run([sys.executable, "-c", code, path], env=dict(env, **env_add), capture_output=True, text=True, timeout=600)
             assert r.returncode == 0, r.stderr[-2000:]
             res[name] = torch.load(path)
-    for name in ("default", "two", "free"):   # free: round 6, every range replays its own step graph on its own stream (opt-in)
+    for name in ("default", "two"):
         for (ids1, lg1), (ids0, lg0) in zip(res[name], res["one"]):
             assert torch.equal(ids1, ids0), name
             assert torch.equal(lg1, lg0), name
