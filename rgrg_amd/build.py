@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librgrg_hip.so")
-SOURCES = ("runtime.hip", "gemm_f32.hip", "gemm_bf16.hip", "detector_ops.hip", "det_train.hip", "decoder.hip", "train_ops.hip", "attn_train16.hip")
+SOURCES = ("runtime.hip", "gemm_f32.hip", "gemm_bf16.hip", "detector_ops.hip", "det_train.hip", "decoder.hip", "decoder_beam.hip",
+           "decoder_lm.hip", "train_ops.hip", "attn_train16.hip")
 ARCH = "gfx950"
 
 
@@ -26,13 +27,14 @@ def _hipcc() -> str:
 
 
 HASH_PATH = os.path.join(LIB_DIR, "librgrg_hip.srchash")
-HEADERS = ("common.h", "skinny_direct.inc", "gemm_kp.inc")
 
 
 def _source_hash() -> str:
     import hashlib
     h = hashlib.sha256()
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", "rgrg_hip.h")]
+    # every source and header of csrc/ (a new header cannot be forgotten) plus the public header
+    deps = [os.path.join(CSRC, s) for s in sorted(os.listdir(CSRC)) if s.endswith((".h", ".inc", ".hip"))]
+    deps.append(os.path.join(HERE, "..", "include", "rgrg_hip.h"))
     for d in deps:
         with open(d, "rb") as f:
             h.update(f.read())

@@ -20,7 +20,7 @@
 //   * softmax / masks / dropout / the dS arithmetic stay fp32 in registers; P and dS are rounded to 16 bit as MFMA operands,
 //     O is normalised in fp32 after the product (P enters as exp(s - max) <= 1).
 // Dropout masks are the counter-based ones of common.h (same index as the fp32 kernels), so forward and backward agree.
-#include "common.h"
+#include "internal.h"
 
 namespace rgrg {
 

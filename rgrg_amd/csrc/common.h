@@ -98,6 +98,42 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Row helpers of the decoder's LayerNorm / embedding kernels (decoder.hip, decoder_lm.hip), 256 threads per workgroup
+constexpr float LN_EPS = 1e-5f;
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// 4 fp32 -> 4 16-bit values (bf16 / fp16 by f16, round to nearest even: the rounding the 16-bit GEMM would apply to an fp32 input)
+__device__ __forceinline__ void store_16x4(unsigned short* dst, const f32x4 v, int f16) {
+    uint2 o;
+    o.x = to16_rt(v[0], f16) | (to16_rt(v[1], f16) << 16);
+    o.y = to16_rt(v[2], f16) | (to16_rt(v[3], f16) << 16);
+    *reinterpret_cast<uint2*>(dst) = o;
+}
+
+// nn.LayerNorm(1024, eps=1e-5) of the row held as one float4 per thread (256 threads)
+__device__ __forceinline__ f32x4 ln_row(const f32x4 v, const float* __restrict__ g, const float* __restrict__ b,
+                                        float* sh, int D) {
+    const int tid = threadIdx.x;
+    const float mean = block_sum_256((v[0] + v[1]) + (v[2] + v[3]), sh) / (float)D;
+    f32x4 d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = v[e] - mean;
+    const float var = block_sum_256((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]), sh) / (float)D;
+    const float rstd = 1.0f / sqrtf(var + LN_EPS);
+    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[tid], bb = reinterpret_cast<const f32x4*>(b)[tid];
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = d[e] * rstd * gg[e] + bb[e];
+    return o;
+}
+
 
 // Counter-based dropout (training pass): Philox4x32-7 keyed by the call's seed, counter = (element index / 4, stream id),
 // element i takes word i % 4 of its call - a kernel that owns 4 consecutive elements pays ONE generator call for them (round 5:

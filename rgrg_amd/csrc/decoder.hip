@@ -18,6 +18,9 @@
 //    over the 4 waves of a workgroup (+ over workgroups when N is small) and reduced in a
 //    fixed order -> bitwise reproducible.
 //  * > 32 sequences: the same step runs on the tiled MFMA GEMM of gemm_f32.hip.
+//
+// This file: the decode step, the decoder object, forward_cached, set_precision and the timing hooks.  Beam search is in
+// decoder_beam.hip, the teacher-forced and training passes in decoder_lm.hip; decoder_internal.h holds what they share.
 #include <math.h>
 #include <stdlib.h>
 
@@ -26,48 +29,16 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "decoder_internal.h"
 
 namespace rgrg {
 
-struct GemmParams;
-int launch_gemm_dense(const float* A, const float* W, const float* shift, const float* R, float* Y, int M, int N, int K,
-                      int ldy, int act, float* ws, size_t ws_floats, hipStream_t st);
-int init_gemm_attrs();
-int init_gemm_bf16_attrs();
-// (gemm_bf16.hip; f16: the 16-bit type - 0 bf16, 1 IEEE fp16)
-struct GemmLnFold {   // LayerNorm folded around the 16-bit GEMMs (gemm_bf16.hip: GemmBf16Params)
-    void* Yb16 = nullptr;               // producer: 16-bit copy of the fp32 result (the raw residual stream) ...
-    float* stats_out = nullptr;         // ... and per-row (sum, sum of squares) slots [M][16][2]
-    const float* ln_stats = nullptr;    // consumer: those slots
-    const float* ln_colsum = nullptr;   // consumer: column sums of the gain-scaled rounded weights
-    void* Ypre16 = nullptr;             // training pass: 16-bit pre-activation copy next to the activated Y16 (c_fc)
-    const void* G16 = nullptr;          // training pass: saved 16-bit pre-activations, result *= gelu_new'(G16) (mlp_proj dgrad)
-    int ksplit = 0;                     // split-K over `ksplit` workgroups per tile with a last-arriver reduce (work space, tickets)
-    float* sk_ws = nullptr;
-    unsigned* sk_cnt = nullptr;
-    float* cand_val = nullptr;          // 256 x 256 kernel: per-row (maximum, column) of every column tile instead of Y (greedy lm_head)
-    int* cand_idx = nullptr;
-    int kp = 0;                         // the K-parity ping-pong kernel (gemm_kp.inc), tile from (N, K) only
-};
-bool gemm_bf16_cand_epilogue_ok(int M, int N, int K);   // would launch_gemm_bf16w_ex pick the 256 x 256 kernel for this lm_head?
-int launch_gemm_bf16w_ex(const float* A, const void* A16, const void* Wb, const float* shift, const float* R, float* Y, void* Y16,
-                         int M, int N, int K, int ldy, int act, hipStream_t st, int f16, const GemmLnFold* ln = nullptr);
-int launch_gemm_bf16w(const float* A, const void* Wb, const float* shift, const float* R, float* Y, int M, int N, int K,
-                      int ldy, int act, hipStream_t st, int f16);
-int convert_f32_to_bf16(const float* src, void* dst, size_t n, hipStream_t st, int f16);
-
-constexpr int MAX_CHAINS = 4;   // row ranges of the many-sequence decode step (enqueue_step)
-constexpr int PAD_ROWS = 32;
-constexpr int SKINNY_MAX_ROWS = 128;  // 4 row tiles of 32 sequences per weight-streaming launch (RGRG_SKINNY_MAX_ROWS)
-static int skinny_max_rows() {
+int skinny_max_rows() {
     static int v = -1;
     if (v < 0) { const char* e = getenv("RGRG_SKINNY_MAX_ROWS"); v = e ? atoi(e) : SKINNY_MAX_ROWS;
         if (v > SKINNY_MAX_ROWS) v = SKINNY_MAX_ROWS; if (v < 32) v = 32; }
     return v;
 }
-constexpr int BOS_ID = 50256, EOS_ID = 50256, PAD_ID = 50256;
-constexpr float LN_EPS = 1e-5f;
 
 // ------------------------------------------------------------------ weight packing
 // W [N,K] row-major -> P [NT][K/8][64 lanes][4]: lane l = (j = l&31, h = l>>5) holds
@@ -329,39 +300,6 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const SkinnyArgs a) 
 }
 
 // ------------------------------------------------------------------ small kernels
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// 4 fp32 -> 4 16-bit values (bf16 / fp16 by f16, round to nearest even: the rounding the 16-bit GEMM would apply to an fp32 input)
-__device__ __forceinline__ void store_16x4(unsigned short* dst, const f32x4 v, int f16) {
-    uint2 o;
-    o.x = to16_rt(v[0], f16) | (to16_rt(v[1], f16) << 16);
-    o.y = to16_rt(v[2], f16) | (to16_rt(v[3], f16) << 16);
-    *reinterpret_cast<uint2*>(dst) = o;
-}
-
-// nn.LayerNorm(1024, eps=1e-5) of the row held as one float4 per thread (256 threads)
-__device__ __forceinline__ f32x4 ln_row(const f32x4 v, const float* __restrict__ g, const float* __restrict__ b,
-                                        float* sh, int D) {
-    const int tid = threadIdx.x;
-    const float mean = block_sum_256((v[0] + v[1]) + (v[2] + v[3]), sh) / (float)D;
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = v[e] - mean;
-    const float var = block_sum_256((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]), sh) / (float)D;
-    const float rstd = 1.0f / sqrtf(var + LN_EPS);
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[tid], bb = reinterpret_cast<const f32x4*>(b)[tid];
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = d[e] * rstd * gg[e] + bb[e];
-    return o;
-}
 
 // x[s] = wte[ids[s][t]] + wte[t] (quirk: positions are embedded with wte, language_model.py:307),
 // xn[s] = ln_1 of layer 0.  One workgroup per sequence, D == 1024.
@@ -430,6 +368,12 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
         if (xn16) store_16x4(xn16 + (size_t)row * D + 4 * (j * 64 + lane), o, f16);
         else reinterpret_cast<f32x4*>(xn + (size_t)row * D)[j * 64 + lane] = o;
     }
+}
+int launch_ln_rows(const float* x, const float* g, const float* b, float* xn, int D, unsigned short* xn16, int f16, int rows,
+                   hipStream_t st) {
+    hipLaunchKernelGGL(ln_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, g, b, xn, D, xn16, f16, rows);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
 }
 
 // Pseudo self-attention for ONE new token per sequence (GPT2PseudoAttention.forward with
@@ -916,646 +860,6 @@ __global__ __launch_bounds__(256) void decode_reset_kernel(long long* __restrict
     }
 }
 
-// ------------------------------------------------------------------ beam search kernels
-constexpr int BEAM_K = 32;  // max 2*num_beams candidates per row (num_beams <= 16)
-
-// Per beam row: max, log-sum-exp and the top-K (value desc, token asc on ties) logits.
-// log_softmax is monotonic within a row, so the row's best continuations are its top logits.
-// Round 6: 1024 threads per row and candidate lists of LIST = 8 / 16 / 32 >= K entries (the scripts' 4 beams need 8): the round-5
-// kernel - 256 threads, lists of 32 - took 204 us per step at 116 beam rows (11 % of the step): a wave runs the whole 31-step
-// insertion chain whenever ONE of its lanes inserts, i.e. for nearly every one of its 196 elements per lane.
-constexpr int BEAM_ROW_THREADS = 1024;
-// max and sum of exp(x - max) of a row, the same value in every thread (fixed order: strided per thread, butterflies per wave, the 16
-// wave sums in wave order)
-template <int THREADS>
-__device__ __forceinline__ void beam_row_max_sumexp(const float* __restrict__ x, int V, float* sh, float& m_out, float& ssum_out) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float m = -INFINITY;
-    for (int i = tid; i < V; i += THREADS) m = fmaxf(m, x[i]);
-    m = wave_max(m);
-    if (lane == 0) sh[wave] = m;
-    __syncthreads();
-    m = sh[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) m = fmaxf(m, sh[w]);
-    __syncthreads();
-    float ssum = 0.f;
-    for (int i = tid; i < V; i += THREADS) ssum += expf(x[i] - m);
-    ssum = wave_sum(ssum);
-    if (lane == 0) sh[wave] = ssum;
-    __syncthreads();
-    ssum = sh[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) ssum += sh[w];
-    __syncthreads();
-    m_out = m; ssum_out = ssum;
-}
-template <int LIST, int THREADS>   // (8, 1024), (16, 1024), (32, 512): 1024 threads x 32 entries spill
-__global__ __launch_bounds__(THREADS) void beam_row_topk_kernel(const float* __restrict__ logits, int ld, int V, int K,
-                                                                         float* __restrict__ row_max, float* __restrict__ row_logsum,
-                                                                         float* __restrict__ top_val, int* __restrict__ top_tok) {
-    constexpr int NW = THREADS / 64;
-    __shared__ float sh[NW];
-    __shared__ float wv[NW];
-    __shared__ int wi[NW];
-    __shared__ int winner;
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* x = logits + (size_t)row * ld;
-    // ONE pass over the row: the thread's running maximum with the sum of exp(x - maximum) rescaled whenever the maximum moves, and its
-    // local top-LIST, sorted (value desc, index asc).  (Three passes - maximum, sum, candidates - took 50 us per step at the scripts'
-    // 116 beam rows, this form 44: what is left is the insertion chain, which a wave runs whenever one of its lanes inserts, and the
-    // exponentials, on 116 of the 256 CUs - profiles/r06_kernel_trace_summary_beam4_fp16.md.)
-    float tm = -INFINITY, ts = 0.f;
-    float lv[LIST];
-    int li[LIST];
-#pragma unroll
-    for (int k = 0; k < LIST; ++k) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
-    // (8 loads in flight per thread)
-    for (int i0 = tid; i0 < V; i0 += 8 * THREADS) {
-        float vb[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) vb[u] = x[min(i0 + u * THREADS, V - 1)];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * THREADS;
-            if (i >= V) break;
-            const float v = vb[u];
-            if (v > tm) { ts = ts * expf(tm - v) + 1.0f; tm = v; }   // (first element: 0 * exp(-inf) + 1)
-            else ts += expf(v - tm);
-            if (v > lv[LIST - 1]) {  // strided indices ascend, so an equal value never displaces an earlier one
-                lv[LIST - 1] = v; li[LIST - 1] = i;
-#pragma unroll
-                for (int k = LIST - 1; k > 0; --k) {
-                    if (lv[k] > lv[k - 1]) {
-                        const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
-                        const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
-                    }
-                }
-            }
-        }
-    }
-    // row maximum, then every thread's sum brought to it; fixed order (butterflies per wave, the wave sums in wave order)
-    float m = wave_max(tm);
-    if (lane == 0) sh[wave] = m;
-    __syncthreads();
-    m = sh[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, sh[w]);
-    __syncthreads();
-    float ssum = wave_sum(tm == -INFINITY ? 0.f : ts * expf(tm - m));
-    if (lane == 0) sh[wave] = ssum;
-    __syncthreads();
-    ssum = sh[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) ssum += sh[w];
-    // K rounds: block-wide arg-max over the threads' current heads; the winner pops its head
-    for (int round = 0; round < K; ++round) {
-        float bv = lv[0];
-        int bi = li[0];
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < NW; ++w)
-                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
-            top_val[(size_t)row * BEAM_K + round] = bv;
-            top_tok[(size_t)row * BEAM_K + round] = bi;
-            winner = bi;
-        }
-        __syncthreads();
-        if (li[0] == winner) {
-#pragma unroll
-            for (int k = 0; k < LIST - 1; ++k) { lv[k] = lv[k + 1]; li[k] = li[k + 1]; }
-            lv[LIST - 1] = -INFINITY; li[LIST - 1] = 0x7fffffff;
-        }
-    }
-    if (tid == 0) { row_max[row] = m; row_logsum[row] = logf(ssum); }
-}
-
-// Per batch item: log_softmax + beam score for the nb*K row candidates, then the top K = 2*nb
-// of the item (score desc; ties: lower flat index beam*V + token first) - language_model.py:545-561.
-constexpr int BEAM_MERGE_THREADS = BEAM_K * BEAM_K / 2;  // one thread per candidate: nb * 2 nb <= 512
-__global__ __launch_bounds__(BEAM_MERGE_THREADS) void beam_merge_kernel(const float* __restrict__ row_max, const float* __restrict__ row_logsum,
-                                                         const float* __restrict__ top_val, const int* __restrict__ top_tok,
-                                                         const float* __restrict__ beam_scores, int nb, int K, int V,
-                                                         float* __restrict__ out_score, int* __restrict__ out_tok,
-                                                         int* __restrict__ out_beam) {
-    // n = nb * 2 nb candidates (<= 512 for nb <= 16): one thread each, ranked against all others through LDS
-    __shared__ float ssc[BEAM_MERGE_THREADS];
-    __shared__ long long sflat[BEAM_MERGE_THREADS];
-    const int item = blockIdx.x, tid = threadIdx.x;
-    const int n = nb * K;
-    float sc = -INFINITY;
-    long long flat = 0x7fffffffffffLL;
-    int tok = 0, b = 0;
-    if (tid < n) {
-        b = tid / K;
-        const int row = item * nb + b;
-        const float v = top_val[(size_t)row * BEAM_K + (tid - b * K)];
-        tok = top_tok[(size_t)row * BEAM_K + (tid - b * K)];
-        sc = ((v - row_max[row]) - row_logsum[row]) + beam_scores[row];
-        flat = (long long)b * V + tok;
-    }
-    ssc[tid] = sc;
-    sflat[tid] = flat;
-    __syncthreads();
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-        const float oj = ssc[j];
-        const long long fj = sflat[j];
-        if (oj > sc || (oj == sc && fj < flat)) ++rank;
-    }
-    if (tid < n && rank < K) {
-        out_score[item * K + rank] = sc;
-        out_tok[item * K + rank] = tok;
-        out_beam[item * K + rank] = b;
-    }
-}
-
-// ---- more than 16 beams (round 6: the reference's loop has no bound, language_model.py:450-475).  The per-thread sorted lists of the
-// kernels above hold 32 candidates in registers; wider beams take K = 2 num_beams rounds of a block-wide arg-max over the elements
-// that come AFTER the previous winner in the same total order (value desc, index asc) - K scans of the row from L2 instead of one,
-// the same winners.  top_val / top_tok rows are K wide here (ldk).
-template <int NW>
-__device__ __forceinline__ void beam_block_argmax(float& bv, long long& bi, float* wv, long long* wi, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const long long oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
-    __syncthreads();
-    bv = wv[0]; bi = wi[0];
-    for (int w = 1; w < NW; ++w)
-        if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
-    __syncthreads();
-}
-__global__ __launch_bounds__(BEAM_ROW_THREADS) void beam_row_topk_wide_kernel(const float* __restrict__ logits, int ld, int V, int K,
-                                                                              float* __restrict__ row_max, float* __restrict__ row_logsum,
-                                                                              float* __restrict__ top_val, int* __restrict__ top_tok) {
-    constexpr int NW = BEAM_ROW_THREADS / 64;
-    __shared__ float sh[NW];
-    __shared__ float wv[NW];
-    __shared__ long long wi[NW];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const float* x = logits + (size_t)row * ld;
-    float m, ssum;
-    beam_row_max_sumexp<BEAM_ROW_THREADS>(x, V, sh, m, ssum);
-    float pv = INFINITY;
-    long long pi = -1;
-    for (int round = 0; round < K; ++round) {
-        float bv = -INFINITY;
-        long long bi = 0x7fffffffLL;
-        for (int i = tid; i < V; i += BEAM_ROW_THREADS) {
-            const float v = x[i];
-            if ((v < pv || (v == pv && i > pi)) && v > bv) { bv = v; bi = i; }   // strided indices ascend: the first of equal values stays
-        }
-        beam_block_argmax<NW>(bv, bi, wv, wi, tid);
-        if (tid == 0) {
-            top_val[(size_t)row * K + round] = bv;
-            top_tok[(size_t)row * K + round] = (int)bi;
-        }
-        pv = bv; pi = bi;
-    }
-    if (tid == 0) { row_max[row] = m; row_logsum[row] = logf(ssum); }
-}
-// Per batch item: the nb * K candidate scores (same expression as beam_merge_kernel) into `score` [item][nb * K], then the item's
-// top K in the order (score desc, flat index beam * V + token asc), again by K rounds over what follows the previous winner.
-__global__ __launch_bounds__(256) void beam_merge_wide_kernel(const float* __restrict__ row_max, const float* __restrict__ row_logsum,
-                                                              const float* __restrict__ top_val, const int* __restrict__ top_tok,
-                                                              const float* __restrict__ beam_scores, int nb, int K, int V,
-                                                              float* __restrict__ score, float* __restrict__ out_score,
-                                                              int* __restrict__ out_tok, int* __restrict__ out_beam) {
-    __shared__ float wv[4];
-    __shared__ long long wi[4];
-    const int item = blockIdx.x, tid = threadIdx.x;
-    const int n = nb * K;
-    float* sc = score + (size_t)item * n;
-    for (int c = tid; c < n; c += 256) {
-        const int b = c / K, row = item * nb + b;
-        sc[c] = ((top_val[(size_t)row * K + (c - b * K)] - row_max[row]) - row_logsum[row]) + beam_scores[row];
-    }
-    __syncthreads();
-    float pv = INFINITY;
-    long long pf = -1;
-    for (int round = 0; round < K; ++round) {
-        float bv = -INFINITY;
-        long long bf = 0x7fffffffffffLL;
-        for (int c = tid; c < n; c += 256) {
-            const int b = c / K;
-            const float v = sc[c];
-            const long long flat = (long long)b * V + top_tok[(size_t)(item * nb + b) * K + (c - b * K)];
-            if ((v < pv || (v == pv && flat > pf)) && (v > bv || (v == bv && flat < bf))) { bv = v; bf = flat; }
-        }
-        beam_block_argmax<4>(bv, bf, wv, wi, tid);
-        if (tid == 0) {
-            out_score[item * K + round] = bv;
-            out_tok[item * K + round] = (int)(bf % V);
-            out_beam[item * K + round] = (int)(bf / V);
-        }
-        pv = bv; pf = bf;
-    }
-}
-
-// New ancestor table after the host picked the surviving beams: row r continues beam parent[r];
-// slots 0..t come from the parent's table, slot t+1 (written this step) lives in the parent's row.
-__global__ __launch_bounds__(256) void beam_advance_kernel(const int* __restrict__ src_old, int* __restrict__ src_new,
-                                                           const int* __restrict__ parent, int* __restrict__ step, int T,
-                                                           int R) {
-    const int r = blockIdx.x, t = *step;
-    const int p = parent[r];
-    for (int j = threadIdx.x; j <= t; j += 256) src_new[(size_t)r * T + j] = src_old[(size_t)p * T + j];
-    if (threadIdx.x == 0) src_new[(size_t)r * T + t + 1] = p;
-    __syncthreads();
-    (void)R;
-}
-__global__ void beam_step_inc_kernel(int* __restrict__ step) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1;
-}
-__global__ __launch_bounds__(256) void beam_init_kernel(int* __restrict__ src, int T, int nb, int R, int* __restrict__ step) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r < R) src[(size_t)r * T] = (r / nb) * nb;  // slot 0 (image key/value) is stored once per item, in its first beam row
-    if (r == 0) *step = 0;
-}
-
-// ------------------------------------------------------------------ teacher-forced pass (LanguageModel.forward, no cache)
-// x[s,t] = wte[ids[s,t]] + wte[t] (position_ids default to arange(T) and are embedded with wte, language_model.py:298-307),
-// xn = ln_1 of layer 0.  One workgroup per token row.
-// Token ids are validated HERE (no host round trip before the launch): an id outside [0, V) is clamped, so nothing is
-// read out of bounds, and raises the decoder's device-side error word; the loss of that pass comes out as NaN and the
-// next decoder call reports the error (torch.nn.Embedding raises IndexError synchronously on the CPU / asserts on the GPU).
-__global__ __launch_bounds__(256) void embed_seq_ln_kernel(const float* __restrict__ wte, const long long* __restrict__ ids,
-                                                           int T, const float* __restrict__ g, const float* __restrict__ b,
-                                                           float* __restrict__ x, float* __restrict__ xn, int D, int V,
-                                                           int* __restrict__ id_error, const long long* __restrict__ pos_ids, int pos_rows) {
-    __shared__ float sh[4];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    long long tok = ids[row];
-    if (tok < 0 || tok >= V) {
-        if (tid == 0) atomicOr(id_error, 1);
-        tok = tok < 0 ? 0 : V - 1;
-    }
-    // position_ids (language_model.py:293-307): default arange(T); given ones ([S,T], or [1,T] broadcast over the sentences:
-    // pos_rows = T) index the TOKEN table like the default ones do (the reference's wte[position_ids] quirk), so their range
-    // is the vocabulary's and they are checked like the token ids
-    long long pos = row % T;
-    if (pos_ids) {
-        pos = pos_ids[row % pos_rows];
-        if (pos < 0 || pos >= V) {
-            if (tid == 0) atomicOr(id_error, 1);
-            pos = pos < 0 ? 0 : V - 1;
-        }
-    }
-    const f32x4 v = reinterpret_cast<const f32x4*>(wte + (size_t)tok * D)[tid] + reinterpret_cast<const f32x4*>(wte + (size_t)pos * D)[tid];
-    reinterpret_cast<f32x4*>(x + (size_t)row * D)[tid] = v;
-    reinterpret_cast<f32x4*>(xn + (size_t)row * D)[tid] = ln_row(v, g, b, sh, D);
-}
-
-// GPT2PseudoAttention.forward without layer_past (:124-160) and _attn (:84-122) over T tokens: keys/values are
-// [uk(img) ; k_0..k_{T-1}], scores / 8, future token columns replaced by -1e4 (the image column is never masked),
-// plus the additive padding mask (1 - [1|attention_mask]) * -10000 (:325-334), softmax, . V.
-//
-// One WAVE per (sequence, head, 32-query tile), everything in registers on the exact-fp32 matrix core
-// (v_mfma_f32_32x32x2_f32), no LDS:
-//   * scores are computed TRANSPOSED, S^T = K Q^T (A = 32 keys x dims, B = dims x 32 queries; a lane half owns
-//     dims [32h, 32h+32), so a lane reads 128 contiguous bytes of its key / query row).  In the accumulator layout a
-//     lane then holds ONE query (column lane&31) and 16 keys per tile, half of that query's keys - the softmax row
-//     reduction is a register loop plus one exchange with lane^32;
-//   * that same layout is exactly the B operand (keys x queries) of O^T = V^T P^T: register j of a tile is fed to
-//     the MFMA as is, next to A = V[key(j, lane half)][dim], a coalesced 128-byte row read.  No transpose.
-// Key tiles entirely in the future of the query tile are skipped: their weights are exp(-1e4 - max) = 0 in fp32
-// because the never-masked image column keeps max = O(1).  Keys beyond T (tile padding) get -inf.
-constexpr int TF_MAX_T = 1023;  // T + 1 keys <= the 1024 positions of GPT-2's causal-mask buffer (the reference's limit)
-template <int NT>  // key tiles held in registers: T + 1 <= 32 * NT
-__global__ __launch_bounds__(256) void attn_prefill_kernel(const float* __restrict__ qkv, const float* __restrict__ ukv, int ld_ukv,
-                                                           int kcol, const float* __restrict__ am, float* __restrict__ out,
-                                                           int S, int H, int T, float* __restrict__ lse, const DropoutParams drop,
-                                                           unsigned short* __restrict__ out16, int f16) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int QT = (T + 31) / 32;
-    const int item = blockIdx.x * 4 + wave;
-    if (item >= S * H * QT) return;
-    const int qt = item % QT, sh = item / QT, hd = sh % H, s = sh / H;
-    const int NK = T + 1, D = H * 64;
-    const int col = lane & 31, half = lane >> 5;
-    const int iq = qt * 32 + col;                    // this lane's query (column of S^T)
-    const int need = min(NK - 1, qt * 32 + 32) / 32 + 1;  // key tiles with a key <= last query of the tile + 1
-    auto krow = [&](int c) -> const float* {         // K row of key c (c = 0: image key); V row = K row + D
-        c = min(c, NK - 1);
-        return c == 0 ? ukv + (size_t)s * ld_ukv + kcol + hd * 64 : qkv + ((size_t)s * T + c - 1) * 3 * D + D + hd * 64;
-    };
-    // B operand of S^T: this lane's query row, dims [32*half, 32*half + 32)
-    f32x4 qf[8];
-    {
-        const float* qp = qkv + ((size_t)s * T + min(iq, T - 1)) * 3 * D + hd * 64 + half * 32;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) qf[u] = *reinterpret_cast<const f32x4*>(qp + 4 * u);
-    }
-    f32x16 sc[NT];
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        if (kt < need) {
-            f32x4 kf[8];
-            const float* kp = krow(kt * 32 + col) + half * 32;   // A operand: key row kt*32 + (lane&31), same dims
-#pragma unroll
-            for (int u = 0; u < 8; ++u) kf[u] = *reinterpret_cast<const f32x4*>(kp + 4 * u);
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[u][e], qf[u][e], acc, 0, 0, 0);
-            sc[kt] = acc;
-        }
-    }
-    // masks, scale, softmax over the keys of query iq (this lane: 16 keys per tile, lane^32 the other 16)
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        if (kt < need) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                float w = -INFINITY;
-                if (c < NK) {
-                    const bool allowed = (c == 0) || (c - 1 <= iq);
-                    const float addm = (c == 0 || !am) ? 0.f : (1.0f - am[(size_t)s * T + c - 1]) * -10000.0f;
-                    w = (allowed ? sc[kt][r] / 8.0f : -1e4f) + addm;
-                }
-                sc[kt][r] = w;
-                m = fmaxf(m, w);
-            }
-        }
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        if (kt < need) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pexp = expf(sc[kt][r] - m);
-                sc[kt][r] = pexp;
-                sum += pexp;
-            }
-        }
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    if (lse && half == 0 && iq < T) lse[((size_t)s * T + iq) * H + hd] = m + logf(sum);  // kept for the backward pass
-    // O^T = V^T P^T : A = V[key(j, half)][dim = lane&31 (+32)], B = register j of the tile
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        if (kt < need) {
-            float v0[16], v1[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float* vp = krow(kt * 32 + (j & 3) + 8 * (j >> 2) + 4 * half) + D;
-                v0[j] = vp[col];
-                v1[j] = vp[32 + col];
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                float pj = sc[kt][j] / sum;
-                if (drop.p > 0.f)  // attn_dropout on the probabilities (training pass); index = [s][head][query][key]
-                    pj *= dropout_mask(drop, (((unsigned long long)s * H + hd) * T + min(iq, T - 1)) * dropout_key_pitch(NK) +
-                                                 min(kt * 32 + (j & 3) + 8 * (j >> 2) + 4 * half, NK - 1));
-                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0[j], pj, o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[j], pj, o1, 0, 0, 0);
-            }
-        }
-    }
-    if (iq < T) {
-        float* op = out + ((size_t)s * T + iq) * D + hd * 64;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dim = (r & 3) + 8 * (r >> 2) + 4 * half;
-            op[dim] = o0[r];
-            op[32 + dim] = o1[r];
-        }
-        if (out16) {   // 16-bit training flow: the copy attn_proj's GEMM reads (4 consecutive dims per 8-byte store)
-            unsigned short* o16 = out16 + ((size_t)s * T + iq) * D + hd * 64 + 4 * half;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                store_16x4(o16 + 8 * q4, f32x4{o0[4 * q4], o0[4 * q4 + 1], o0[4 * q4 + 2], o0[4 * q4 + 3]}, f16);
-                store_16x4(o16 + 32 + 8 * q4, f32x4{o1[4 * q4], o1[4 * q4 + 1], o1[4 * q4 + 2], o1[4 * q4 + 3]}, f16);
-            }
-        }
-    }
-}
-
-// T + 1 > 256 keys (up to the reference's 1024 positions, language_model.py:60-67): the score tiles no longer fit in
-// registers, so they are RECOMPUTED - pass 1 row max, pass 2 row sum, pass 3 probabilities x V - in the same tile and
-// register order as attn_prefill_kernel, which makes the two kernels bit-identical where both apply (tested).  3x the
-// score MFMAs of the register kernel; only long reports take this path.
-__global__ __launch_bounds__(256) void attn_prefill_stream_kernel(const float* __restrict__ qkv, const float* __restrict__ ukv, int ld_ukv,
-                                                                  int kcol, const float* __restrict__ am, float* __restrict__ out,
-                                                                  int S, int H, int T, float* __restrict__ lse, const DropoutParams drop,
-                                                                  unsigned short* __restrict__ out16, int f16) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int QT = (T + 31) / 32;
-    const int item = blockIdx.x * 4 + wave;
-    if (item >= S * H * QT) return;
-    const int qt = item % QT, sh = item / QT, hd = sh % H, s = sh / H;
-    const int NK = T + 1, D = H * 64;
-    const int col = lane & 31, half = lane >> 5;
-    const int iq = qt * 32 + col;
-    const int need = min(NK - 1, qt * 32 + 32) / 32 + 1;
-    auto krow = [&](int c) -> const float* {
-        c = min(c, NK - 1);
-        return c == 0 ? ukv + (size_t)s * ld_ukv + kcol + hd * 64 : qkv + ((size_t)s * T + c - 1) * 3 * D + D + hd * 64;
-    };
-    f32x4 qf[8];
-    {
-        const float* qp = qkv + ((size_t)s * T + min(iq, T - 1)) * 3 * D + hd * 64 + half * 32;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) qf[u] = *reinterpret_cast<const f32x4*>(qp + 4 * u);
-    }
-    // masked, scaled scores of key tile kt for this lane's query (16 keys: rows (r&3) + 8*(r>>2) + 4*half of the tile)
-    auto tile_scores = [&](int kt) -> f32x16 {
-        f32x4 kf[8];
-        const float* kp = krow(kt * 32 + col) + half * 32;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) kf[u] = *reinterpret_cast<const f32x4*>(kp + 4 * u);
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[u][e], qf[u][e], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            float w = -INFINITY;
-            if (c < NK) {
-                const bool allowed = (c == 0) || (c - 1 <= iq);
-                const float addm = (c == 0 || !am) ? 0.f : (1.0f - am[(size_t)s * T + c - 1]) * -10000.0f;
-                w = (allowed ? acc[r] / 8.0f : -1e4f) + addm;
-            }
-            acc[r] = w;
-        }
-        return acc;
-    };
-    float m = -INFINITY;
-    for (int kt = 0; kt < need; ++kt) {
-        const f32x16 w = tile_scores(kt);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) m = fmaxf(m, w[r]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float sum = 0.f;
-    for (int kt = 0; kt < need; ++kt) {
-        const f32x16 w = tile_scores(kt);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += expf(w[r] - m);
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    if (lse && half == 0 && iq < T) lse[((size_t)s * T + iq) * H + hd] = m + logf(sum);
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-    for (int kt = 0; kt < need; ++kt) {
-        const f32x16 w = tile_scores(kt);
-        float v0[16], v1[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float* vp = krow(kt * 32 + (j & 3) + 8 * (j >> 2) + 4 * half) + D;
-            v0[j] = vp[col];
-            v1[j] = vp[32 + col];
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            float pj = expf(w[j] - m) / sum;
-            if (drop.p > 0.f)
-                pj *= dropout_mask(drop, (((unsigned long long)s * H + hd) * T + min(iq, T - 1)) * dropout_key_pitch(NK) +
-                                             min(kt * 32 + (j & 3) + 8 * (j >> 2) + 4 * half, NK - 1));
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0[j], pj, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[j], pj, o1, 0, 0, 0);
-        }
-    }
-    if (iq < T) {
-        float* op = out + ((size_t)s * T + iq) * D + hd * 64;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dim = (r & 3) + 8 * (r >> 2) + 4 * half;
-            op[dim] = o0[r];
-            op[32 + dim] = o1[r];
-        }
-        if (out16) {   // 16-bit training flow: the copy attn_proj's GEMM reads (4 consecutive dims per 8-byte store)
-            unsigned short* o16 = out16 + ((size_t)s * T + iq) * D + hd * 64 + 4 * half;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                store_16x4(o16 + 8 * q4, f32x4{o0[4 * q4], o0[4 * q4 + 1], o0[4 * q4 + 2], o0[4 * q4 + 3]}, f16);
-                store_16x4(o16 + 32 + 8 * q4, f32x4{o1[4 * q4], o1[4 * q4 + 1], o1[4 * q4 + 2], o1[4 * q4 + 3]}, f16);
-            }
-        }
-    }
-}
-
-// RGRG_PREFILL_STREAM=1 forces the streaming kernel for every length (tests compare it with the register kernel)
-static bool prefill_stream_forced() {
-    static const bool v = [] { const char* e = getenv("RGRG_PREFILL_STREAM"); return e && atoi(e) != 0; }();
-    return v;
-}
-
-static int launch_attn_prefill(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, float* out, int S, int H,
-                               int T, float* lse, const DropoutParams& drop, hipStream_t st, unsigned short* out16 = nullptr, int f16 = 0) {
-    const int items = S * H * ((T + 31) / 32);
-    const dim3 grid((items + 3) / 4), block(256);
-    if (T + 1 > 256 || prefill_stream_forced())
-        hipLaunchKernelGGL(attn_prefill_stream_kernel, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
-    else if (T + 1 <= 96)
-        hipLaunchKernelGGL(attn_prefill_kernel<3>, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
-    else
-        hipLaunchKernelGGL(attn_prefill_kernel<8>, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
-}
-
-// CrossEntropyLoss(ignore_index=-100) on the shifted logits/labels (:368-396): the row of token (s,t), t < T-1, is
-// scored against ids[s][t+1] unless attention_mask[s][t+1] == 0.  One workgroup per logits row of the chunk.
-__global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, size_t ld, int V, int row0,
-                                                      const long long* __restrict__ ids, const float* __restrict__ am, int T,
-                                                      float* __restrict__ row_loss, int* __restrict__ row_valid,
-                                                      float* __restrict__ row_lse, int* __restrict__ id_error) {
-    __shared__ float shv[4];
-    const int r = row0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t = r % T;
-    const bool ignore = (t == T - 1) || (am && am[r + 1] == 0.f);
-    if (ignore) {
-        if (tid == 0) { row_loss[r] = 0.f; row_valid[r] = 0; }
-        return;
-    }
-    const float* x = logits + (size_t)blockIdx.x * ld;
-    float m = -INFINITY;
-    for (int i = tid; i < V; i += 256) m = fmaxf(m, x[i]);
-    m = wave_max(m);
-    if (lane == 0) shv[wave] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(shv[0], shv[1]), fmaxf(shv[2], shv[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int i = tid; i < V; i += 256) sum += expf(x[i] - m);
-    sum = wave_sum(sum);
-    if (lane == 0) shv[wave] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        const float tot = (shv[0] + shv[1]) + (shv[2] + shv[3]);
-        const float lse = m + logf(tot);
-        // the label is a raw caller-supplied id: clamp it for the read (an id outside [0, V) would index outside the
-        // logits row) and raise the error word - that pass's loss and gradients come out as NaN, the next call reports it
-        long long label = ids[r + 1];
-        if (label < 0 || label >= V) {
-            atomicOr(id_error, 1);
-            label = label < 0 ? 0 : V - 1;
-        }
-        row_loss[r] = lse - x[label];
-        row_valid[r] = 1;
-        if (row_lse) row_lse[r] = lse;
-    }
-}
-
-// mean over the scored rows in a fixed order (double accumulation); no scored row -> nan, like torch
-__global__ __launch_bounds__(256) void ce_finalize_kernel(const float* __restrict__ row_loss, const int* __restrict__ row_valid,
-                                                          int n, float* __restrict__ loss, int* __restrict__ n_scored = nullptr,
-                                                          const int* __restrict__ id_error = nullptr) {
-    __shared__ double ssum[256];
-    __shared__ int scnt[256];
-    double a = 0.0;
-    int c = 0;
-    for (int i = threadIdx.x; i < n; i += 256) { a += (double)row_loss[i]; c += row_valid[i]; }
-    ssum[threadIdx.x] = a;
-    scnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { ssum[threadIdx.x] += ssum[threadIdx.x + o]; scnt[threadIdx.x] += scnt[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (loss) *loss = (id_error && *id_error) ? nanf("") : (float)(ssum[0] / (double)scnt[0]);  // invalid token id: poisoned
-        if (n_scored) *n_scored = scnt[0];
-    }
-}
-
-// row_valid of every token row from the ids/mask alone (the scored-row count is needed before the first chunk's backward)
-__global__ __launch_bounds__(256) void ce_valid_kernel(const float* __restrict__ am, int T, int n, float* __restrict__ row_loss,
-                                                       int* __restrict__ row_valid) {
-    for (int r = blockIdx.x * 256 + threadIdx.x; r < n; r += gridDim.x * 256) {
-        const int t = r % T;
-        row_valid[r] = !((t == T - 1) || (am && am[r + 1] == 0.f));
-        row_loss[r] = 0.f;
-    }
-}
-
 // LayerNorm(gain, beta) folded into the [N,K] weight of the GEMM behind it, 16-bit flavour (one wave per output column):
 // wb[n][k] = round16(gain[k] w[n][k]); cs[n] = sum_k wb[n][k] of the rounded values - what the GEMM really multiplies the
 // mean with -, c2[n] = b[n] + sum_k beta[k] w[n][k].  LN(x) W^T + b = rstd (x wb^T - mean cs) + c2 up to the 16-bit
@@ -1582,149 +886,8 @@ __global__ __launch_bounds__(256) void ln_fold16_kernel(const float* __restrict_
     if (lane == 0) { cs[n] = a; c2[n] = (b ? b[n] : 0.f) + c; }
 }
 
-// ------------------------------------------------------------------ decoder object
-struct Lin {
-    const float* w = nullptr;  // [N,K]
-    const float* b = nullptr;  // [N]
-    float* packed = nullptr;   // skinny layout
-    void* wb = nullptr;        // bf16 copy of w (opt-in many-sequence path)
-    float* wT = nullptr;       // [K][Np] transposed copy, Np = N rounded up to 256 (backward pass: dX = dY W)
-    void* wTb = nullptr;       // 16-bit copy of wT (training under autocast)
-    int wb_f16 = 0, wTb_f16 = 0;   // the 16-bit type wb / wTb currently hold (0 bf16, 1 fp16)
-    // 16-bit many-sequence decode with the LayerNorm in front of this GEMM folded in (enqueue_step): wb_ln[n][k] =
-    // round16(gain[k] w[n][k]), cs16[n] = sum_k wb_ln[n][k] (of the ROUNDED values), c2_16[n] = b[n] + sum_k beta[k] w[n][k]
-    void* wb_ln = nullptr;
-    float *cs16 = nullptr, *c2_16 = nullptr;
-    int wb_ln_f16 = -1;
-    int N = 0, K = 0, NT = 0, KS = 1, ntile = 32;
-    // fused decode plan (skinny_direct.inc): `packed` holds 16-column fragments, pre-scaled by the LayerNorm weight of
-    // the LayerNorm this GEMM consumes when lnf is set; c1 / c2 are the folded vectors of that LayerNorm
-    bool direct = false, lnf = false;
-    float *c1 = nullptr, *c2 = nullptr;
-    // 16-bit-weight variant of the fused plan (33-128 rows under autocast, round 6): `packed` rounded to the autocast type, and
-    // the column sums of those ROUNDED values (lnf)
-    void* packed16 = nullptr;
-    float* c1_16 = nullptr;
-    int packed16_f16 = -1;
-};
-
-struct LayerW {
-    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    Lin c_attn, attn_proj, c_fc, mlp_proj;
-};
-
-struct GraphEntry {
-    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3)
-    hipGraphExec_t exec;
-    int key2 = 0, key3 = 0;
-};
-
-}  // namespace rgrg
-
-using namespace rgrg;
-
-struct rgrg_decoder {
-    int n_layer, D, H, V, max_seqs, rows, T, max_len;
-    const float* wte;
-    const float *lnf_g, *lnf_b;
-    Lin fst0, fst2, ukv, lm_head;
-    std::vector<LayerW> layers;
-    // workspace
-    float *feats, *h1, *img, *ukv_out, *x, *x2, *xn, *qkv, *att, *ff, *logits, *part, *kv, *cand_val, *gemm_ws;
-    size_t gemm_ws_floats;
-    int* cand_idx;
-    size_t kv_layer_stride, kv_kv_stride;
-    int ld_logits, ld_ukv;
-    long long* ids;
-    int *next, *finished, *step, *done_len, *sync;
-    // beam search
-    int *src_a, *src_b, *beam_tok, *beam_parent, *cand_tok, *cand_beam, *top_tok;
-    float *beam_scores, *row_max, *row_logsum, *top_val, *cand_score;
-    float *wide_val = nullptr, *wide_score = nullptr;   // more than 16 beams: [rows][K] row candidates, [items][num_beams * K] scores
-    int* wide_tok = nullptr;
-    size_t wide_cap = 0;                                 // rows * K the wide buffers were sized for
-    int* h_done;  // pinned: [0] final read, [1..2] the two in-flight "all finished" polls of the greedy loop
-    hipEvent_t ev_poll[2] = {nullptr, nullptr};
-    // Token-id validation of the teacher-forced passes, without a host round trip.  id_error[0]: raised by the CURRENT
-    // pass (embedding / cross-entropy kernels) when an id is outside [0, vocab), cleared when a pass starts - it poisons
-    // THAT pass's loss and gradients (NaN).  id_error[1]: sticky "some pass failed and has not been reported yet",
-    // folded from [0] at the end of every pass and copied to the pinned mirror; the next call that finds the mirror set
-    // reports torch.nn.Embedding's IndexError and clears both.
-    int* id_error = nullptr;
-    int* h_id_error = nullptr;
-    hipStream_t stream;
-    hipEvent_t ev_in;
-    std::vector<GraphEntry> graphs;
-    std::vector<void*> allocs;
-    size_t gemm_bytes_per_step = 0;
-    double gemm_flops_per_step = 0.0;
-    // teacher-forced pass workspace (grown on demand, rgrg_decoder_lm_forward)
-    float *tf_x = nullptr, *tf_xn = nullptr, *tf_qkv = nullptr, *tf_att = nullptr, *tf_ff = nullptr, *tf_logits = nullptr,
-          *tf_ws = nullptr, *tf_row_loss = nullptr;
-    int* tf_row_valid = nullptr;
-    size_t tf_rows = 0, tf_ws_floats = 0;
-    // training pass (rgrg_decoder_lm_loss_grad): saved activations and gradient work space, grown on demand
-    float *tr_xs = nullptr, *tr_qkv = nullptr, *tr_ffpre = nullptr, *tr_ff = nullptr, *tr_dx = nullptr, *tr_dbig = nullptr,
-          *tr_dxn = nullptr, *tr_logits = nullptr, *tr_dukv = nullptr, *tr_t1 = nullptr, *tr_t2 = nullptr, *tr_dimg = nullptr,
-          *tr_dh1 = nullptr, *tr_row_lse = nullptr, *tr_att = nullptr, *tr_lse = nullptr, *tr_delta = nullptr;
-    int* tr_count = nullptr;
-    size_t tr_rows = 0, tr_seqs = 0;
-    // 16-bit activation flow of the training pass (autocast, > 128 token rows; round 5): every GEMM input is written as 16 bit
-    // by its producer - LayerNorm outputs, attention outputs, gelu outputs + the saved c_fc pre-activations of every layer,
-    // masked gradients, d(c_fc output), d(qkv), d(logits) of the chunk
-    unsigned short *tr_xn16 = nullptr, *tr_att16 = nullptr, *tr_ff16 = nullptr, *tr_ffpre16 = nullptr, *tr_dx16 = nullptr,
-                   *tr_dff16 = nullptr, *tr_dqkv16 = nullptr, *tr_dl16 = nullptr;
-    // ... and, for T + 1 <= 128 keys, the 16-bit attention kernels (attn_train16.hip): q / k / v and the attention output of
-    // every layer kept as 16 bit, d(attention output) and the image key / value of slot 0 as 16 bit
-    unsigned short *tr_qkv16 = nullptr, *tr_datt16 = nullptr, *tr_ukv16 = nullptr;
-    bool tr_a16 = false;
-    bool tr_h16 = false;       // what the current training work space was reserved for
-    size_t tr_chunk = 0;       // token rows per lm_head / cross-entropy chunk of that reservation
-    bool have_wT = false;
-    int bf16_gemms = 0;  // 1 (bf16) / 2 (fp16): 16-bit-weight MFMA GEMMs on the many-sequence path (not bit-exact; opt-in)
-    int f16() const { return bf16_gemms == 2 ? 1 : 0; }   // the 16-bit type of that mode
-    unsigned short *xn16 = nullptr, *att16 = nullptr, *ff16 = nullptr;  // bf16 activations of that path (GEMM inputs)
-    float* sk_ws = nullptr;     // split-K work space of the N = 1024 projections of the many-sequence decode step (gemm_bf16.hip)
-    unsigned* sk_cnt = nullptr;
-    int sk_attn = 0, sk_mlp = 0; // K slices of attn_proj / mlp_proj there (RGRG_SK_ATTN / RGRG_SK_MLP; 1 = off; -1 = automatic: 2 / 4 slices for a
-                                 // step of <= 256 rows - 32-64 output tiles for 256 CUs - and none above)
-    int step_rows = 0;           // token rows of the many-sequence step being enqueued (all row ranges together)
-    float* ln_stat = nullptr;   // [rows][16][2]: per-row (sum, sum of squares) slots (one per 64 columns) of the residual stream (folded LayerNorm)
-    bool ln_fold = true;        // 16-bit path: LayerNorms folded into the GEMMs around them; RGRG_LN_FOLD=0: ln_rows launches (A/B)
-    bool tr_seen_a16 = false, tr_seen_a32 = false, tr_seen_h16 = false, tr_seen_h32 = false, tr_seen_h16_a32 = false;   // tr_reserve: modes seen
-    float* key_mask = nullptr;             // [rows][T] additive padding mask of the cache slots (forward(use_cache=True) with padding)
-    const float* key_mask_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached when a mask was given
-    const long long* tf_pos = nullptr;   // position_ids of the NEXT teacher-forced pass (rgrg_decoder_set_lm_positions), [tf_pos_rows] int64
-    int tf_pos_rows = 1;
-    // rgrg_decoder_trace_step: one hipEvent after every launch of an eagerly enqueued step, on the stream it was launched on
-    struct TraceMark { hipEvent_t ev; int r0; int tag; };
-    std::vector<TraceMark>* trace = nullptr;
-    bool w16_fused = true;      // under autocast 33-128 rows run the fused plan on 16-bit weights (skinny_direct.inc W16); RGRG_W16_FUSED=0: the
-                                // many-sequence 16-bit path from 33 rows on (A/B)
-    int kp_gemms = 2;           // ... and run on the K-parity ping-pong kernel (gemm_kp.inc, round 6): RGRG_GEMM_KP = 0 none (the LDS-DMA kernel), 1 all four,
-                                // 2 (default) the producers only (attn_proj / mlp_proj, N = 1024), 3 the consumers only (c_attn / c_fc, 128 x 128 row-split kernel).
-                                // Measured per mode: profiles/r06_step_trace_v3.log
-    int gemm_launches_per_step = 0;
-    void* a16_scratch = nullptr;   // bf16 copy of an fp32 GEMM input (teacher-forced / training passes under autocast)
-    size_t a16_bytes = 0;
-    const int* pos_override_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached: per-row embedding positions
-    int* row_pos = nullptr;                  // [rows] buffer behind it
-    // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
-    // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
-    int logits_stale_rows = 0;
-    bool logits_valid = false;   // d->logits / the retained ln_f rows belong to the last step of a completed generate / beam / cached call (ADVICE r05:
-                                 // the timing hooks and a precision change overwrite them - rgrg_decoder_copy_last_logits then refuses)
-    // enqueue_step: extra streams + fork / join events of the multi-range many-sequence step (RGRG_DECODE_CHAINS)
-    hipStream_t streams_x[MAX_CHAINS - 1] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_CHAINS - 1] = {};
-    int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
-                      // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
-                      // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
-};
-
-namespace rgrg {
-
-static int dmalloc(rgrg_decoder* d, void** p, size_t bytes, bool zero) {
+// ------------------------------------------------------------------ decoder object (struct rgrg_decoder: decoder_internal.h)
+int dmalloc(rgrg_decoder* d, void** p, size_t bytes, bool zero) {
     RGRG_HIP(hipMalloc(p, bytes));
     d->allocs.push_back(*p);
     if (zero) RGRG_HIP(hipMemset(*p, 0, bytes));
@@ -1837,8 +1000,8 @@ static bool kv_is_bf16(const rgrg_decoder* d, int rows) { return d->bf16_gemms &
 // Y[:M] = act(X W^T + b + R).  Prefill GEMMs (packed, <= 128 rows): LDS-staged weight-streaming kernel (+ a small
 // reduce kernel when the layer splits K over workgroups); everything else: tiled MFMA GEMM (fp32, or the bf16-weight
 // kernel in the opt-in bf16 mode, optionally with bf16 activations in / out).
-static int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act,
-                  bool count, const unsigned short* X16 = nullptr, unsigned short* Y16 = nullptr, const GemmLnFold* ln = nullptr) {
+int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act,
+           bool count, const unsigned short* X16, unsigned short* Y16, const GemmLnFold* ln) {
     if (M <= skinny_max_rows() && l.packed && !l.direct) {
         // up to 4 row tiles of 32 sequences in ONE launch: the weights stay in registers across the tiles
         SkinnyArgs a{X, l.packed, l.b, R, Y, d->part, M, l.K, l.N, l.NT, l.KS, ldy, act};
@@ -2125,8 +1288,7 @@ static int trace_mark(rgrg_decoder* d, int r0, int tag) {
 // One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
 //   embed+ln1 | per layer: c_attn, attention, attn_proj (+ residual), ln2, c_fc+gelu, mlp_proj (+ residual),
 //   ln1 of the next layer / ln_f | lm_head, per-32-column arg-max candidates, argmax + bookkeeping
-static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = nullptr, const int* src = nullptr,
-                        bool beam = false) {
+int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, const int* src, bool beam) {
     if (S <= decode_row_limit(d)) return enqueue_step_fused(d, S, count, tok_override, src, beam);
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     d->step_rows = S;
@@ -2182,16 +1344,14 @@ static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_overr
             if ((rc2 = linear(d, w.attn_proj, d->att + o, x, x, rows, D, RGRG_ACT_NONE, count, att16r, nullptr, pfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 2))) return rc2;
             if (!fold) {
-                hipLaunchKernelGGL(ln_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, rs, x, w.ln2_g, w.ln2_b, xn, D, xn16r, d->f16(), rows);
-                RGRG_LAUNCH_CHECK();
+                if ((rc2 = launch_ln_rows(x, w.ln2_g, w.ln2_b, xn, D, xn16r, d->f16(), rows, rs))) return rc2;
             }
             if ((rc2 = linear(d, w.c_fc, xn, nullptr, d->ff + 4 * o, rows, 4 * D, RGRG_ACT_GELU_NEW, count, xn16r, ff16r, cfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 3))) return rc2;
             if ((rc2 = linear(d, w.mlp_proj, d->ff + 4 * o, x, x, rows, D, RGRG_ACT_NONE, count, ff16r, nullptr, pfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 4))) return rc2;
             if (!fold || l + 1 == d->n_layer) {
-                hipLaunchKernelGGL(ln_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, rs, x, ng, nb, xn, D, xn16r, d->f16(), rows);
-                RGRG_LAUNCH_CHECK();
+                if ((rc2 = launch_ln_rows(x, ng, nb, xn, D, xn16r, d->f16(), rows, rs))) return rc2;
                 if ((rc2 = trace_mark(d, r0, 1001))) return rc2;
             }
         }
@@ -2221,7 +1381,7 @@ static int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_overr
     return RGRG_OK;
 }
 
-static int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1) {
+int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
     hipStream_t st = d->stream;
     const int D = d->D;
     hipLaunchKernelGGL(decode_reset_kernel, dim3(64), dim3(256), 0, st, d->ids, d->max_len, d->finished, d->step,
@@ -2246,6 +1406,8 @@ static int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_m
 }
 
 }  // namespace rgrg
+
+using namespace rgrg;
 
 extern "C" size_t rgrg_decoder_kv_cache_bytes(int n_layer, int max_seqs, int max_len) {
     return (size_t)n_layer * 2 * (size_t)max_seqs * 16 * (size_t)(max_len + 1) * 64 * sizeof(float);
@@ -2380,18 +1542,13 @@ extern "C" int rgrg_decoder_create_with_cache(const rgrg_decoder_weights* w, int
     return RGRG_OK;
 }
 
-namespace rgrg {
-static void tf_free(rgrg_decoder* d);
-static void tr_free(rgrg_decoder* d);
-}
-
 extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
     if (!d) return;
     for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);
     for (void* p : d->allocs) (void)hipFree(p);
-    tf_free(d);
-    tr_free(d);
-    if (d->a16_scratch) (void)hipFree(d->a16_scratch);
+    d->tf.free();
+    d->tr.free();
+    if (d->tr.a16_scratch) (void)hipFree(d->tr.a16_scratch);
     if (d->h_done) (void)hipHostFree(d->h_done);
     for (hipEvent_t e : d->ev_poll)
         if (e) (void)hipEventDestroy(e);
@@ -2473,206 +1630,6 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
     return RGRG_OK;
 }
 
-// ------------------------------------------------------------------ beam search (host side)
-// BeamHypotheses / BeamSearchScorer of transformers 4.19.2 (used by language_model.py:457-464, :570-578,
-// :597-605), restated on the host: hypothesis scores, worst_score and the is_done test are double arithmetic
-// (HF does them on Python floats obtained through .item()), beam scores stay float32.
-namespace rgrg {
-struct Hyp { double score; std::vector<long long> toks; };
-struct BeamHyps {
-    std::vector<Hyp> beams;
-    double worst = 1e9;
-    void add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp) {
-        const double score = sum_logprobs / std::pow((double)toks.size(), lp);
-        if ((int)beams.size() < nb || score > worst) {
-            beams.push_back({score, toks});
-            if ((int)beams.size() > nb) {
-                int i0 = 0;  // sorted([(score, idx)]): smallest (score, idx) is dropped, worst = the next one
-                for (int i = 1; i < (int)beams.size(); ++i)
-                    if (beams[i].score < beams[i0].score) i0 = i;
-                beams.erase(beams.begin() + i0);
-                double w = beams[0].score;
-                for (auto& h : beams) w = h.score < w ? h.score : w;
-                worst = w;
-            } else {
-                worst = score < worst ? score : worst;
-            }
-        }
-    }
-    bool is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const {
-        if ((int)beams.size() < nb) return false;
-        if (early) return true;
-        return worst >= best_sum_logprobs / std::pow((double)cur_len, lp);
-    }
-};
-}  // namespace rgrg
-
-extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length,
-                                        int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
-                                        int out_ld, int* out_len, void* stream) {
-    RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && num_beams > 1 && num_beams <= (1 << 14));
-    RGRG_CHECK_ARG(num_return_sequences >= 1 && num_return_sequences <= num_beams);
-    const int nb = num_beams, K = 2 * nb, R = S * nb;
-    RGRG_CHECK_ARG(R <= d->max_seqs && max_length >= 2 && max_length <= d->max_len && out_ld >= max_length);
-    hipStream_t st = d->stream;
-    const bool wide = K > BEAM_K;   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
-    if (wide && d->wide_cap < (size_t)R * K) {
-        RGRG_HIP(hipStreamSynchronize(st));
-        for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);   // (captured beam steps bake the buffers in)
-        d->graphs.clear();
-        for (void** q : {(void**)&d->wide_val, (void**)&d->wide_tok, (void**)&d->wide_score}) {   // grown: the smaller buffers go
-            if (!*q) continue;
-            auto it = std::find(d->allocs.begin(), d->allocs.end(), *q);
-            if (it != d->allocs.end()) d->allocs.erase(it);
-            (void)hipFree(*q);
-            *q = nullptr;
-        }
-        d->wide_cap = 0;
-        int r;
-        if ((r = dmalloc(d, (void**)&d->wide_val, (size_t)R * K * 4, true)) || (r = dmalloc(d, (void**)&d->wide_tok, (size_t)R * K * 4, true)) ||
-            (r = dmalloc(d, (void**)&d->wide_score, (size_t)R * K * 4, true)))
-            return r;
-        d->wide_cap = (size_t)R * K;
-    }
-    RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
-    RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
-    // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
-    int rc = enqueue_prefill(d, feats, S, nb);
-    if (rc) return rc;
-    hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d->src_a, d->T, nb, R, d->step);
-    RGRG_LAUNCH_CHECK();
-
-    std::vector<std::vector<long long>> ids(R, std::vector<long long>(1, BOS_ID));
-    std::vector<float> beam_scores(R, 0.f), h_score((size_t)S * K);
-    std::vector<int> beam_tok(R, BOS_ID), parent(R, 0), h_tok((size_t)S * K), h_beam((size_t)S * K);
-    for (int r = 0; r < R; ++r) beam_scores[r] = (r % nb == 0) ? 0.f : -1e9f;
-    std::vector<BeamHyps> hyps(S);
-    std::vector<char> done(S, 0);
-    const double lp = (double)length_penalty;
-    int* src_cur = d->src_a;
-    int* src_nxt = d->src_b;
-    int cur_len = 1;
-    std::vector<float> nscore(R);
-    std::vector<int> ntok(R), nidx(R);
-    d->logits_stale_rows = 0;   // beam steps write d->logits
-    d->logits_valid = false;
-    while (true) {
-        RGRG_HIP(hipMemcpyAsync(d->beam_tok, beam_tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-        RGRG_HIP(hipMemcpyAsync(d->beam_scores, beam_scores.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
-        {
-            // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed
-            const int parity = (src_cur == d->src_a) ? 1 : 2;
-            hipGraphExec_t exec = nullptr;
-            for (auto& g : d->graphs)
-                if (g.S == R && g.key2 == parity && g.key3 == nb) exec = g.exec;
-            if (!exec) {
-                hipGraph_t graph = nullptr;
-                RGRG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_step(d, R, false, d->beam_tok, src_cur, true);
-                if (!rc && !wide) {
-#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(R), dim3(THREADS_), 0, st, d->logits, d->ld_logits, d->V, K, \
-                                                      d->row_max, d->row_logsum, d->top_val, d->top_tok)
-                    if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
-#undef BEAM_TOPK
-                    hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
-                                       d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
-                } else if (!rc) {
-                    hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
-                                       d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
-                    hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, d->row_max, d->row_logsum, d->wide_val, d->wide_tok,
-                                       d->beam_scores, nb, K, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam);
-                }
-                hipError_t e = hipStreamEndCapture(st, &graph);
-                if (rc) return rc;
-                if (e != hipSuccess) { set_error("beam: hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
-                RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-                d->graphs.push_back({R, exec, parity, nb});
-            }
-            RGRG_HIP(hipGraphLaunch(exec, st));
-        }
-        RGRG_HIP(hipMemcpyAsync(h_score.data(), d->cand_score, (size_t)S * K * sizeof(float), hipMemcpyDeviceToHost, st));
-        RGRG_HIP(hipMemcpyAsync(h_tok.data(), d->cand_tok, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
-        RGRG_HIP(hipMemcpyAsync(h_beam.data(), d->cand_beam, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
-        RGRG_HIP(hipStreamSynchronize(st));
-        // BeamSearchScorer.process
-        for (int b = 0; b < S; ++b) {
-            if (done[b]) {
-                for (int j = 0; j < nb; ++j) { nscore[b * nb + j] = 0.f; ntok[b * nb + j] = PAD_ID; nidx[b * nb + j] = 0; }
-                continue;
-            }
-            int beam_idx = 0;
-            for (int rank = 0; rank < K; ++rank) {
-                const int tok = h_tok[(size_t)b * K + rank];
-                const float sc = h_score[(size_t)b * K + rank];
-                const int row = b * nb + h_beam[(size_t)b * K + rank];
-                if (tok == EOS_ID) {
-                    if (rank >= nb) continue;
-                    hyps[b].add(ids[row], (double)sc, nb, lp);
-                } else {
-                    nscore[b * nb + beam_idx] = sc; ntok[b * nb + beam_idx] = tok; nidx[b * nb + beam_idx] = row;
-                    ++beam_idx;
-                }
-                if (beam_idx == nb) break;
-            }
-            if (beam_idx < nb) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
-            done[b] = done[b] || hyps[b].is_done((double)h_score[(size_t)b * K], cur_len, early_stopping != 0, nb, lp);
-        }
-        // input_ids = cat(input_ids[beam_idx], tokens); cache "re-order" = new ancestor table
-        std::vector<std::vector<long long>> nids(R);
-        for (int r = 0; r < R; ++r) { nids[r] = ids[nidx[r]]; nids[r].push_back(ntok[r]); }
-        ids.swap(nids);
-        beam_scores = nscore;
-        for (int r = 0; r < R; ++r) { beam_tok[r] = ntok[r]; parent[r] = nidx[r]; }
-        ++cur_len;
-        bool all_done = true;
-        for (int b = 0; b < S; ++b) all_done = all_done && done[b];
-        if (all_done || cur_len >= max_length) break;
-        RGRG_HIP(hipMemcpyAsync(d->beam_parent, parent.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_cur, src_nxt, d->beam_parent, d->step, d->T, R);
-        RGRG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(beam_step_inc_kernel, dim3(1), dim3(64), 0, st, d->step);
-        RGRG_LAUNCH_CHECK();
-        int* tmp = src_cur; src_cur = src_nxt; src_nxt = tmp;
-    }
-    // BeamSearchScorer.finalize (num_beam_hyps_to_keep = 1)
-    for (int b = 0; b < S; ++b) {
-        if (done[b]) continue;
-        for (int j = 0; j < nb; ++j) hyps[b].add(ids[b * nb + j], (double)beam_scores[b * nb + j], nb, lp);
-    }
-    // num_beam_hyps_to_keep best hypotheses per item: sorted(beams, key=score) is stable and pop() takes the last, i.e.
-    // descending score and, among equal scores, the LATER-added hypothesis first
-    const int keep = num_return_sequences, NR = S * keep;
-    std::vector<const std::vector<long long>*> best(NR);
-    int max_sent = 0, min_sent = 1 << 30;
-    for (int b = 0; b < S; ++b) {
-        const int nh = (int)hyps[b].beams.size();
-        if (nh < keep) { set_error("beam search: item %d has %d finished hypotheses, %d requested", b, nh, keep); return RGRG_ESTATE; }
-        std::vector<int> order(nh);
-        for (int j = 0; j < nh; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hyps[b].beams[x].score < hyps[b].beams[y].score; });
-        for (int j = 0; j < keep; ++j) {
-            best[b * keep + j] = &hyps[b].beams[order[nh - 1 - j]].toks;
-            const int len = (int)best[b * keep + j]->size();
-            max_sent = len > max_sent ? len : max_sent;
-            min_sent = len < min_sent ? len : min_sent;
-        }
-    }
-    const int L = (max_sent + 1 < max_length) ? max_sent + 1 : max_length;
-    std::vector<long long> dec((size_t)NR * L, PAD_ID);
-    for (int b = 0; b < NR; ++b) {
-        const int len = (int)best[b]->size();
-        for (int j = 0; j < len && j < L; ++j) dec[(size_t)b * L + j] = (*best[b])[j];
-        if (len < max_length) dec[(size_t)b * L + len] = EOS_ID;
-    }
-    RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), dec.data(), (size_t)L * sizeof(long long),
-                              (size_t)L * sizeof(long long), NR, hipMemcpyHostToDevice, st));
-    RGRG_HIP(hipStreamSynchronize(st));
-    *out_len = L;
-    d->logits_valid = true;
-    return RGRG_OK;
-}
-
 namespace rgrg {
 // forward(use_cache=True): attention_mask [S][L] over the L = past_len + T token keys -> additive mask of the cache slots,
 // slot 0 (the image key) never masked (language_model.py:316-334: a ones column is concatenated in front)
@@ -2702,663 +1659,6 @@ __global__ __launch_bounds__(256) void forward_cached_tokens_kernel(const long l
     if (s == 0) *step = position;
 }
 }  // namespace rgrg
-
-// ------------------------------------------------------------------ teacher-forced pass (host side)
-namespace rgrg {
-// A previous teacher-forced pass saw a token id outside [0, vocab): report it now (its loss was NaN), clear the flag
-static int check_id_error(rgrg_decoder* d) {
-    if (d->h_id_error && *d->h_id_error) {
-        *d->h_id_error = 0;
-        (void)hipMemsetAsync(d->id_error, 0, 2 * sizeof(int), d->stream);
-        set_error("index out of range in self: a token id of a previous teacher-forced pass was outside [0, %d)", d->V);
-        return RGRG_EINVAL;
-    }
-    return RGRG_OK;
-}
-__global__ void id_error_fold_kernel(int* __restrict__ e) {
-    if (threadIdx.x == 0 && blockIdx.x == 0 && e[0]) e[1] = 1;
-}
-// start of a pass (on the decoder stream, after the wait for the caller): this pass's error word starts clean
-static int id_error_begin(rgrg_decoder* d) {
-    RGRG_HIP(hipMemsetAsync(d->id_error, 0, sizeof(int), d->stream));
-    return RGRG_OK;
-}
-// end of a pass: fold this pass's word into the sticky one and mirror the sticky word to the host (asynchronously)
-static int id_error_end(rgrg_decoder* d) {
-    hipLaunchKernelGGL(id_error_fold_kernel, dim3(1), dim3(64), 0, d->stream, d->id_error);
-    RGRG_LAUNCH_CHECK();
-    RGRG_HIP(hipMemcpyAsync(d->h_id_error, d->id_error + 1, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    return RGRG_OK;
-}
-constexpr int TF_LOGIT_ROWS = 2048;  // lm_head + cross entropy run over chunks of this many token rows (412 MB of logits)
-
-static void tf_free(rgrg_decoder* d) {
-    float** fs[] = {&d->tf_x, &d->tf_xn, &d->tf_qkv, &d->tf_att, &d->tf_ff, &d->tf_logits, &d->tf_ws, &d->tf_row_loss};
-    for (float** f : fs) { if (*f) (void)hipFree(*f); *f = nullptr; }
-    if (d->tf_row_valid) (void)hipFree(d->tf_row_valid);
-    d->tf_row_valid = nullptr;
-    d->tf_rows = 0;
-    d->tf_ws_floats = 0;
-}
-
-static int tf_reserve(rgrg_decoder* d, size_t rows) {
-    if (rows <= d->tf_rows) return RGRG_OK;
-    tf_free(d);
-    const size_t D = (size_t)d->D;
-    const size_t chunk = rows < (size_t)TF_LOGIT_ROWS ? rows : (size_t)TF_LOGIT_ROWS;
-    d->tf_ws_floats = 4 * rows * D;  // split-K partials of the narrow (N = 1024) GEMMs when there are few row tiles
-    RGRG_HIP(hipMalloc((void**)&d->tf_x, rows * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_xn, rows * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_qkv, rows * 3 * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_att, rows * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_ff, rows * 4 * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_logits, chunk * (size_t)d->V * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_ws, d->tf_ws_floats * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_row_loss, rows * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tf_row_valid, rows * 4));
-    d->tf_rows = rows;
-    return RGRG_OK;
-}
-
-// tiled GEMM for the M = S*T token rows (never the skinny path: its buffers are sized for decode rows)
-// bf16-weight GEMM of the teacher-forced / training passes on an fp32 activation matrix: X is rounded to bf16 ONCE into a
-// scratch buffer (the same round-to-nearest-even the register-staged kernel applied tile by tile, so the operands are
-// identical) and the product runs on the LDS-DMA kernel - at M = S x T token rows it reaches 2-3x the register-staged rate.
-static int bf16_linear_f32in(rgrg_decoder* d, const float* X, const void* Wb, const float* b, const float* R, float* Y, int M, int N,
-                             int K, int ldy, int act) {
-    const size_t need = (size_t)M * K * sizeof(unsigned short);
-    if (need > d->a16_bytes) {
-        RGRG_HIP(hipStreamSynchronize(d->stream));  // the old buffer may still be read by a queued GEMM
-        if (d->a16_scratch) (void)hipFree(d->a16_scratch);
-        d->a16_scratch = nullptr; d->a16_bytes = 0;
-        RGRG_HIP(hipMalloc(&d->a16_scratch, need));
-        d->a16_bytes = need;
-    }
-    int rc = convert_f32_to_bf16(X, d->a16_scratch, (size_t)M * K, d->stream, d->f16());
-    if (rc) return rc;
-    return launch_gemm_bf16w_ex(nullptr, d->a16_scratch, Wb, b, R, Y, nullptr, M, N, K, ldy, act, d->stream, d->f16());
-}
-
-static int tf_linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act) {
-    if (d->bf16_gemms && l.wb && l.K % 256 == 0 && M > skinny_max_rows())
-        return bf16_linear_f32in(d, X, l.wb, l.b, R, Y, M, l.N, l.K, ldy, act);
-    return launch_gemm_dense(X, l.w, l.b, R, Y, M, l.N, l.K, ldy, act, d->tf_ws, d->tf_ws_floats, d->stream);
-}
-}  // namespace rgrg
-
-// position_ids of the teacher-forced passes (language_model.py:293-307): `pos` = int64 device array of S * T entries (per sentence)
-// or T entries (one row, broadcast), read by the NEXT rgrg_decoder_lm_forward / rgrg_decoder_lm_loss_grad call of that shape and
-// dropped by it; NULL = the default arange(T).  Like the token ids they index the token table (the reference's
-// wte[position_ids]) and are range-checked on the device.
-extern "C" int rgrg_decoder_set_lm_positions(rgrg_decoder* d, const int64_t* pos, int64_t n) {
-    RGRG_CHECK_ARG(d && (pos == nullptr || n > 0));
-    d->tf_pos = reinterpret_cast<const long long*>(pos);
-    d->tf_pos_rows = pos ? (int)n : 1;
-    return RGRG_OK;
-}
-
-extern "C" int rgrg_decoder_lm_forward(rgrg_decoder* d, const float* feats, const int64_t* input_ids,
-                                       const float* attention_mask, int S, int T, float* logits_out, float* loss_out,
-                                       void* stream) {
-    RGRG_CHECK_ARG(d && feats && input_ids && S > 0 && S <= d->max_seqs && T >= 1 && T <= TF_MAX_T && (logits_out || loss_out));
-    RGRG_CHECK_ARG(!loss_out || T >= 2);
-    RGRG_CHECK_ARG(!d->tf_pos || d->tf_pos_rows == T || d->tf_pos_rows == S * T);   // rgrg_decoder_set_lm_positions: [T] or [S * T]
-    const int D = d->D, M = S * T;
-    int rc = check_id_error(d);
-    if (rc) return rc;
-    if ((rc = tf_reserve(d, (size_t)M))) return rc;
-    hipStream_t caller = as_stream(stream), st = d->stream;
-    RGRG_HIP(hipEventRecord(d->ev_in, caller));
-    RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
-    if ((rc = id_error_begin(d))) return rc;
-    // feature_space_transformation_nn (:284), then uk / uv of every layer in one GEMM (:145-150)
-    RGRG_HIP(hipMemcpyAsync(d->feats, feats, (size_t)S * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if ((rc = linear(d, d->fst0, d->feats, nullptr, d->h1, S, D, RGRG_ACT_RELU, false))) return rc;
-    if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, S, D, RGRG_ACT_NONE, false))) return rc;
-    if ((rc = linear(d, d->ukv, d->img, nullptr, d->ukv_out, S, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
-    const long long* ids = reinterpret_cast<const long long*>(input_ids);
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       d->tf_x, d->tf_xn, D, d->V, d->id_error, d->tf_pos, d->tf_pos_rows);
-    RGRG_LAUNCH_CHECK();
-    d->tf_pos = nullptr; d->tf_pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
-    for (int l = 0; l < d->n_layer; ++l) {
-        const LayerW& w = d->layers[l];
-        const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
-        const float* nb = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_b : d->lnf_b;
-        if ((rc = tf_linear(d, w.c_attn, d->tf_xn, nullptr, d->tf_qkv, M, 3 * D, RGRG_ACT_NONE))) return rc;
-        if ((rc = launch_attn_prefill(d->tf_qkv, d->ukv_out, d->ld_ukv, l * 2 * D, attention_mask, d->tf_att, S, d->H, T, nullptr,
-                                      DropoutParams{0ull, 0u, 0.f}, st)))
-            return rc;
-        if ((rc = tf_linear(d, w.attn_proj, d->tf_att, d->tf_x, d->tf_x, M, D, RGRG_ACT_NONE))) return rc;
-        hipLaunchKernelGGL(ln_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, d->tf_x, w.ln2_g, w.ln2_b, d->tf_xn, D, (unsigned short*)nullptr, 0, M);
-        RGRG_LAUNCH_CHECK();
-        if ((rc = tf_linear(d, w.c_fc, d->tf_xn, nullptr, d->tf_ff, M, 4 * D, RGRG_ACT_GELU_NEW))) return rc;
-        if ((rc = tf_linear(d, w.mlp_proj, d->tf_ff, d->tf_x, d->tf_x, M, D, RGRG_ACT_NONE))) return rc;
-        hipLaunchKernelGGL(ln_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, d->tf_x, ng, nb, d->tf_xn, D, (unsigned short*)nullptr, 0, M);
-        RGRG_LAUNCH_CHECK();
-    }
-    // lm_head (tied to wte, no bias) and the loss, over chunks of token rows
-    for (int r0 = 0; r0 < M; r0 += TF_LOGIT_ROWS) {
-        const int rows = (M - r0 < TF_LOGIT_ROWS) ? M - r0 : TF_LOGIT_ROWS;
-        float* lg = logits_out ? logits_out + (size_t)r0 * d->V : d->tf_logits;
-        if ((rc = tf_linear(d, d->lm_head, d->tf_xn + (size_t)r0 * D, nullptr, lg, rows, d->V, RGRG_ACT_NONE))) return rc;
-        if (loss_out) {
-            hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, lg, (size_t)d->V, d->V, r0, ids, attention_mask, T,
-                               d->tf_row_loss, d->tf_row_valid, (float*)nullptr, d->id_error);
-            RGRG_LAUNCH_CHECK();
-        }
-    }
-    if (loss_out) {
-        hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf_row_loss, d->tf_row_valid, M, loss_out, (int*)nullptr,
-                           d->id_error);
-        RGRG_LAUNCH_CHECK();
-    }
-    if ((rc = id_error_end(d))) return rc;
-    // the caller's stream continues after this pass (no host synchronisation)
-    RGRG_HIP(hipEventRecord(d->ev_in, st));
-    RGRG_HIP(hipStreamWaitEvent(caller, d->ev_in, 0));
-    return RGRG_OK;
-}
-
-// ------------------------------------------------------------------ training pass: loss + gradients (host side)
-namespace rgrg {
-// train_ops.hip
-int launch_gelu_apply(const float* pre, float* out, size_t n, hipStream_t st);
-int launch_gelu_backward(float* d, const float* pre, size_t n, hipStream_t st);
-int launch_relu_backward(float* d, const float* h, size_t n, hipStream_t st);
-int launch_ln_backward(const float* dy, const float* x, const float* g, float* out, int rows, int D, int accumulate, hipStream_t st);
-int launch_ce_backward(float* logits, size_t ld, int V, int row0, int rows, const long long* ids, const int* row_valid,
-                       const float* row_lse, const int* n_scored, float scale, const int* id_error, hipStream_t st);
-int launch_transpose_pad(const float* src, float* dst, int R, int Cc, int Rp, hipStream_t st);
-int launch_colsum(const float* src, float* out, int R, int Cc, hipStream_t st);
-int launch_attn_backward(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, const float* d_att,
-                         const float* att, const float* lse, float* delta, float* d_qkv, float* d_ukv, int S, int H, int T,
-                         DropoutParams drop, hipStream_t st, unsigned short* d_qkv16 = nullptr, int f16 = 0, float ukv_scale = 1.0f);
-bool attn16_supported(int T);
-int launch_attn16_forward(const unsigned short* qkv16, const unsigned short* ukv16, int ld_ukv, int kcol, const float* am,
-                          unsigned short* out16, float* lse, int S, int H, int T, DropoutParams drop, int f16, hipStream_t st);
-int launch_attn16_backward(const unsigned short* qkv16, const unsigned short* ukv16, int ld_ukv, int kcol, const float* am,
-                           const unsigned short* d_att16, const unsigned short* att16, const float* lse, unsigned short* d_qkv16,
-                           float* d_ukv, int S, int H, int T, DropoutParams drop, float ukv_scale, int f16, hipStream_t st);
-int launch_resid_dropout_ln16(const float* y, const unsigned short* y16, const float* resid, float* x, const float* g, const float* b,
-                              unsigned short* xn16, DropoutParams drop, int f16, int rows, int D, hipStream_t st);
-int launch_ln_backward16(const float* dy, const unsigned short* dy16, const float* x, const float* g, float* out, unsigned short* out16,
-                         int rows, int D, int accumulate, DropoutParams drop, int f16, hipStream_t st);
-int launch_ce_backward16(const float* logits, size_t ld, int V, int row0, int rows, const long long* ids, const int* row_valid,
-                         const float* row_lse, const int* n_scored, float scale, const int* id_error, unsigned short* out16, int f16,
-                         hipStream_t st);
-int launch_dropout_add(const float* src, const float* resid, float* out, size_t n, DropoutParams drop, hipStream_t st);
-
-static int pad32(int n) { return (n + 31) / 32 * 32; }
-static int pad256(int n) { return (n + 255) / 256 * 256; }  // K granularity of the bf16 GEMM pipeline
-
-// transposed copies of the frozen weights the activation gradients flow through (made once)
-static int make_wT(rgrg_decoder* d, Lin& l) {
-    const int Np = pad256(l.N);
-    int rc;
-    if (!l.wT) {
-        if ((rc = dmalloc(d, (void**)&l.wT, (size_t)l.K * Np * sizeof(float), false))) return rc;
-        if ((rc = launch_transpose_pad(l.w, l.wT, l.N, l.K, Np, d->stream))) return rc;
-    }
-    if (d->bf16_gemms && (!l.wTb || l.wTb_f16 != d->f16())) {   // (re)made in the current 16-bit type
-        if (!l.wTb && (rc = dmalloc(d, &l.wTb, (size_t)l.K * Np * 2, false))) return rc;
-        if ((rc = convert_f32_to_bf16(l.wT, l.wTb, (size_t)l.K * Np, d->stream, d->f16()))) return rc;
-        l.wTb_f16 = d->f16();
-    }
-    return RGRG_OK;
-}
-
-static int ensure_wT(rgrg_decoder* d) {
-    if (d->have_wT && (!d->bf16_gemms || (d->layers[0].c_attn.wTb && d->layers[0].c_attn.wTb_f16 == d->f16()))) return RGRG_OK;
-    int rc;
-    if ((rc = make_wT(d, d->lm_head)) || (rc = make_wT(d, d->ukv)) || (rc = make_wT(d, d->fst2))) return rc;
-    for (auto& w : d->layers)
-        if ((rc = make_wT(d, w.c_attn)) || (rc = make_wT(d, w.attn_proj)) || (rc = make_wT(d, w.c_fc)) || (rc = make_wT(d, w.mlp_proj)))
-            return rc;
-    d->have_wT = true;
-    return RGRG_OK;
-}
-
-static void tr_free(rgrg_decoder* d) {
-    float** fs[] = {&d->tr_xs, &d->tr_qkv, &d->tr_ffpre, &d->tr_ff, &d->tr_dx, &d->tr_dbig, &d->tr_dxn, &d->tr_logits,
-                    &d->tr_dukv, &d->tr_t1, &d->tr_t2, &d->tr_dimg, &d->tr_dh1, &d->tr_row_lse, &d->tr_att, &d->tr_lse, &d->tr_delta};
-    for (float** f : fs) { if (*f) (void)hipFree(*f); *f = nullptr; }
-    if (d->tr_count) (void)hipFree(d->tr_count);
-    d->tr_count = nullptr;
-    unsigned short** hs[] = {&d->tr_xn16, &d->tr_att16, &d->tr_ff16, &d->tr_ffpre16, &d->tr_dx16, &d->tr_dff16, &d->tr_dqkv16, &d->tr_dl16,
-                             &d->tr_qkv16, &d->tr_datt16, &d->tr_ukv16};
-    for (unsigned short** h : hs) { if (*h) (void)hipFree(*h); *h = nullptr; }
-    d->tr_rows = d->tr_seqs = 0;
-    d->tr_chunk = 0;
-}
-
-// The 16-bit flow runs lm_head + cross entropy over up to 16 384 token rows at a time (a configs[4] step = 14 848 rows in ONE
-// chunk: 3.3 GB of fp32 logits + 1.65 GB of 16-bit d(logits), 116 x 394 tiles per GEMM instead of eight launches of 16 x 394)
-constexpr int TR_LOGIT_ROWS_H16 = 16384;
-
-static int tr_reserve(rgrg_decoder* d, size_t rows, size_t seqs, bool h16, bool a16) {
-    // The work space holds the buffers of EVERY mode seen so far (16-bit / fp32 activation flow x 16-bit / fp32 attention): a16
-    // follows T + 1 <= 128 and h16 follows S * T > 128, so batches whose padded length moves across those edges flip the mode
-    // back and forth - freeing and re-allocating multi-GB buffers (plus a 1.6 GB memset) on every flip.  A mode
-    // that is new to this decoder costs one re-allocation; after that only a larger batch does.
-    bool& seen_a = a16 ? d->tr_seen_a16 : d->tr_seen_a32;
-    bool& seen_h = h16 ? d->tr_seen_h16 : d->tr_seen_h32;
-    const size_t cap = h16 ? (size_t)TR_LOGIT_ROWS_H16 : (size_t)TF_LOGIT_ROWS;
-    if (rows <= d->tr_rows && seqs <= d->tr_seqs && seen_a && seen_h && (!h16 || a16 || d->tr_seen_h16_a32 || d->tr_seen_a16)) {
-        d->tr_h16 = h16; d->tr_a16 = a16;
-        d->tr_chunk = d->tr_rows < cap ? d->tr_rows : cap;
-        return RGRG_OK;
-    }
-    const size_t keep = d->tr_rows, keep_s = d->tr_seqs;
-    tr_free(d);
-    seen_a = true; seen_h = true;
-    if (h16 && !a16) d->tr_seen_h16_a32 = true;
-    rows = rows > keep ? rows : keep;
-    seqs = seqs > keep_s ? seqs : keep_s;
-    const size_t D = (size_t)d->D, L = (size_t)d->n_layer, Sp = (size_t)pad32((int)seqs), VP = (size_t)pad256(d->V);
-    const size_t cap_all = d->tr_seen_h16 ? (size_t)TR_LOGIT_ROWS_H16 : (size_t)TF_LOGIT_ROWS;   // the larger chunk of the modes seen
-    const size_t chunk = rows < cap_all ? rows : cap_all;
-    d->tr_h16 = h16;
-    d->tr_a16 = a16;
-    d->tr_chunk = rows < cap ? rows : cap;
-    RGRG_HIP(hipMalloc((void**)&d->tr_xs, (2 * L + 1) * rows * D * 4));
-    if (d->tr_seen_a16) {
-        RGRG_HIP(hipMalloc((void**)&d->tr_qkv16, L * rows * 3 * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_att16, L * rows * D * 2));   // (the fp32-attention 16-bit flow uses its first rows x D)
-        RGRG_HIP(hipMalloc((void**)&d->tr_datt16, rows * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_ukv16, seqs * (size_t)d->ld_ukv * 2));
-    }
-    if (d->tr_seen_a32) {
-        RGRG_HIP(hipMalloc((void**)&d->tr_qkv, L * rows * 3 * D * 4));
-        RGRG_HIP(hipMalloc((void**)&d->tr_att, L * rows * D * 4));
-        RGRG_HIP(hipMalloc((void**)&d->tr_delta, rows * (size_t)d->H * 4));
-        if (d->tr_seen_h16_a32 && !d->tr_seen_a16) RGRG_HIP(hipMalloc((void**)&d->tr_att16, rows * D * 2));
-    }
-    if (d->tr_seen_h16) {
-        RGRG_HIP(hipMalloc((void**)&d->tr_xn16, rows * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_ff16, rows * 4 * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_ffpre16, L * rows * 4 * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_dx16, rows * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_dff16, rows * 4 * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_dqkv16, rows * 3 * D * 2));
-        RGRG_HIP(hipMalloc((void**)&d->tr_dl16, chunk * VP * 2));
-        RGRG_HIP(hipMemset(d->tr_dl16, 0, chunk * VP * 2));   // the K-padding columns stay 0 for the backward GEMM
-    }
-    if (d->tr_seen_h32) {
-        RGRG_HIP(hipMalloc((void**)&d->tr_ffpre, L * rows * 4 * D * 4));
-        RGRG_HIP(hipMalloc((void**)&d->tr_ff, rows * 4 * D * 4));
-    }
-    RGRG_HIP(hipMalloc((void**)&d->tr_dx, rows * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_dbig, rows * 4 * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_dxn, rows * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_logits, chunk * VP * 4));
-    RGRG_HIP(hipMemset(d->tr_logits, 0, chunk * VP * 4));  // the K-padding columns stay 0 for the backward GEMM
-    RGRG_HIP(hipMalloc((void**)&d->tr_dukv, seqs * (size_t)d->ld_ukv * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_t1, (size_t)d->ld_ukv * Sp * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_t2, D * Sp * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_dimg, seqs * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_dh1, seqs * D * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_row_lse, rows * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_lse, L * rows * (size_t)d->H * 4));
-    RGRG_HIP(hipMalloc((void**)&d->tr_count, 4));
-    d->tr_rows = rows;
-    d->tr_seqs = seqs;
-    return RGRG_OK;
-}
-
-// Y = X W^T (+R) on the fp32 tiled GEMM with the teacher-forced pass's split-K work space
-static int tr_gemm(rgrg_decoder* d, const float* X, const float* W, const float* b, const float* R, float* Y, int M, int N, int K,
-                   int ldy, int act = RGRG_ACT_NONE) {
-    return launch_gemm_dense(X, W, b, R, Y, M, N, K, ldy, act, d->tf_ws, d->tf_ws_floats, d->stream);
-}
-// frozen-weight GEMM of the training pass: forward (Y = X W^T + b) or activation gradient (Y = X W, on the transposed
-// copy); bf16 MFMA when the decoder is in bf16 mode (torch.autocast) and there are more than 128 token rows
-static int tr_lin(rgrg_decoder* d, const Lin& l, bool transposed, const float* X, const float* R, float* Y, int M, int ldy,
-                  int act = RGRG_ACT_NONE) {
-    const int N = transposed ? l.K : l.N, K = transposed ? pad256(l.N) : l.K;
-    const float* W = transposed ? l.wT : l.w;
-    const void* Wb = transposed ? l.wTb : l.wb;
-    const float* b = transposed ? nullptr : l.b;
-    if (d->bf16_gemms && Wb && K % 256 == 0 && M > skinny_max_rows())
-        return bf16_linear_f32in(d, X, Wb, b, R, Y, M, N, K, ldy, act);
-    return launch_gemm_dense(X, W, b, R, Y, M, N, K, ldy, act, d->tf_ws, d->tf_ws_floats, d->stream);
-}
-// the same on 16-bit activations that their producer wrote (16-bit flow): no conversion pass, optional 16-bit output and the
-// training epilogues (GemmLnFold::Ypre16 / G16)
-static int tr_lin16(rgrg_decoder* d, const Lin& l, bool transposed, const unsigned short* A16, const float* R, float* Y,
-                    unsigned short* Y16, int M, int ldy, int act = RGRG_ACT_NONE, const GemmLnFold* ex = nullptr) {
-    const int N = transposed ? l.K : l.N, K = transposed ? pad256(l.N) : l.K;
-    const void* Wb = transposed ? l.wTb : l.wb;
-    if (!Wb || K % 256 != 0) { set_error("decoder: 16-bit weights missing for a training GEMM (N %d, K %d)", N, K); return RGRG_EINVAL; }
-    return launch_gemm_bf16w_ex(nullptr, A16, Wb, transposed ? nullptr : l.b, R, Y, Y16, M, N, K, ldy, act, d->stream, d->f16(), ex);
-}
-
-// Forward (keeping what the backward needs), lm_head + loss + d(logits), and the backward through the 24 frozen blocks of
-// rgrg_decoder_lm_loss_grad in the 16-bit activation flow (tr_h16).  Per layer, forward: c_attn (xn16 -> qkv fp32) ->
-// attention (-> att fp32 + att16) -> attn_proj (-> y) -> x_mid = x_in + dropout(y), xn16 = ln_2(x_mid) [one kernel] ->
-// c_fc (-> ffpre16 kept + ff16 = gelu) -> mlp_proj (-> y) -> x_out = x_mid + dropout(y), xn16 = next LayerNorm [one kernel].
-// Backward: mlp_proj^T with the gelu' epilogue (dx16 -> dff16) -> c_fc^T (-> dxn) -> ln_2 backward (dx +=, dx16 = masked copy)
-// -> attn_proj^T (-> d_att) -> attention backward (-> dqkv16, d_ukv) -> c_attn^T (-> dxn) -> ln_1 backward.
-// fp16: gradients carry an internal scale of 2^15 from d(logits) to d_ukv (where the attention backward removes it), like
-// the reference's GradScaler keeps fp16 gradients out of the flush-to-zero range (train_full_model.py:172-237).
-static int tr_body16(rgrg_decoder* d, const long long* ids, const float* attention_mask, int S, int T, float loss_scale,
-                     float dropout_p, uint64_t dropout_seed, float* loss_out) {
-    const int D = d->D, M = S * T, L = d->n_layer, V = d->V, VP = pad256(V), LD = d->ld_ukv, f16 = d->f16();
-    hipStream_t st = d->stream;
-    const size_t MD = (size_t)M * D;
-    int rc;
-    auto xs = [&](int i) { return d->tr_xs + (size_t)i * MD; };
-    auto dp = [&](int l, int site) { return DropoutParams{dropout_seed, (unsigned)(l * 4 + site), dropout_p}; };
-    const DropoutParams none{0ull, 0u, 0.f};
-    const float s_int = f16 ? 32768.0f : 1.0f;
-    // [M, D] 16-bit scratch for a projection's output in front of the residual / dropout / LayerNorm kernel (forward: the
-    // buffer of the masked gradient, unused until the backward) and for d(LayerNorm output) in front of the LayerNorm-backward
-    // kernel (backward: the buffer of the LayerNorm outputs, unused after the forward).  16 bit like every GEMM output of the
-    // reference under autocast: half the store tail of the K = 1024 GEMMs, whose 256 KiB tiles leave through the HBM write path.
-    unsigned short* y16 = d->tr_dx16;
-    unsigned short* dy16 = d->tr_xn16;
-    const bool a16 = d->tr_a16;
-    if (a16 && (rc = convert_f32_to_bf16(d->ukv_out, d->tr_ukv16, (size_t)S * LD, st, f16))) return rc;
-
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       xs(0), d->tf_xn, D, d->V, d->id_error, d->tf_pos, d->tf_pos_rows);
-    RGRG_LAUNCH_CHECK();
-    d->tf_pos = nullptr; d->tf_pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
-    // self.drop on the embeddings (language_model.py:311) and ln_1 of layer 0 as 16 bit
-    if ((rc = launch_resid_dropout_ln16(xs(0), nullptr, nullptr, xs(0), d->layers[0].ln1_g, d->layers[0].ln1_b, d->tr_xn16, dp(0, 0), f16, M, D, st)))
-        return rc;
-    for (int l = 0; l < L; ++l) {
-        const LayerW& w = d->layers[l];
-        const float* ng = (l + 1 < L) ? d->layers[l + 1].ln1_g : d->lnf_g;
-        const float* nb = (l + 1 < L) ? d->layers[l + 1].ln1_b : d->lnf_b;
-        float* qkv = a16 ? nullptr : d->tr_qkv + (size_t)l * M * 3 * D;
-        unsigned short* ffpre16 = d->tr_ffpre16 + (size_t)l * M * 4 * D;
-        float* att = a16 ? nullptr : d->tr_att + (size_t)l * MD;
-        float* lse = d->tr_lse + (size_t)l * M * d->H;
-        if (a16) {
-            unsigned short* qkv16 = d->tr_qkv16 + (size_t)l * M * 3 * D;
-            unsigned short* att16 = d->tr_att16 + (size_t)l * MD;
-            if ((rc = tr_lin16(d, w.c_attn, false, d->tr_xn16, nullptr, nullptr, qkv16, M, 3 * D))) return rc;
-            if ((rc = launch_attn16_forward(qkv16, d->tr_ukv16, LD, l * 2 * D, attention_mask, att16, lse, S, d->H, T, dp(l, 1), f16, st)))
-                return rc;
-            if ((rc = tr_lin16(d, w.attn_proj, false, att16, nullptr, nullptr, y16, M, D))) return rc;
-        } else {
-            if ((rc = tr_lin16(d, w.c_attn, false, d->tr_xn16, nullptr, qkv, nullptr, M, 3 * D))) return rc;
-            if ((rc = launch_attn_prefill(qkv, d->ukv_out, LD, l * 2 * D, attention_mask, att, S, d->H, T, lse, dp(l, 1), st, d->tr_att16, f16)))
-                return rc;
-            if ((rc = tr_lin16(d, w.attn_proj, false, d->tr_att16, nullptr, nullptr, y16, M, D))) return rc;
-        }
-        if ((rc = launch_resid_dropout_ln16(nullptr, y16, xs(2 * l), xs(2 * l + 1), w.ln2_g, w.ln2_b, d->tr_xn16, dp(l, 2), f16, M, D, st))) return rc;
-        GemmLnFold pre{};
-        pre.Ypre16 = ffpre16;
-        if ((rc = tr_lin16(d, w.c_fc, false, d->tr_xn16, nullptr, nullptr, d->tr_ff16, M, 4 * D, RGRG_ACT_GELU_NEW, &pre))) return rc;
-        if ((rc = tr_lin16(d, w.mlp_proj, false, d->tr_ff16, nullptr, nullptr, y16, M, D))) return rc;
-        if ((rc = launch_resid_dropout_ln16(nullptr, y16, xs(2 * l + 1), xs(2 * l + 2), ng, nb, d->tr_xn16, dp(l, 3), f16, M, D, st))) return rc;
-    }
-    // lm_head + loss + d(logits) + d(ln_f output), chunk by chunk
-    hipLaunchKernelGGL(ce_valid_kernel, dim3((M + 255) / 256), dim3(256), 0, st, attention_mask, T, M, d->tf_row_loss, d->tf_row_valid);
-    RGRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf_row_loss, d->tf_row_valid, M, (float*)nullptr, d->tr_count);
-    RGRG_LAUNCH_CHECK();
-    const int chunk = (int)d->tr_chunk;
-    for (int r0 = 0; r0 < M; r0 += chunk) {
-        const int rows = (M - r0 < chunk) ? M - r0 : chunk;
-        if ((rc = tr_lin16(d, d->lm_head, false, d->tr_xn16 + (size_t)r0 * D, nullptr, d->tr_logits, nullptr, rows, VP))) return rc;
-        hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, d->tr_logits, (size_t)VP, V, r0, ids, attention_mask, T,
-                           d->tf_row_loss, d->tf_row_valid, d->tr_row_lse, d->id_error);
-        RGRG_LAUNCH_CHECK();
-        if ((rc = launch_ce_backward16(d->tr_logits, (size_t)VP, V, r0, rows, ids, d->tf_row_valid, d->tr_row_lse, d->tr_count,
-                                       loss_scale * s_int, d->id_error, d->tr_dl16, f16, st)))
-            return rc;
-        // (fp32: the 16-bit scratch still holds the ln_f rows the lm_head of later chunks reads)
-        if ((rc = tr_lin16(d, d->lm_head, true, d->tr_dl16, nullptr, d->tr_dxn + (size_t)r0 * D, nullptr, rows, D))) return rc;
-    }
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf_row_loss, d->tf_row_valid, M, loss_out, (int*)nullptr,
-                       d->id_error);
-    RGRG_LAUNCH_CHECK();
-    if ((rc = id_error_end(d))) return rc;
-    // backward through ln_f and the 24 frozen blocks; dx16 always carries the mask of the branch the gradient enters next
-    if ((rc = launch_ln_backward16(d->tr_dxn, nullptr, xs(2 * L), d->lnf_g, d->tr_dx, d->tr_dx16, M, D, 0, dp(L - 1, 3), f16, st))) return rc;
-    for (int l = L - 1; l >= 0; --l) {
-        const LayerW& w = d->layers[l];
-        float* qkv = a16 ? nullptr : d->tr_qkv + (size_t)l * M * 3 * D;
-        GemmLnFold gb{};
-        gb.G16 = d->tr_ffpre16 + (size_t)l * M * 4 * D;
-        if ((rc = tr_lin16(d, w.mlp_proj, true, d->tr_dx16, nullptr, nullptr, d->tr_dff16, M, 4 * D, RGRG_ACT_NONE, &gb))) return rc;
-        if ((rc = tr_lin16(d, w.c_fc, true, d->tr_dff16, nullptr, nullptr, dy16, M, D))) return rc;
-        if ((rc = launch_ln_backward16(nullptr, dy16, xs(2 * l + 1), w.ln2_g, d->tr_dx, d->tr_dx16, M, D, 1, dp(l, 2), f16, st))) return rc;
-        if (a16) {
-            if ((rc = tr_lin16(d, w.attn_proj, true, d->tr_dx16, nullptr, nullptr, d->tr_datt16, M, D))) return rc;
-            if ((rc = launch_attn16_backward(d->tr_qkv16 + (size_t)l * M * 3 * D, d->tr_ukv16, LD, l * 2 * D, attention_mask, d->tr_datt16,
-                                             d->tr_att16 + (size_t)l * MD, d->tr_lse + (size_t)l * M * d->H, d->tr_dqkv16, d->tr_dukv, S,
-                                             d->H, T, dp(l, 1), 1.0f / s_int, f16, st)))
-                return rc;
-        } else {
-            if ((rc = tr_lin16(d, w.attn_proj, true, d->tr_dx16, nullptr, d->tf_att, nullptr, M, D))) return rc;
-            if ((rc = launch_attn_backward(qkv, d->ukv_out, LD, l * 2 * D, attention_mask, d->tf_att, d->tr_att + (size_t)l * MD,
-                                           d->tr_lse + (size_t)l * M * d->H, d->tr_delta, nullptr, d->tr_dukv, S, d->H, T, dp(l, 1), st,
-                                           d->tr_dqkv16, f16, 1.0f / s_int)))
-                return rc;
-        }
-        if ((rc = tr_lin16(d, w.c_attn, true, d->tr_dqkv16, nullptr, nullptr, dy16, M, D))) return rc;
-        // the gradient enters layer l - 1 through its mlp branch (site 3); below layer 0 nothing reads the 16-bit copy
-        if ((rc = launch_ln_backward16(nullptr, dy16, xs(2 * l), w.ln1_g, d->tr_dx, l > 0 ? d->tr_dx16 : nullptr, M, D, 1,
-                                       l > 0 ? dp(l - 1, 3) : none, f16, st)))
-            return rc;
-    }
-    return RGRG_OK;
-}
-}  // namespace rgrg
-
-extern "C" int rgrg_decoder_lm_loss_grad(rgrg_decoder* d, const float* feats, const int64_t* input_ids,
-                                         const float* attention_mask, int S, int T, float loss_scale, float dropout_p,
-                                         uint64_t dropout_seed, float* loss_out,
-                                         float* grad_ukv_w, float* grad_ukv_b, float* grad_fst0_w, float* grad_fst0_b,
-                                         float* grad_fst2_w, float* grad_fst2_b, void* stream) {
-    RGRG_CHECK_ARG(d && feats && input_ids && loss_out && grad_ukv_w && grad_ukv_b && grad_fst0_w && grad_fst0_b && grad_fst2_w &&
-                   grad_fst2_b);
-    RGRG_CHECK_ARG(S > 0 && S <= d->max_seqs && T >= 2 && T <= TF_MAX_T);
-    RGRG_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f);
-    RGRG_CHECK_ARG(!d->tf_pos || d->tf_pos_rows == T || d->tf_pos_rows == S * T);   // rgrg_decoder_set_lm_positions: [T] or [S * T]
-    const int D = d->D, M = S * T, L = d->n_layer, V = d->V, VP = pad256(V), Sp = pad32(S), LD = d->ld_ukv;
-    int rc;
-    if ((rc = check_id_error(d))) return rc;
-    const bool h16 = d->bf16_gemms && M > skinny_max_rows();   // 16-bit activation flow (tr_body16)
-    const bool a16 = h16 && attn16_supported(T);               // ... with the 16-bit attention kernels
-    if ((rc = tf_reserve(d, (size_t)M)) || (rc = tr_reserve(d, (size_t)M, (size_t)S, h16, a16))) return rc;
-    hipStream_t caller = as_stream(stream), st = d->stream;
-    RGRG_HIP(hipEventRecord(d->ev_in, caller));
-    RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
-    if ((rc = id_error_begin(d))) return rc;
-    if ((rc = ensure_wT(d))) return rc;
-    const long long* ids = reinterpret_cast<const long long*>(input_ids);
-    const size_t MD = (size_t)M * D;
-    auto xs = [&](int i) { return d->tr_xs + (size_t)i * MD; };
-
-    // ---------------- forward, keeping what the backward needs (layer inputs, qkv, c_fc pre-activations)
-    RGRG_HIP(hipMemcpyAsync(d->feats, feats, (size_t)S * D * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if ((rc = linear(d, d->fst0, d->feats, nullptr, d->h1, S, D, RGRG_ACT_RELU, false))) return rc;
-    if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, S, D, RGRG_ACT_NONE, false))) return rc;
-    if ((rc = linear(d, d->ukv, d->img, nullptr, d->ukv_out, S, LD, RGRG_ACT_NONE, false))) return rc;
-    if (h16) {
-        if ((rc = tr_body16(d, ids, attention_mask, S, T, loss_scale, dropout_p, dropout_seed, loss_out))) return rc;
-    } else {
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       xs(0), d->tf_xn, D, d->V, d->id_error, d->tf_pos, d->tf_pos_rows);
-    RGRG_LAUNCH_CHECK();
-    d->tf_pos = nullptr; d->tf_pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
-    if (dropout_p > 0.f) {  // self.drop on the embeddings (language_model.py:311), then ln_1 of layer 0 again
-        if ((rc = launch_dropout_add(xs(0), nullptr, xs(0), MD, DropoutParams{dropout_seed, 0u, dropout_p}, st))) return rc;
-        hipLaunchKernelGGL(ln_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, xs(0), d->layers[0].ln1_g,
-                           d->layers[0].ln1_b, d->tf_xn, D, (unsigned short*)nullptr, 0, M);
-        RGRG_LAUNCH_CHECK();
-    }
-    for (int l = 0; l < L; ++l) {
-        const LayerW& w = d->layers[l];
-        const float* ng = (l + 1 < L) ? d->layers[l + 1].ln1_g : d->lnf_g;
-        const float* nb = (l + 1 < L) ? d->layers[l + 1].ln1_b : d->lnf_b;
-        float* qkv = d->tr_qkv + (size_t)l * M * 3 * D;
-        float* ffpre = d->tr_ffpre + (size_t)l * M * 4 * D;
-        if ((rc = tr_lin(d, w.c_attn, false, d->tf_xn, nullptr, qkv, M, 3 * D))) return rc;
-        float* att = d->tr_att + (size_t)l * MD;              // attention output and row log-sum-exp, kept per layer
-        float* lse = d->tr_lse + (size_t)l * M * d->H;
-        const DropoutParams dp_att{dropout_seed, (unsigned)(l * 4 + 1), dropout_p}, dp_r1{dropout_seed, (unsigned)(l * 4 + 2), dropout_p},
-            dp_r2{dropout_seed, (unsigned)(l * 4 + 3), dropout_p};
-        if ((rc = launch_attn_prefill(qkv, d->ukv_out, LD, l * 2 * D, attention_mask, att, S, d->H, T, lse, dp_att, st))) return rc;
-        if (dropout_p > 0.f) {  // resid_dropout: x_mid = x_in + dropout(c_proj(att))
-            if ((rc = tr_lin(d, w.attn_proj, false, att, nullptr, d->tr_dbig, M, D))) return rc;
-            if ((rc = launch_dropout_add(d->tr_dbig, xs(2 * l), xs(2 * l + 1), MD, dp_r1, st))) return rc;
-        } else if ((rc = tr_lin(d, w.attn_proj, false, att, xs(2 * l), xs(2 * l + 1), M, D))) return rc;
-        hipLaunchKernelGGL(ln_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, xs(2 * l + 1), w.ln2_g, w.ln2_b, d->tf_xn, D, (unsigned short*)nullptr, 0, M);
-        RGRG_LAUNCH_CHECK();
-        if ((rc = tr_lin(d, w.c_fc, false, d->tf_xn, nullptr, ffpre, M, 4 * D))) return rc;
-        if ((rc = launch_gelu_apply(ffpre, d->tr_ff, (size_t)M * 4 * D, st))) return rc;
-        if (dropout_p > 0.f) {  // mlp dropout: x_out = x_mid + dropout(c_proj(gelu(c_fc(.))))
-            if ((rc = tr_lin(d, w.mlp_proj, false, d->tr_ff, nullptr, d->tr_dxn, M, D))) return rc;
-            if ((rc = launch_dropout_add(d->tr_dxn, xs(2 * l + 1), xs(2 * l + 2), MD, dp_r2, st))) return rc;
-        } else if ((rc = tr_lin(d, w.mlp_proj, false, d->tr_ff, xs(2 * l + 1), xs(2 * l + 2), M, D))) return rc;
-        hipLaunchKernelGGL(ln_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, xs(2 * l + 2), ng, nb, d->tf_xn, D, (unsigned short*)nullptr, 0, M);
-        RGRG_LAUNCH_CHECK();
-    }
-    // ---------------- lm_head + loss + d(logits) + d(ln_f output), chunk by chunk (the logits never exist as a whole)
-    hipLaunchKernelGGL(ce_valid_kernel, dim3((M + 255) / 256), dim3(256), 0, st, attention_mask, T, M, d->tf_row_loss, d->tf_row_valid);
-    RGRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf_row_loss, d->tf_row_valid, M, (float*)nullptr, d->tr_count);
-    RGRG_LAUNCH_CHECK();
-    for (int r0 = 0; r0 < M; r0 += TF_LOGIT_ROWS) {
-        const int rows = (M - r0 < TF_LOGIT_ROWS) ? M - r0 : TF_LOGIT_ROWS;
-        if ((rc = tr_lin(d, d->lm_head, false, d->tf_xn + (size_t)r0 * D, nullptr, d->tr_logits, rows, VP))) return rc;
-        hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, d->tr_logits, (size_t)VP, V, r0, ids, attention_mask, T,
-                           d->tf_row_loss, d->tf_row_valid, d->tr_row_lse, d->id_error);
-        RGRG_LAUNCH_CHECK();
-        if ((rc = launch_ce_backward(d->tr_logits, (size_t)VP, V, r0, rows, ids, d->tf_row_valid, d->tr_row_lse, d->tr_count,
-                                     loss_scale, d->id_error, st)))
-            return rc;
-        if ((rc = tr_lin(d, d->lm_head, true, d->tr_logits, nullptr, d->tr_dxn + (size_t)r0 * D, rows, D))) return rc;
-    }
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf_row_loss, d->tf_row_valid, M, loss_out, (int*)nullptr,
-                       d->id_error);
-    RGRG_LAUNCH_CHECK();
-    if ((rc = id_error_end(d))) return rc;
-    // ---------------- backward through ln_f and the 24 frozen blocks (activation gradients only)
-    if ((rc = launch_ln_backward(d->tr_dxn, xs(2 * L), d->lnf_g, d->tr_dx, M, D, 0, st))) return rc;
-    for (int l = L - 1; l >= 0; --l) {
-        const LayerW& w = d->layers[l];
-        float* qkv = d->tr_qkv + (size_t)l * M * 3 * D;
-        float* ffpre = d->tr_ffpre + (size_t)l * M * 4 * D;
-        // x_out = x_mid + dropout(mlp_proj(gelu(c_fc(ln_2(x_mid)))))
-        const float* dbr = d->tr_dx;  // gradient entering the branch = dx * mask (same mask as the forward pass)
-        if (dropout_p > 0.f) {
-            if ((rc = launch_dropout_add(d->tr_dx, nullptr, d->tf_att, MD, DropoutParams{dropout_seed, (unsigned)(l * 4 + 3), dropout_p}, st)))
-                return rc;
-            dbr = d->tf_att;
-        }
-        if ((rc = tr_lin(d, w.mlp_proj, true, dbr, nullptr, d->tr_dbig, M, 4 * D))) return rc;
-        if ((rc = launch_gelu_backward(d->tr_dbig, ffpre, (size_t)M * 4 * D, st))) return rc;
-        if ((rc = tr_lin(d, w.c_fc, true, d->tr_dbig, nullptr, d->tr_dxn, M, D))) return rc;
-        if ((rc = launch_ln_backward(d->tr_dxn, xs(2 * l + 1), w.ln2_g, d->tr_dx, M, D, 1, st))) return rc;
-        // x_mid = x_in + dropout(attn_proj(attention(c_attn(ln_1(x_in)), uk(img), uv(img))))
-        dbr = d->tr_dx;
-        if (dropout_p > 0.f) {
-            if ((rc = launch_dropout_add(d->tr_dx, nullptr, d->tr_dxn, MD, DropoutParams{dropout_seed, (unsigned)(l * 4 + 2), dropout_p}, st)))
-                return rc;
-            dbr = d->tr_dxn;
-        }
-        if ((rc = tr_lin(d, w.attn_proj, true, dbr, nullptr, d->tf_att, M, D))) return rc;
-        if ((rc = launch_attn_backward(qkv, d->ukv_out, LD, l * 2 * D, attention_mask, d->tf_att, d->tr_att + (size_t)l * MD,
-                                       d->tr_lse + (size_t)l * M * d->H, d->tr_delta, d->tr_dbig, d->tr_dukv, S, d->H, T,
-                                       DropoutParams{dropout_seed, (unsigned)(l * 4 + 1), dropout_p}, st)))
-            return rc;
-        if ((rc = tr_lin(d, w.c_attn, true, d->tr_dbig, nullptr, d->tr_dxn, M, D))) return rc;
-        if ((rc = launch_ln_backward(d->tr_dxn, xs(2 * l), w.ln1_g, d->tr_dx, M, D, 1, st))) return rc;
-    }
-    }   // fp32-activation flow
-    // ---------------- uk / uv of every layer (one stacked Linear) and feature_space_transformation_nn
-    if ((rc = launch_colsum(d->tr_dukv, grad_ukv_b, S, LD, st))) return rc;
-    if ((rc = tr_gemm(d, d->tr_dukv, d->ukv.wT, nullptr, nullptr, d->tr_dimg, S, D, pad256(LD), D))) return rc;
-    if ((rc = launch_transpose_pad(d->tr_dukv, d->tr_t1, S, LD, Sp, st))) return rc;
-    if ((rc = launch_transpose_pad(d->img, d->tr_t2, S, D, Sp, st))) return rc;
-    if ((rc = tr_gemm(d, d->tr_t1, d->tr_t2, nullptr, nullptr, grad_ukv_w, LD, D, Sp, D))) return rc;
-    if ((rc = launch_colsum(d->tr_dimg, grad_fst2_b, S, D, st))) return rc;
-    if ((rc = launch_transpose_pad(d->tr_dimg, d->tr_t1, S, D, Sp, st))) return rc;
-    if ((rc = launch_transpose_pad(d->h1, d->tr_t2, S, D, Sp, st))) return rc;
-    if ((rc = tr_gemm(d, d->tr_t1, d->tr_t2, nullptr, nullptr, grad_fst2_w, D, D, Sp, D))) return rc;
-    if ((rc = tr_gemm(d, d->tr_dimg, d->fst2.wT, nullptr, nullptr, d->tr_dh1, S, D, pad256(D), D))) return rc;
-    if ((rc = launch_relu_backward(d->tr_dh1, d->h1, (size_t)S * D, st))) return rc;
-    if ((rc = launch_colsum(d->tr_dh1, grad_fst0_b, S, D, st))) return rc;
-    if ((rc = launch_transpose_pad(d->tr_dh1, d->tr_t1, S, D, Sp, st))) return rc;
-    if ((rc = launch_transpose_pad(d->feats, d->tr_t2, S, D, Sp, st))) return rc;
-    if ((rc = tr_gemm(d, d->tr_t1, d->tr_t2, nullptr, nullptr, grad_fst0_w, D, D, Sp, D))) return rc;
-    RGRG_HIP(hipEventRecord(d->ev_in, st));
-    RGRG_HIP(hipStreamWaitEvent(caller, d->ev_in, 0));
-    return RGRG_OK;
-}
-
-// Roofline support for BASELINE configs[4] (bench.py): the frozen-weight GEMMs of ONE training step of the 16-bit flow - per
-// layer c_attn, attn_proj, c_fc, mlp_proj forward and their four activation-gradient GEMMs, lm_head forward and dgrad per
-// chunk - launched back to back on the decoder's stream with the operands and epilogues of tr_body16, timed between two HIP
-// events (one untimed pass in front).  The work space of the last rgrg_decoder_lm_loss_grad call at this shape is reused (its
-// contents are overwritten with garbage: timing only).  flops = 2 M N K of those launches.
-extern "C" int rgrg_decoder_time_train_gemms(rgrg_decoder* d, int S, int T, int iters, float* ms_per_step, double* flops_per_step,
-                                             int* launches_per_step) {
-    RGRG_CHECK_ARG(d && S > 0 && T >= 2 && iters > 0 && ms_per_step && flops_per_step && launches_per_step);
-    const int D = d->D, M = S * T, L = d->n_layer, VP = pad256(d->V);
-    if (!d->tr_h16 || (size_t)M > d->tr_rows || !d->bf16_gemms) {
-        set_error("time_train_gemms: run a 16-bit training pass of this shape first (16-bit work space %d, rows %zu of %d, mode %d)",
-                  (int)d->tr_h16, d->tr_rows, M, d->bf16_gemms);
-        return RGRG_EINVAL;
-    }
-    const bool a16 = d->tr_a16;
-    const size_t MD = (size_t)M * D;
-    hipEvent_t e0, e1;
-    RGRG_HIP(hipEventCreate(&e0));
-    RGRG_HIP(hipEventCreate(&e1));
-    int rc = RGRG_OK, launches = 0;
-    double flops = 0.0;
-    auto cnt = [&](const Lin& l) { flops += 2.0 * M * (double)l.N * l.K; ++launches; };
-    for (int it = -1; it < iters && !rc; ++it) {
-        if (it == 0) RGRG_HIP(hipEventRecord(e0, d->stream));
-        const bool c = it == -1;
-        for (int l = 0; l < L && !rc; ++l) {
-            const LayerW& w = d->layers[l];
-            unsigned short* att16 = a16 ? d->tr_att16 + (size_t)l * MD : d->tr_att16;
-            GemmLnFold pre{}, gb{};
-            pre.Ypre16 = d->tr_ffpre16 + (size_t)l * M * 4 * D;
-            gb.G16 = d->tr_ffpre16 + (size_t)l * M * 4 * D;
-            if (a16) rc = tr_lin16(d, w.c_attn, false, d->tr_xn16, nullptr, nullptr, d->tr_qkv16 + (size_t)l * M * 3 * D, M, 3 * D);
-            else rc = tr_lin16(d, w.c_attn, false, d->tr_xn16, nullptr, d->tr_qkv + (size_t)l * M * 3 * D, nullptr, M, 3 * D);
-            if (rc || (rc = tr_lin16(d, w.attn_proj, false, att16, nullptr, nullptr, d->tr_dx16, M, D))) break;
-            if ((rc = tr_lin16(d, w.c_fc, false, d->tr_xn16, nullptr, nullptr, d->tr_ff16, M, 4 * D, RGRG_ACT_GELU_NEW, &pre))) break;
-            if ((rc = tr_lin16(d, w.mlp_proj, false, d->tr_ff16, nullptr, nullptr, d->tr_dx16, M, D))) break;
-            if ((rc = tr_lin16(d, w.mlp_proj, true, d->tr_dx16, nullptr, nullptr, d->tr_dff16, M, 4 * D, RGRG_ACT_NONE, &gb))) break;
-            if ((rc = tr_lin16(d, w.c_fc, true, d->tr_dff16, nullptr, nullptr, d->tr_xn16, M, D))) break;
-            if (a16) rc = tr_lin16(d, w.attn_proj, true, d->tr_dx16, nullptr, nullptr, d->tr_datt16, M, D);
-            else rc = tr_lin16(d, w.attn_proj, true, d->tr_dx16, nullptr, d->tr_dxn, nullptr, M, D);
-            if (rc || (rc = tr_lin16(d, w.c_attn, true, d->tr_dqkv16, nullptr, nullptr, d->tr_xn16, M, D))) break;
-            if (c) { cnt(w.c_attn); cnt(w.attn_proj); cnt(w.c_fc); cnt(w.mlp_proj); cnt(w.mlp_proj); cnt(w.c_fc); cnt(w.attn_proj); cnt(w.c_attn); }
-        }
-        const int chunk = (int)d->tr_chunk;
-        for (int r0 = 0; r0 < M && !rc; r0 += chunk) {
-            const int rows = (M - r0 < chunk) ? M - r0 : chunk;
-            if ((rc = tr_lin16(d, d->lm_head, false, d->tr_xn16 + (size_t)r0 * D, nullptr, d->tr_logits, nullptr, rows, VP))) break;
-            if ((rc = tr_lin16(d, d->lm_head, true, d->tr_dl16, nullptr, d->tr_dxn + (size_t)r0 * D, nullptr, rows, D))) break;
-            if (c) { flops += 2.0 * 2.0 * rows * (double)d->lm_head.N * d->lm_head.K; launches += 2; }
-        }
-    }
-    float ms = 0.f;
-    if (!rc) {
-        RGRG_HIP(hipEventRecord(e1, d->stream));
-        RGRG_HIP(hipEventSynchronize(e1));
-        RGRG_HIP(hipEventElapsedTime(&ms, e0, e1));
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    *ms_per_step = ms / iters;
-    *flops_per_step = flops;
-    *launches_per_step = launches;
-    return RGRG_OK;
-}
 
 // LanguageModel.forward(input_ids, ..., past_key_values, use_cache=True) (language_model.py:258-366, :396-399): the
 // incremental form the reference's own generate loop is built on, over THIS decoder's K/V cache.  past_len == 0: the image

@@ -1,0 +1,479 @@
+// Beam search of the RGRG decoder (LanguageModel.generate with num_beams > 1 -> beam_search of ttanida/rgrg):
+// the ranking / merge / ancestor-table kernels and the host-side restatement of transformers' BeamSearchScorer.
+// A beam step is the decode step of decoder.hip (enqueue_step) with the beam tokens and the ancestor table as inputs.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "decoder_internal.h"
+
+namespace rgrg {
+
+// ------------------------------------------------------------------ beam search kernels
+// Per beam row: max, log-sum-exp and the top-K (value desc, token asc on ties) logits.
+// log_softmax is monotonic within a row, so the row's best continuations are its top logits.
+// Round 6: 1024 threads per row and candidate lists of LIST = 8 / 16 / 32 >= K entries (the scripts' 4 beams need 8): the round-5
+// kernel - 256 threads, lists of 32 - took 204 us per step at 116 beam rows (11 % of the step): a wave runs the whole 31-step
+// insertion chain whenever ONE of its lanes inserts, i.e. for nearly every one of its 196 elements per lane.
+constexpr int BEAM_ROW_THREADS = 1024;
+// max and sum of exp(x - max) of a row, the same value in every thread (fixed order: strided per thread, butterflies per wave, the 16
+// wave sums in wave order)
+template <int THREADS>
+__device__ __forceinline__ void beam_row_max_sumexp(const float* __restrict__ x, int V, float* sh, float& m_out, float& ssum_out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += THREADS) m = fmaxf(m, x[i]);
+    m = wave_max(m);
+    if (lane == 0) sh[wave] = m;
+    __syncthreads();
+    m = sh[0];
+#pragma unroll
+    for (int w = 1; w < THREADS / 64; ++w) m = fmaxf(m, sh[w]);
+    __syncthreads();
+    float ssum = 0.f;
+    for (int i = tid; i < V; i += THREADS) ssum += expf(x[i] - m);
+    ssum = wave_sum(ssum);
+    if (lane == 0) sh[wave] = ssum;
+    __syncthreads();
+    ssum = sh[0];
+#pragma unroll
+    for (int w = 1; w < THREADS / 64; ++w) ssum += sh[w];
+    __syncthreads();
+    m_out = m; ssum_out = ssum;
+}
+template <int LIST, int THREADS>   // (8, 1024), (16, 1024), (32, 512): 1024 threads x 32 entries spill
+__global__ __launch_bounds__(THREADS) void beam_row_topk_kernel(const float* __restrict__ logits, int ld, int V, int K,
+                                                                         float* __restrict__ row_max, float* __restrict__ row_logsum,
+                                                                         float* __restrict__ top_val, int* __restrict__ top_tok) {
+    constexpr int NW = THREADS / 64;
+    __shared__ float sh[NW];
+    __shared__ float wv[NW];
+    __shared__ int wi[NW];
+    __shared__ int winner;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* x = logits + (size_t)row * ld;
+    // ONE pass over the row: the thread's running maximum with the sum of exp(x - maximum) rescaled whenever the maximum moves, and its
+    // local top-LIST, sorted (value desc, index asc).  (Three passes - maximum, sum, candidates - took 50 us per step at the scripts'
+    // 116 beam rows, this form 44: what is left is the insertion chain, which a wave runs whenever one of its lanes inserts, and the
+    // exponentials, on 116 of the 256 CUs - profiles/r06_kernel_trace_summary_beam4_fp16.md.)
+    float tm = -INFINITY, ts = 0.f;
+    float lv[LIST];
+    int li[LIST];
+#pragma unroll
+    for (int k = 0; k < LIST; ++k) { lv[k] = -INFINITY; li[k] = 0x7fffffff; }
+    // (8 loads in flight per thread)
+    for (int i0 = tid; i0 < V; i0 += 8 * THREADS) {
+        float vb[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vb[u] = x[min(i0 + u * THREADS, V - 1)];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * THREADS;
+            if (i >= V) break;
+            const float v = vb[u];
+            if (v > tm) { ts = ts * expf(tm - v) + 1.0f; tm = v; }   // (first element: 0 * exp(-inf) + 1)
+            else ts += expf(v - tm);
+            if (v > lv[LIST - 1]) {  // strided indices ascend, so an equal value never displaces an earlier one
+                lv[LIST - 1] = v; li[LIST - 1] = i;
+#pragma unroll
+                for (int k = LIST - 1; k > 0; --k) {
+                    if (lv[k] > lv[k - 1]) {
+                        const float tv = lv[k]; lv[k] = lv[k - 1]; lv[k - 1] = tv;
+                        const int ti = li[k]; li[k] = li[k - 1]; li[k - 1] = ti;
+                    }
+                }
+            }
+        }
+    }
+    // row maximum, then every thread's sum brought to it; fixed order (butterflies per wave, the wave sums in wave order)
+    float m = wave_max(tm);
+    if (lane == 0) sh[wave] = m;
+    __syncthreads();
+    m = sh[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) m = fmaxf(m, sh[w]);
+    __syncthreads();
+    float ssum = wave_sum(tm == -INFINITY ? 0.f : ts * expf(tm - m));
+    if (lane == 0) sh[wave] = ssum;
+    __syncthreads();
+    ssum = sh[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) ssum += sh[w];
+    // K rounds: block-wide arg-max over the threads' current heads; the winner pops its head
+    for (int round = 0; round < K; ++round) {
+        float bv = lv[0];
+        int bi = li[0];
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < NW; ++w)
+                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
+            top_val[(size_t)row * BEAM_K + round] = bv;
+            top_tok[(size_t)row * BEAM_K + round] = bi;
+            winner = bi;
+        }
+        __syncthreads();
+        if (li[0] == winner) {
+#pragma unroll
+            for (int k = 0; k < LIST - 1; ++k) { lv[k] = lv[k + 1]; li[k] = li[k + 1]; }
+            lv[LIST - 1] = -INFINITY; li[LIST - 1] = 0x7fffffff;
+        }
+    }
+    if (tid == 0) { row_max[row] = m; row_logsum[row] = logf(ssum); }
+}
+
+// Per batch item: log_softmax + beam score for the nb*K row candidates, then the top K = 2*nb
+// of the item (score desc; ties: lower flat index beam*V + token first) - language_model.py:545-561.
+constexpr int BEAM_MERGE_THREADS = BEAM_K * BEAM_K / 2;  // one thread per candidate: nb * 2 nb <= 512
+__global__ __launch_bounds__(BEAM_MERGE_THREADS) void beam_merge_kernel(const float* __restrict__ row_max, const float* __restrict__ row_logsum,
+                                                         const float* __restrict__ top_val, const int* __restrict__ top_tok,
+                                                         const float* __restrict__ beam_scores, int nb, int K, int V,
+                                                         float* __restrict__ out_score, int* __restrict__ out_tok,
+                                                         int* __restrict__ out_beam) {
+    // n = nb * 2 nb candidates (<= 512 for nb <= 16): one thread each, ranked against all others through LDS
+    __shared__ float ssc[BEAM_MERGE_THREADS];
+    __shared__ long long sflat[BEAM_MERGE_THREADS];
+    const int item = blockIdx.x, tid = threadIdx.x;
+    const int n = nb * K;
+    float sc = -INFINITY;
+    long long flat = 0x7fffffffffffLL;
+    int tok = 0, b = 0;
+    if (tid < n) {
+        b = tid / K;
+        const int row = item * nb + b;
+        const float v = top_val[(size_t)row * BEAM_K + (tid - b * K)];
+        tok = top_tok[(size_t)row * BEAM_K + (tid - b * K)];
+        sc = ((v - row_max[row]) - row_logsum[row]) + beam_scores[row];
+        flat = (long long)b * V + tok;
+    }
+    ssc[tid] = sc;
+    sflat[tid] = flat;
+    __syncthreads();
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+        const float oj = ssc[j];
+        const long long fj = sflat[j];
+        if (oj > sc || (oj == sc && fj < flat)) ++rank;
+    }
+    if (tid < n && rank < K) {
+        out_score[item * K + rank] = sc;
+        out_tok[item * K + rank] = tok;
+        out_beam[item * K + rank] = b;
+    }
+}
+
+// ---- more than 16 beams (round 6: the reference's loop has no bound, language_model.py:450-475).  The per-thread sorted lists of the
+// kernels above hold 32 candidates in registers; wider beams take K = 2 num_beams rounds of a block-wide arg-max over the elements
+// that come AFTER the previous winner in the same total order (value desc, index asc) - K scans of the row from L2 instead of one,
+// the same winners.  top_val / top_tok rows are K wide here (ldk).
+template <int NW>
+__device__ __forceinline__ void beam_block_argmax(float& bv, long long& bi, float* wv, long long* wi, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const long long oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+    __syncthreads();
+    bv = wv[0]; bi = wi[0];
+    for (int w = 1; w < NW; ++w)
+        if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
+    __syncthreads();
+}
+__global__ __launch_bounds__(BEAM_ROW_THREADS) void beam_row_topk_wide_kernel(const float* __restrict__ logits, int ld, int V, int K,
+                                                                              float* __restrict__ row_max, float* __restrict__ row_logsum,
+                                                                              float* __restrict__ top_val, int* __restrict__ top_tok) {
+    constexpr int NW = BEAM_ROW_THREADS / 64;
+    __shared__ float sh[NW];
+    __shared__ float wv[NW];
+    __shared__ long long wi[NW];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* x = logits + (size_t)row * ld;
+    float m, ssum;
+    beam_row_max_sumexp<BEAM_ROW_THREADS>(x, V, sh, m, ssum);
+    float pv = INFINITY;
+    long long pi = -1;
+    for (int round = 0; round < K; ++round) {
+        float bv = -INFINITY;
+        long long bi = 0x7fffffffLL;
+        for (int i = tid; i < V; i += BEAM_ROW_THREADS) {
+            const float v = x[i];
+            if ((v < pv || (v == pv && i > pi)) && v > bv) { bv = v; bi = i; }   // strided indices ascend: the first of equal values stays
+        }
+        beam_block_argmax<NW>(bv, bi, wv, wi, tid);
+        if (tid == 0) {
+            top_val[(size_t)row * K + round] = bv;
+            top_tok[(size_t)row * K + round] = (int)bi;
+        }
+        pv = bv; pi = bi;
+    }
+    if (tid == 0) { row_max[row] = m; row_logsum[row] = logf(ssum); }
+}
+// Per batch item: the nb * K candidate scores (same expression as beam_merge_kernel) into `score` [item][nb * K], then the item's
+// top K in the order (score desc, flat index beam * V + token asc), again by K rounds over what follows the previous winner.
+__global__ __launch_bounds__(256) void beam_merge_wide_kernel(const float* __restrict__ row_max, const float* __restrict__ row_logsum,
+                                                              const float* __restrict__ top_val, const int* __restrict__ top_tok,
+                                                              const float* __restrict__ beam_scores, int nb, int K, int V,
+                                                              float* __restrict__ score, float* __restrict__ out_score,
+                                                              int* __restrict__ out_tok, int* __restrict__ out_beam) {
+    __shared__ float wv[4];
+    __shared__ long long wi[4];
+    const int item = blockIdx.x, tid = threadIdx.x;
+    const int n = nb * K;
+    float* sc = score + (size_t)item * n;
+    for (int c = tid; c < n; c += 256) {
+        const int b = c / K, row = item * nb + b;
+        sc[c] = ((top_val[(size_t)row * K + (c - b * K)] - row_max[row]) - row_logsum[row]) + beam_scores[row];
+    }
+    __syncthreads();
+    float pv = INFINITY;
+    long long pf = -1;
+    for (int round = 0; round < K; ++round) {
+        float bv = -INFINITY;
+        long long bf = 0x7fffffffffffLL;
+        for (int c = tid; c < n; c += 256) {
+            const int b = c / K;
+            const float v = sc[c];
+            const long long flat = (long long)b * V + top_tok[(size_t)(item * nb + b) * K + (c - b * K)];
+            if ((v < pv || (v == pv && flat > pf)) && (v > bv || (v == bv && flat < bf))) { bv = v; bf = flat; }
+        }
+        beam_block_argmax<4>(bv, bf, wv, wi, tid);
+        if (tid == 0) {
+            out_score[item * K + round] = bv;
+            out_tok[item * K + round] = (int)(bf % V);
+            out_beam[item * K + round] = (int)(bf / V);
+        }
+        pv = bv; pf = bf;
+    }
+}
+
+// New ancestor table after the host picked the surviving beams: row r continues beam parent[r];
+// slots 0..t come from the parent's table, slot t+1 (written this step) lives in the parent's row.
+__global__ __launch_bounds__(256) void beam_advance_kernel(const int* __restrict__ src_old, int* __restrict__ src_new,
+                                                           const int* __restrict__ parent, int* __restrict__ step, int T,
+                                                           int R) {
+    const int r = blockIdx.x, t = *step;
+    const int p = parent[r];
+    for (int j = threadIdx.x; j <= t; j += 256) src_new[(size_t)r * T + j] = src_old[(size_t)p * T + j];
+    if (threadIdx.x == 0) src_new[(size_t)r * T + t + 1] = p;
+    __syncthreads();
+    (void)R;
+}
+__global__ void beam_step_inc_kernel(int* __restrict__ step) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1;
+}
+__global__ __launch_bounds__(256) void beam_init_kernel(int* __restrict__ src, int T, int nb, int R, int* __restrict__ step) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < R) src[(size_t)r * T] = (r / nb) * nb;  // slot 0 (image key/value) is stored once per item, in its first beam row
+    if (r == 0) *step = 0;
+}
+
+}  // namespace rgrg
+
+using namespace rgrg;
+
+// ------------------------------------------------------------------ beam search (host side)
+// BeamHypotheses / BeamSearchScorer of transformers 4.19.2 (used by language_model.py:457-464, :570-578,
+// :597-605), restated on the host: hypothesis scores, worst_score and the is_done test are double arithmetic
+// (HF does them on Python floats obtained through .item()), beam scores stay float32.
+namespace rgrg {
+struct Hyp { double score; std::vector<long long> toks; };
+struct BeamHyps {
+    std::vector<Hyp> beams;
+    double worst = 1e9;
+    void add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp) {
+        const double score = sum_logprobs / std::pow((double)toks.size(), lp);
+        if ((int)beams.size() < nb || score > worst) {
+            beams.push_back({score, toks});
+            if ((int)beams.size() > nb) {
+                int i0 = 0;  // sorted([(score, idx)]): smallest (score, idx) is dropped, worst = the next one
+                for (int i = 1; i < (int)beams.size(); ++i)
+                    if (beams[i].score < beams[i0].score) i0 = i;
+                beams.erase(beams.begin() + i0);
+                double w = beams[0].score;
+                for (auto& h : beams) w = h.score < w ? h.score : w;
+                worst = w;
+            } else {
+                worst = score < worst ? score : worst;
+            }
+        }
+    }
+    bool is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const {
+        if ((int)beams.size() < nb) return false;
+        if (early) return true;
+        return worst >= best_sum_logprobs / std::pow((double)cur_len, lp);
+    }
+};
+}  // namespace rgrg
+
+extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length,
+                                        int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
+                                        int out_ld, int* out_len, void* stream) {
+    RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && num_beams > 1 && num_beams <= (1 << 14));
+    RGRG_CHECK_ARG(num_return_sequences >= 1 && num_return_sequences <= num_beams);
+    const int nb = num_beams, K = 2 * nb, R = S * nb;
+    RGRG_CHECK_ARG(R <= d->max_seqs && max_length >= 2 && max_length <= d->max_len && out_ld >= max_length);
+    hipStream_t st = d->stream;
+    const bool wide = K > BEAM_K;   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
+    if (wide && d->wide_cap < (size_t)R * K) {
+        RGRG_HIP(hipStreamSynchronize(st));
+        for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);   // (captured beam steps bake the buffers in)
+        d->graphs.clear();
+        for (void** q : {(void**)&d->wide_val, (void**)&d->wide_tok, (void**)&d->wide_score}) {   // grown: the smaller buffers go
+            if (!*q) continue;
+            auto it = std::find(d->allocs.begin(), d->allocs.end(), *q);
+            if (it != d->allocs.end()) d->allocs.erase(it);
+            (void)hipFree(*q);
+            *q = nullptr;
+        }
+        d->wide_cap = 0;
+        int r;
+        if ((r = dmalloc(d, (void**)&d->wide_val, (size_t)R * K * 4, true)) || (r = dmalloc(d, (void**)&d->wide_tok, (size_t)R * K * 4, true)) ||
+            (r = dmalloc(d, (void**)&d->wide_score, (size_t)R * K * 4, true)))
+            return r;
+        d->wide_cap = (size_t)R * K;
+    }
+    RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
+    RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
+    // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
+    int rc = enqueue_prefill(d, feats, S, nb);
+    if (rc) return rc;
+    hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d->src_a, d->T, nb, R, d->step);
+    RGRG_LAUNCH_CHECK();
+
+    std::vector<std::vector<long long>> ids(R, std::vector<long long>(1, BOS_ID));
+    std::vector<float> beam_scores(R, 0.f), h_score((size_t)S * K);
+    std::vector<int> beam_tok(R, BOS_ID), parent(R, 0), h_tok((size_t)S * K), h_beam((size_t)S * K);
+    for (int r = 0; r < R; ++r) beam_scores[r] = (r % nb == 0) ? 0.f : -1e9f;
+    std::vector<BeamHyps> hyps(S);
+    std::vector<char> done(S, 0);
+    const double lp = (double)length_penalty;
+    int* src_cur = d->src_a;
+    int* src_nxt = d->src_b;
+    int cur_len = 1;
+    std::vector<float> nscore(R);
+    std::vector<int> ntok(R), nidx(R);
+    d->logits_stale_rows = 0;   // beam steps write d->logits
+    d->logits_valid = false;
+    while (true) {
+        RGRG_HIP(hipMemcpyAsync(d->beam_tok, beam_tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+        RGRG_HIP(hipMemcpyAsync(d->beam_scores, beam_scores.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
+        {
+            // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed
+            const int parity = (src_cur == d->src_a) ? 1 : 2;
+            hipGraphExec_t exec = nullptr;
+            for (auto& g : d->graphs)
+                if (g.S == R && g.key2 == parity && g.key3 == nb) exec = g.exec;
+            if (!exec) {
+                hipGraph_t graph = nullptr;
+                RGRG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                rc = enqueue_step(d, R, false, d->beam_tok, src_cur, true);
+                if (!rc && !wide) {
+#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(R), dim3(THREADS_), 0, st, d->logits, d->ld_logits, d->V, K, \
+                                                      d->row_max, d->row_logsum, d->top_val, d->top_tok)
+                    if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
+#undef BEAM_TOPK
+                    hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
+                                       d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
+                } else if (!rc) {
+                    hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
+                                       d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
+                    hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, d->row_max, d->row_logsum, d->wide_val, d->wide_tok,
+                                       d->beam_scores, nb, K, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam);
+                }
+                hipError_t e = hipStreamEndCapture(st, &graph);
+                if (rc) return rc;
+                if (e != hipSuccess) { set_error("beam: hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+                RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+                (void)hipGraphDestroy(graph);
+                d->graphs.push_back({R, exec, parity, nb});
+            }
+            RGRG_HIP(hipGraphLaunch(exec, st));
+        }
+        RGRG_HIP(hipMemcpyAsync(h_score.data(), d->cand_score, (size_t)S * K * sizeof(float), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipMemcpyAsync(h_tok.data(), d->cand_tok, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipMemcpyAsync(h_beam.data(), d->cand_beam, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipStreamSynchronize(st));
+        // BeamSearchScorer.process
+        for (int b = 0; b < S; ++b) {
+            if (done[b]) {
+                for (int j = 0; j < nb; ++j) { nscore[b * nb + j] = 0.f; ntok[b * nb + j] = PAD_ID; nidx[b * nb + j] = 0; }
+                continue;
+            }
+            int beam_idx = 0;
+            for (int rank = 0; rank < K; ++rank) {
+                const int tok = h_tok[(size_t)b * K + rank];
+                const float sc = h_score[(size_t)b * K + rank];
+                const int row = b * nb + h_beam[(size_t)b * K + rank];
+                if (tok == EOS_ID) {
+                    if (rank >= nb) continue;
+                    hyps[b].add(ids[row], (double)sc, nb, lp);
+                } else {
+                    nscore[b * nb + beam_idx] = sc; ntok[b * nb + beam_idx] = tok; nidx[b * nb + beam_idx] = row;
+                    ++beam_idx;
+                }
+                if (beam_idx == nb) break;
+            }
+            if (beam_idx < nb) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
+            done[b] = done[b] || hyps[b].is_done((double)h_score[(size_t)b * K], cur_len, early_stopping != 0, nb, lp);
+        }
+        // input_ids = cat(input_ids[beam_idx], tokens); cache "re-order" = new ancestor table
+        std::vector<std::vector<long long>> nids(R);
+        for (int r = 0; r < R; ++r) { nids[r] = ids[nidx[r]]; nids[r].push_back(ntok[r]); }
+        ids.swap(nids);
+        beam_scores = nscore;
+        for (int r = 0; r < R; ++r) { beam_tok[r] = ntok[r]; parent[r] = nidx[r]; }
+        ++cur_len;
+        bool all_done = true;
+        for (int b = 0; b < S; ++b) all_done = all_done && done[b];
+        if (all_done || cur_len >= max_length) break;
+        RGRG_HIP(hipMemcpyAsync(d->beam_parent, parent.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_cur, src_nxt, d->beam_parent, d->step, d->T, R);
+        RGRG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(beam_step_inc_kernel, dim3(1), dim3(64), 0, st, d->step);
+        RGRG_LAUNCH_CHECK();
+        int* tmp = src_cur; src_cur = src_nxt; src_nxt = tmp;
+    }
+    // BeamSearchScorer.finalize (num_beam_hyps_to_keep = 1)
+    for (int b = 0; b < S; ++b) {
+        if (done[b]) continue;
+        for (int j = 0; j < nb; ++j) hyps[b].add(ids[b * nb + j], (double)beam_scores[b * nb + j], nb, lp);
+    }
+    // num_beam_hyps_to_keep best hypotheses per item: sorted(beams, key=score) is stable and pop() takes the last, i.e.
+    // descending score and, among equal scores, the LATER-added hypothesis first
+    const int keep = num_return_sequences, NR = S * keep;
+    std::vector<const std::vector<long long>*> best(NR);
+    int max_sent = 0, min_sent = 1 << 30;
+    for (int b = 0; b < S; ++b) {
+        const int nh = (int)hyps[b].beams.size();
+        if (nh < keep) { set_error("beam search: item %d has %d finished hypotheses, %d requested", b, nh, keep); return RGRG_ESTATE; }
+        std::vector<int> order(nh);
+        for (int j = 0; j < nh; ++j) order[j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hyps[b].beams[x].score < hyps[b].beams[y].score; });
+        for (int j = 0; j < keep; ++j) {
+            best[b * keep + j] = &hyps[b].beams[order[nh - 1 - j]].toks;
+            const int len = (int)best[b * keep + j]->size();
+            max_sent = len > max_sent ? len : max_sent;
+            min_sent = len < min_sent ? len : min_sent;
+        }
+    }
+    const int L = (max_sent + 1 < max_length) ? max_sent + 1 : max_length;
+    std::vector<long long> dec((size_t)NR * L, PAD_ID);
+    for (int b = 0; b < NR; ++b) {
+        const int len = (int)best[b]->size();
+        for (int j = 0; j < len && j < L; ++j) dec[(size_t)b * L + j] = (*best[b])[j];
+        if (len < max_length) dec[(size_t)b * L + len] = EOS_ID;
+    }
+    RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), dec.data(), (size_t)L * sizeof(long long),
+                              (size_t)L * sizeof(long long), NR, hipMemcpyHostToDevice, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    *out_len = L;
+    d->logits_valid = true;
+    return RGRG_OK;
+}

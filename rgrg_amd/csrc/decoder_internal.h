@@ -1,0 +1,191 @@
+// What the decoder's translation units (decoder.hip: the decode step and the object; decoder_beam.hip: beam search;
+// decoder_lm.hip: the teacher-forced and training passes) share: the rgrg_decoder object, its constants and the few host
+// helpers that are called across those files.  Everything else is static in the file that uses it.
+#pragma once
+#include <vector>
+
+#include "internal.h"
+
+namespace rgrg {
+
+constexpr int MAX_CHAINS = 4;   // row ranges of the many-sequence decode step (enqueue_step)
+constexpr int PAD_ROWS = 32;
+constexpr int SKINNY_MAX_ROWS = 128;  // 4 row tiles of 32 sequences per weight-streaming launch (RGRG_SKINNY_MAX_ROWS)
+constexpr int BOS_ID = 50256, EOS_ID = 50256, PAD_ID = 50256;
+constexpr int BEAM_K = 32;  // max 2*num_beams candidates per row (num_beams <= 16)
+
+struct Lin {
+    const float* w = nullptr;  // [N,K]
+    const float* b = nullptr;  // [N]
+    float* packed = nullptr;   // skinny layout
+    void* wb = nullptr;        // bf16 copy of w (opt-in many-sequence path)
+    float* wT = nullptr;       // [K][Np] transposed copy, Np = N rounded up to 256 (backward pass: dX = dY W)
+    void* wTb = nullptr;       // 16-bit copy of wT (training under autocast)
+    int wb_f16 = 0, wTb_f16 = 0;   // the 16-bit type wb / wTb currently hold (0 bf16, 1 fp16)
+    // 16-bit many-sequence decode with the LayerNorm in front of this GEMM folded in (enqueue_step): wb_ln[n][k] =
+    // round16(gain[k] w[n][k]), cs16[n] = sum_k wb_ln[n][k] (of the ROUNDED values), c2_16[n] = b[n] + sum_k beta[k] w[n][k]
+    void* wb_ln = nullptr;
+    float *cs16 = nullptr, *c2_16 = nullptr;
+    int wb_ln_f16 = -1;
+    int N = 0, K = 0, NT = 0, KS = 1, ntile = 32;
+    // fused decode plan (skinny_direct.inc): `packed` holds 16-column fragments, pre-scaled by the LayerNorm weight of
+    // the LayerNorm this GEMM consumes when lnf is set; c1 / c2 are the folded vectors of that LayerNorm
+    bool direct = false, lnf = false;
+    float *c1 = nullptr, *c2 = nullptr;
+    // 16-bit-weight variant of the fused plan (33-128 rows under autocast, round 6): `packed` rounded to the autocast type, and
+    // the column sums of those ROUNDED values (lnf)
+    void* packed16 = nullptr;
+    float* c1_16 = nullptr;
+    int packed16_f16 = -1;
+};
+
+struct LayerW {
+    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    Lin c_attn, attn_proj, c_fc, mlp_proj;
+};
+
+struct GraphEntry {
+    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3)
+    hipGraphExec_t exec;
+    int key2 = 0, key3 = 0;
+};
+
+}  // namespace rgrg
+
+struct rgrg_decoder {
+    int n_layer, D, H, V, max_seqs, rows, T, max_len;
+    const float* wte;
+    const float *lnf_g, *lnf_b;
+    rgrg::Lin fst0, fst2, ukv, lm_head;
+    std::vector<rgrg::LayerW> layers;
+    // workspace
+    float *feats, *h1, *img, *ukv_out, *x, *x2, *xn, *qkv, *att, *ff, *logits, *part, *kv, *cand_val, *gemm_ws;
+    size_t gemm_ws_floats;
+    int* cand_idx;
+    size_t kv_layer_stride, kv_kv_stride;
+    int ld_logits, ld_ukv;
+    long long* ids;
+    int *next, *finished, *step, *done_len, *sync;
+    // beam search
+    int *src_a, *src_b, *beam_tok, *beam_parent, *cand_tok, *cand_beam, *top_tok;
+    float *beam_scores, *row_max, *row_logsum, *top_val, *cand_score;
+    float *wide_val = nullptr, *wide_score = nullptr;   // more than 16 beams: [rows][K] row candidates, [items][num_beams * K] scores
+    int* wide_tok = nullptr;
+    size_t wide_cap = 0;                                 // rows * K the wide buffers were sized for
+    int* h_done;  // pinned: [0] final read, [1..2] the two in-flight "all finished" polls of the greedy loop
+    hipEvent_t ev_poll[2] = {nullptr, nullptr};
+    // Token-id validation of the teacher-forced passes, without a host round trip.  id_error[0]: raised by the CURRENT
+    // pass (embedding / cross-entropy kernels) when an id is outside [0, vocab), cleared when a pass starts - it poisons
+    // THAT pass's loss and gradients (NaN).  id_error[1]: sticky "some pass failed and has not been reported yet",
+    // folded from [0] at the end of every pass and copied to the pinned mirror; the next call that finds the mirror set
+    // reports torch.nn.Embedding's IndexError and clears both.
+    int* id_error = nullptr;
+    int* h_id_error = nullptr;
+    hipStream_t stream;
+    hipEvent_t ev_in;
+    std::vector<rgrg::GraphEntry> graphs;
+    std::vector<void*> allocs;
+    size_t gemm_bytes_per_step = 0;
+    double gemm_flops_per_step = 0.0;
+    // teacher-forced pass workspace (grown on demand, rgrg_decoder_lm_forward; decoder_lm.hip tf_reserve)
+    struct TfWork {
+        float *x = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr, *logits = nullptr, *ws = nullptr,
+              *row_loss = nullptr;
+        int* row_valid = nullptr;
+        size_t rows = 0, ws_floats = 0;
+        const long long* pos = nullptr;   // position_ids of the NEXT teacher-forced pass (rgrg_decoder_set_lm_positions), [pos_rows] int64
+        int pos_rows = 1;
+        void free() {
+            float** fs[] = {&x, &xn, &qkv, &att, &ff, &logits, &ws, &row_loss};
+            for (float** f : fs) { if (*f) (void)hipFree(*f); *f = nullptr; }
+            if (row_valid) (void)hipFree(row_valid);
+            row_valid = nullptr;
+            rows = 0;
+            ws_floats = 0;
+        }
+    } tf;
+    // training pass (rgrg_decoder_lm_loss_grad; decoder_lm.hip tr_reserve): saved activations and gradient work space, grown on demand
+    struct TrWork {
+        float *xs = nullptr, *qkv = nullptr, *ffpre = nullptr, *ff = nullptr, *dx = nullptr, *dbig = nullptr, *dxn = nullptr,
+              *logits = nullptr, *dukv = nullptr, *t1 = nullptr, *t2 = nullptr, *dimg = nullptr, *dh1 = nullptr, *row_lse = nullptr,
+              *att = nullptr, *lse = nullptr, *delta = nullptr;
+        int* count = nullptr;
+        size_t rows = 0, seqs = 0;
+        // 16-bit activation flow of the training pass (autocast, > 128 token rows; round 5): every GEMM input is written as 16 bit
+        // by its producer - LayerNorm outputs, attention outputs, gelu outputs + the saved c_fc pre-activations of every layer,
+        // masked gradients, d(c_fc output), d(qkv), d(logits) of the chunk
+        unsigned short *xn16 = nullptr, *att16 = nullptr, *ff16 = nullptr, *ffpre16 = nullptr, *dx16 = nullptr, *dff16 = nullptr,
+                       *dqkv16 = nullptr, *dl16 = nullptr;
+        // ... and, for T + 1 <= 128 keys, the 16-bit attention kernels (attn_train16.hip): q / k / v and the attention output of
+        // every layer kept as 16 bit, d(attention output) and the image key / value of slot 0 as 16 bit
+        unsigned short *qkv16 = nullptr, *datt16 = nullptr, *ukv16 = nullptr;
+        bool a16 = false;
+        bool h16 = false;       // what the current training work space was reserved for
+        size_t chunk = 0;       // token rows per lm_head / cross-entropy chunk of that reservation
+        bool seen_a16 = false, seen_a32 = false, seen_h16 = false, seen_h32 = false, seen_h16_a32 = false;   // tr_reserve: modes seen
+        bool have_wT = false;
+        void* a16_scratch = nullptr;   // bf16 copy of an fp32 GEMM input (teacher-forced / training passes under autocast); outlives free()
+        size_t a16_bytes = 0;
+        void free() {   // the work space of tr_reserve (not the weight copies, not a16_scratch)
+            float** fs[] = {&xs, &qkv, &ffpre, &ff, &dx, &dbig, &dxn, &logits, &dukv, &t1, &t2, &dimg, &dh1, &row_lse, &att, &lse, &delta};
+            for (float** f : fs) { if (*f) (void)hipFree(*f); *f = nullptr; }
+            if (count) (void)hipFree(count);
+            count = nullptr;
+            unsigned short** hs[] = {&xn16, &att16, &ff16, &ffpre16, &dx16, &dff16, &dqkv16, &dl16, &qkv16, &datt16, &ukv16};
+            for (unsigned short** h : hs) { if (*h) (void)hipFree(*h); *h = nullptr; }
+            rows = seqs = 0;
+            chunk = 0;
+        }
+    } tr;
+    int bf16_gemms = 0;  // 1 (bf16) / 2 (fp16): 16-bit-weight MFMA GEMMs on the many-sequence path (not bit-exact; opt-in)
+    int f16() const { return bf16_gemms == 2 ? 1 : 0; }   // the 16-bit type of that mode
+    unsigned short *xn16 = nullptr, *att16 = nullptr, *ff16 = nullptr;  // bf16 activations of that path (GEMM inputs)
+    float* sk_ws = nullptr;     // split-K work space of the N = 1024 projections of the many-sequence decode step (gemm_bf16.hip)
+    unsigned* sk_cnt = nullptr;
+    int sk_attn = 0, sk_mlp = 0; // K slices of attn_proj / mlp_proj there (RGRG_SK_ATTN / RGRG_SK_MLP; 1 = off; -1 = automatic: 2 / 4 slices for a
+                                 // step of <= 256 rows - 32-64 output tiles for 256 CUs - and none above)
+    int step_rows = 0;           // token rows of the many-sequence step being enqueued (all row ranges together)
+    float* ln_stat = nullptr;   // [rows][16][2]: per-row (sum, sum of squares) slots (one per 64 columns) of the residual stream (folded LayerNorm)
+    bool ln_fold = true;        // 16-bit path: LayerNorms folded into the GEMMs around them; RGRG_LN_FOLD=0: ln_rows launches (A/B)
+    float* key_mask = nullptr;             // [rows][T] additive padding mask of the cache slots (forward(use_cache=True) with padding)
+    const float* key_mask_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached when a mask was given
+    // rgrg_decoder_trace_step: one hipEvent after every launch of an eagerly enqueued step, on the stream it was launched on
+    struct TraceMark { hipEvent_t ev; int r0; int tag; };
+    std::vector<TraceMark>* trace = nullptr;
+    bool w16_fused = true;      // under autocast 33-128 rows run the fused plan on 16-bit weights (skinny_direct.inc W16); RGRG_W16_FUSED=0: the
+                                // many-sequence 16-bit path from 33 rows on (A/B)
+    int kp_gemms = 2;           // ... and run on the K-parity ping-pong kernel (gemm_kp.inc, round 6): RGRG_GEMM_KP = 0 none (the LDS-DMA kernel), 1 all four,
+                                // 2 (default) the producers only (attn_proj / mlp_proj, N = 1024), 3 the consumers only (c_attn / c_fc, 128 x 128 row-split kernel).
+                                // Measured per mode: profiles/r06_step_trace_v3.log
+    int gemm_launches_per_step = 0;
+    const int* pos_override_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached: per-row embedding positions
+    int* row_pos = nullptr;                  // [rows] buffer behind it
+    // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
+    // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
+    int logits_stale_rows = 0;
+    bool logits_valid = false;   // d->logits / the retained ln_f rows belong to the last step of a completed generate / beam / cached call (ADVICE r05:
+                                 // the timing hooks and a precision change overwrite them - rgrg_decoder_copy_last_logits then refuses)
+    // enqueue_step: extra streams + fork / join events of the multi-range many-sequence step (RGRG_DECODE_CHAINS)
+    hipStream_t streams_x[rgrg::MAX_CHAINS - 1] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[rgrg::MAX_CHAINS - 1] = {};
+    int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
+                      // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
+                      // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
+};
+
+namespace rgrg {
+
+inline int pad256(int n) { return (n + 255) / 256 * 256; }  // K granularity of the bf16 GEMM pipeline
+
+// decoder.hip
+int dmalloc(rgrg_decoder* d, void** p, size_t bytes, bool zero);
+int skinny_max_rows();
+int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act,
+           bool count, const unsigned short* X16 = nullptr, unsigned short* Y16 = nullptr, const GemmLnFold* ln = nullptr);
+int launch_ln_rows(const float* x, const float* g, const float* b, float* xn, int D, unsigned short* xn16, int f16, int rows,
+                   hipStream_t st);   // ln_rows_kernel, one wave per row
+int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = nullptr, const int* src = nullptr,
+                 bool beam = false);
+int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1);
+
+}  // namespace rgrg

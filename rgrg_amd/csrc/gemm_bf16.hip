@@ -10,29 +10,13 @@
 // consecutive k) is conflict free.  A and B fragments use the same (lane half, element) -> k mapping, so
 // the K order inside a tile is irrelevant.  Not bit-exact with the fp32 reference by construction: this
 // path is opt-in (torch.autocast) and its tests are tolerance-based.
-#include "common.h"
+#include "internal.h"
 
 namespace rgrg {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
-
-// optional LayerNorm-fold operands of launch_gemm_bf16w_ex (see GemmBf16Params)
-struct GemmLnFold {
-    void* Yb16 = nullptr;
-    float* stats_out = nullptr;
-    const float* ln_stats = nullptr;
-    const float* ln_colsum = nullptr;
-    void* Ypre16 = nullptr;       // training pass: GemmBf16Params::Ypre16 / G16
-    const void* G16 = nullptr;
-    int ksplit = 0;               // split-K (GemmBf16Params::ksplit / sk_ws / sk_cnt)
-    float* sk_ws = nullptr;
-    unsigned* sk_cnt = nullptr;
-    float* cand_val = nullptr;    // arg-max candidates instead of Y (GemmBf16Params::cand_val / cand_idx)
-    int* cand_idx = nullptr;
-    int kp = 0;                   // 1: the K-parity ping-pong kernel (gemm_kp.inc), tile picked from (N, K) only
-};
 
 struct GemmBf16Params {
     const float* A;    // fp32 activations (rounded to bf16 while staged) ...

@@ -14,7 +14,7 @@
 // takes A[i=lane&31][k=lane>>5]; we let half h=lane>>5 own k = 8*kk + 4*h + j for
 // j = 0..3, i.e. MFMA j contracts the k pair {8kk+j, 8kk+4+j}.  A and B use the same
 // permutation of K, so the sum over the tile is unchanged.
-#include "common.h"
+#include "internal.h"
 
 namespace rgrg {
 

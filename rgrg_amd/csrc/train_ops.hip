@@ -4,7 +4,7 @@
 // (:230-236); every other GPT-2 tensor is frozen (:207-213, Conv1DWithTrainedWeights :11-29), so only activation
 // gradients flow through it).  The GEMMs of the backward pass reuse gemm_f32.hip on transposed weight copies; this
 // file holds the element-wise / row-wise / attention parts.  Launchers are called from decoder.hip.
-#include "common.h"
+#include "internal.h"
 
 namespace rgrg {
 
