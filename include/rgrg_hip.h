@@ -261,8 +261,12 @@ int rgrg_dropout_mask_f32(uint64_t seed, uint32_t stream_id, float p, int64_t n,
  * position_ids is NULL, past_len + j (what prepare_inputs_for_generation passes, :498-520); each appends its key / value;
  * logits_out f32 [S,T,vocab] receives lm_logits of every fed position.  past_len + T <= the decoder's max_len.
  * attention_mask: NULL (all ones: generation) or f32 [S][past_len + T] over ALL token keys so far - the reference adds
- * (1 - mask) * -1e4 to the scores of a masked key for every query, the image key is never masked (:316-334).  Runs on the
- * decoder's stream between two event edges with `stream`. */
+ * (1 - mask) * -1e4 to the scores of a masked key for every query, the image key is never masked (:316-334).  The mask is
+ * applied by the fp32 attention kernel only: in precision mode 1 / 2 (rgrg_decoder_set_precision) with S above
+ * rgrg_decoder_row_limit() the step would read the 16-bit K/V cache, whose kernel has no mask operand, so a non-NULL
+ * attention_mask then FAILS with RGRG_EINVAL (rgrg_last_error() says so) before anything is launched - it never returns
+ * unmasked logits.  Set precision mode 0 first (the Python layer does).  Runs on the decoder's stream between two event edges
+ * with `stream`. */
 int rgrg_decoder_forward_cached(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const int64_t* position_ids,
                                 const float* attention_mask,
                                 int S, int T, int past_len, float* logits_out, void* stream);
@@ -365,6 +369,46 @@ int rgrg_debug_linear_bf16_ln(const uint16_t* A16, const uint16_t* Wb, const flo
 int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t* Wb, const float* shift, const float* R, float* Y,
                                  uint16_t* Y16, uint16_t* Yb16, float* stats_out, const float* ln_stats, const float* ln_colsum,
                                  int M, int N, int K, int ldy, int act, int fp16, int kp, void* stream);
+/* Test hooks for the attention kernels (GPT2PseudoAttention, src/language_model/language_model.py: _attn :84-122 - scores / 8,
+ * future token columns replaced by -1e4, the additive padding mask (1 - [1 | attention_mask]) * -1e4 of :316-334, softmax,
+ * attn_dropout :116, the product with V - and forward :124-160, which puts the image key / value uk(img) / uv(img) in front of
+ * the token keys).  Each entry launches the kernels of the product path on the caller's device buffers through the product's own
+ * launcher (same instantiation and grid rules); none needs a decoder object.
+ * rgrg_debug_attn_decode: ONE decode step of the incremental form (layer_past given, :162-166; greedy_search / beam_search
+ * :420-428, _reorder_cache :492-496).  qkv [S][ld_qkv] = q | k | v of the new token; kcache / vcache [S][H][T_slots][64];
+ * *step_dev = t: keys are slots 0 .. t + 1, the new key / value is written to slot t + 1 of the row.  src [S][T_slots] (or
+ * NULL): the cache row that holds slot j of row s (beam search).  kmask [S][T_slots] (or NULL): additive mask per slot.
+ *   kv16 = 0: fp32 cache, attn_decode_kernel<src, ni, kmask>; ni = 9 / 2 keys per group and chunk, 0 = the product's rule
+ *             (S * H <= 4096 ? 9 : 2); frag_out = 1: `out` in the fragment-major layout of the fused plan's attn_proj.
+ *   kv16 = 1: 16-bit cache (fp16 = 0 bf16 / 1 IEEE half), attn_decode_kv16_wave_kernel<src, fp16>; the result goes to out16
+ *             when given, else to out; max_workgroups > 0 caps the grid (RGRG_ATTN_WGS_PER_CU does that in the product).
+ *   RGRG_EINVAL: kmask with src, kmask with kv16, H % 4 with kv16, ni outside {0, 2, 9}. */
+int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                           uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int kv16, int fp16,
+                           int ni, int frag_out, int max_workgroups, void* stream);
+/* rgrg_debug_attn_prefill: the attention without layer_past over T tokens (:135-157, :84-122) of rgrg_decoder_lm_forward and
+ * the forward half of rgrg_decoder_lm_loss_grad.  qkv [S*T][3*H*64]; ukv [S][ld_ukv], image key at column kcol, image value at
+ * kcol + H*64; am [S][T] or NULL; out f32 [S*T][H*64]; out16 (optional) the same as 16 bit; lse (optional) [S*T][H];
+ * dropout (seed, stream_id, p) as rgrg_dropout_mask_f32 with row_len = T + 1.  variant 0: the product's rule; 1 / 2:
+ * attn_prefill_kernel<3> / <8> (T + 1 <= 96 / 256 keys in registers); 3: attn_prefill_stream_kernel.  RGRG_EINVAL when T + 1
+ * keys do not fit the forced variant. */
+int rgrg_debug_attn_prefill(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, float* out, uint16_t* out16,
+                            float* lse, int S, int H, int T, int variant, uint64_t seed, uint32_t stream_id, float p, int fp16,
+                            void* stream);
+/* rgrg_debug_attn_backward_f32: the autograd of that attention (loss.backward() of train_full_model.py:208 through :84-160) in
+ * fp32: attn_delta_kernel, attn_bwd_dq_kernel, attn_bwd_dkv_kernel.  d_att / att [S*T][H*64] (gradient and value of the forward
+ * output), lse from the forward; delta [S*T][H] (written); d_qkv [S*T][3*H*64] or, when d_qkv16 is given, that tensor as 16 bit
+ * only; d_ukv [S][ld_ukv]: the image key / value gradient at kcol .. kcol + 2*H*64, times ukv_scale.  H == 16. */
+int rgrg_debug_attn_backward_f32(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, const float* d_att,
+                                 const float* att, const float* lse, float* delta, float* d_qkv, float* d_ukv, uint16_t* d_qkv16,
+                                 int S, int H, int T, uint64_t seed, uint32_t stream_id, float p, int fp16, float ukv_scale,
+                                 void* stream);
+/* rgrg_debug_attn_train16: the same attention on 16-bit operands (torch.autocast around the training step,
+ * train_full_model.py:172-237): backward = 0 runs attn16_fwd_kernel (qkv16, ukv16, am -> att16, lse), backward = 1
+ * attn16_bwd_kernel (+ d_att16, att16, lse -> d_qkv16, d_ukv f32 times ukv_scale).  RGRG_EINVAL for T + 1 > 128 keys. */
+int rgrg_debug_attn_train16(int backward, const uint16_t* qkv16, const uint16_t* ukv16, int ld_ukv, int kcol, const float* am,
+                            uint16_t* att16, float* lse, const uint16_t* d_att16, uint16_t* d_qkv16, float* d_ukv, int S, int H,
+                            int T, uint64_t seed, uint32_t stream_id, float p, float ukv_scale, int fp16, void* stream);
 /* ---- detector targets and losses: ObjectDetector.forward(images, targets), the detector half of
  * ReportGenerationModel.forward(images, image_targets, ...) (src/full_model/report_generation_model.py:55,91 ->
  * src/object_detector/object_detector.py:216-224 -> custom_rpn.py:74-83, custom_roi_heads.py:225-242, and underneath

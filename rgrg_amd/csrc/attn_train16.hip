@@ -436,3 +436,17 @@ int launch_attn16_backward(const unsigned short* qkv16, const unsigned short* uk
 }
 
 }  // namespace rgrg
+
+using namespace rgrg;
+
+// Test hook: the 16-bit training attention alone.  backward == 0: launch_attn16_forward writes att16 / lse; else launch_attn16_backward
+// reads them (with d_att16) and writes d_qkv16 / d_ukv.  RGRG_EINVAL when !attn16_supported(T).
+extern "C" int rgrg_debug_attn_train16(int backward, const uint16_t* qkv16, const uint16_t* ukv16, int ld_ukv, int kcol, const float* am,
+                                       uint16_t* att16, float* lse, const uint16_t* d_att16, uint16_t* d_qkv16, float* d_ukv, int S,
+                                       int H, int T, uint64_t seed, uint32_t stream_id, float p, float ukv_scale, int fp16, void* stream) {
+    RGRG_CHECK_ARG(S > 0 && H > 0 && kcol >= 0 && ld_ukv >= kcol + 2 * H * 64 && p >= 0.f && p < 1.f);
+    const DropoutParams drop{seed, stream_id, p};
+    if (!backward) return launch_attn16_forward(qkv16, ukv16, ld_ukv, kcol, am, att16, lse, S, H, T, drop, fp16 ? 1 : 0, as_stream(stream));
+    return launch_attn16_backward(qkv16, ukv16, ld_ukv, kcol, am, d_att16, att16, lse, d_qkv16, d_ukv, S, H, T, drop, ukv_scale, fp16 ? 1 : 0,
+                                  as_stream(stream));
+}

@@ -416,30 +416,43 @@ __device__ __forceinline__ void attn_chunk(const float* __restrict__ kc, const f
         mk[i] = HAS_MASK ? kmask[(size_t)s * T + jc] : 0.f;
     }
     __builtin_amdgcn_sched_barrier(0);  // all 2 * NI loads are in flight before the first dot product waits
+    // The running softmax advances ONE KEY AT A TIME, so that a group's result is a function of its sequence of keys alone and
+    // not of how the launcher cuts that sequence into chunks: the 9- and the 2-key instantiation, and every size of the tail
+    // chunk, give the same bits (tests/test_gpu_attention_kernels.py).  Per key one of (rescale of the past, weight of the key)
+    // is 1 and the other exp(-|score - max|): one exponential per key, as before.  Contraction is spelled out (fmaf) and
+    // otherwise off, so that the compiler cannot fuse the differently unrolled instantiations differently.
+    {
+#pragma clang fp contract(off)
     float sc[NI];
-    float cmax = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int j = base + (i * 4 + wave) * 4 + g;
         if (j == slot) { kk[i] = k4; vv[i] = v4; }  // selects, not branches: the new token's key / value
-        const float dot = group16_sum_dpp((q4[0] * kk[i][0] + q4[1] * kk[i][1]) + (q4[2] * kk[i][2] + q4[3] * kk[i][3]));
-        sc[i] = j < nkeys ? (HAS_MASK ? dot / 8.0f + mk[i] : dot / 8.0f) : -INFINITY;
-        cmax = fmaxf(cmax, sc[i]);
+        const float dot = group16_sum_dpp(fmaf(q4[0], kk[i][0], q4[1] * kk[i][1]) + fmaf(q4[2], kk[i][2], q4[3] * kk[i][3]));
+        sc[i] = HAS_MASK ? dot / 8.0f + mk[i] : dot / 8.0f;
     }
-    const float m_new = fmaxf(m, cmax);
-    const float scale = (m == -INFINITY) ? 0.f : expf(m - m_new);  // 1 on the first chunk's empty start, never NaN
-    l *= scale;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] *= scale;
+    // prefix maxima first (a chain of compares), so that the exponentials below do not wait for one another
+    float ex[NI];
+    bool up[NI];
+    float mp = m;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        const int j = base + (i * 4 + wave) * 4 + g;
-        const float p = j < nkeys ? expf(sc[i] - m_new) : 0.f;
-        l += p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += p * (j < nkeys ? vv[i][e] : 0.f);
+        const bool valid = base + (i * 4 + wave) * 4 + g < nkeys;
+        up[i] = valid && sc[i] > mp;                                 // this key raises the maximum (the first key: from -inf)
+        ex[i] = valid ? expf(-fabsf(sc[i] - mp)) : 0.f;              // exp(-inf) = 0 on the first key, never NaN
+        mp = up[i] ? sc[i] : mp;
     }
-    m = m_new;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const bool valid = base + (i * 4 + wave) * 4 + g < nkeys;
+        const float scale = up[i] ? ex[i] : 1.f;
+        const float p = up[i] ? 1.f : ex[i];                         // 0 for a key that does not exist
+        l = fmaf(l, scale, p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = fmaf(p, valid ? vv[i][e] : 0.f, acc[e] * scale);
+    }
+    m = mp;
+    }
 }
 
 // ATT_NI = keys per group per FULL chunk: 9 (up to 144 keys with everything in flight at once) when the grid is a
@@ -447,7 +460,8 @@ __device__ __forceinline__ void attn_chunk(const float* __restrict__ kc, const f
 // to the keys that exist in steps of 16 (a wave-uniform switch; round 4: it used to request, dot and exponentiate 144
 // rows whatever the step, 2.2x what a 128-token decode needs on average); 2 when thousands of workgroups queue up
 // (throughput bound: fewer registers -> more resident workgroups).  A key's group and register do not depend on the
-// chunk size: results are unchanged bit for bit.
+// chunk size and the running softmax advances key by key (attn_chunk): results are unchanged bit for bit, across the
+// tail sizes and between the two instantiations.
 // HAS_MASK (round 6, forward(use_cache=True) with padding): kmask [S][T] = the additive mask of every cache slot (slot 0, the image,
 // holds 0); the default instantiation carries none of it.
 template <bool HAS_SRC, int ATT_NI, bool HAS_MASK = false>  // HAS_SRC (beam search): per-slot ancestor table (one more dependent load per key, requested first)
@@ -1068,46 +1082,79 @@ static bool lm_head_cand_path(const rgrg_decoder* d, int S) {
            gemm_bf16_cand_epilogue_ok(S, d->lm_head.N, d->lm_head.K);
 }
 
-// r0: first sequence of the launch (the many-sequence step may run as two row ranges on two streams, enqueue_step); src / att16
-// are the caller's pointers for that first sequence already
-static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsigned short* att16, int frag_out = 0, int r0 = 0) {
-    hipStream_t st = d->stream;
-    const int D = d->D;
-    float* kc = d->kv + (size_t)l * d->kv_layer_stride;
-    float* vc = kc + d->kv_kv_stride;
-    if (kv_is_bf16(d, S)) {
-        u16* kc16 = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride;
+// One decode-attention launch on plain device pointers: the variant and grid rules of the product path.  launch_attention fills
+// it from the decoder object, the test hook rgrg_debug_attn_decode from its arguments - the rules exist once, here.
+struct AttnDecodeLaunch {
+    const float* qkv; int ld_qkv;          // [S][ld_qkv]: q | k | v of the current token, D floats each
+    void *kc, *vc;                         // K / V plane [rows][H][T][64]: fp32, or 16 bit (kv16)
+    size_t plane_elems;                    // elements of one plane (kv16: bounds the 32-bit byte offsets of the buffer loads)
+    const int* step;
+    float* out; unsigned short* out16;
+    int S, H, T;
+    const int* src;                        // beam search: [S][T] ancestor table, or NULL
+    const float* kmask;                    // [S][T] additive padding mask of the cache slots, or NULL (fp32 kernel without src only)
+    int kv16, f16;
+    int ni;                                // fp32 kernel: 9 / 2 keys per group and chunk; 0 = S * H <= 4096 ? 9 : 2
+    int frag_out;
+    int max_wgs;                           // kv16 kernel: > 0 caps the grid, each wave then walks several (sequence, head) items
+    hipStream_t st;
+};
+static int launch_attn_decode(const AttnDecodeLaunch& a) {
+    if (a.kmask && (a.kv16 || a.src)) {
+        set_error("decode attention: the padding mask exists only in the fp32 kernel without an ancestor table (%s)",
+                  a.kv16 ? "16-bit K/V cache" : "beam search");
+        return RGRG_EINVAL;
+    }
+    if (a.kv16) {
         // one wave per (sequence, head); the cache rows are addressed with 32-bit byte offsets into one layer's K (V)
         // plane through a buffer descriptor, which bounds a plane at 2 GiB (8128 sequences at max_length 128)
-        if ((d->H & 3) != 0 || (size_t)d->kv_kv_stride * sizeof(u16) >= ((size_t)1 << 31)) {
+        if ((a.H & 3) != 0 || a.plane_elems * sizeof(u16) >= ((size_t)1 << 31)) {
             set_error("decoder: the bf16 K/V cache plane of one layer (%zu bytes) exceeds the 2 GiB the attention kernel addresses: "
-                      "lower the batch or max_length", (size_t)d->kv_kv_stride * sizeof(u16));
+                      "lower the batch or max_length", a.plane_elems * sizeof(u16));
             return RGRG_EINVAL;
         }
-        // RGRG_ATTN_WGS_PER_CU = n > 0: at most n * 256 workgroups, each wave walks several (sequence, head) items
-        static const int cap = [] { const char* e = getenv("RGRG_ATTN_WGS_PER_CU"); return e ? atoi(e) : 0; }();
-        const int wgs = S * d->H / 4;
-        const dim3 wgrid(cap > 0 ? std::min(wgs, cap * 256) : wgs), wblk(256);
-        u16* kc16r = kc16 + (size_t)r0 * d->H * d->T * 64;   // cache rows of sequence r0 (layout [sequence][head][slot][64])
-#define KV16_LAUNCH(SRC_, F16_) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<SRC_, F16_>), wgrid, wblk, 0, st, d->qkv + (size_t)r0 * 3 * D, 3 * D, kc16r, \
-                                                  kc16r + d->kv_kv_stride, d->step, d->att + (size_t)r0 * D, S, d->H, d->T, src, att16)
-        if (src) { if (d->f16()) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
-        else { if (d->f16()) KV16_LAUNCH(false, true); else KV16_LAUNCH(false, false); }
+        const int wgs = a.S * a.H / 4;
+        const dim3 wgrid(a.max_wgs > 0 ? std::min(wgs, a.max_wgs) : wgs), wblk(256);
+#define KV16_LAUNCH(SRC_, F16_) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<SRC_, F16_>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
+                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.out16)
+        if (a.src) { if (a.f16) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
+        else { if (a.f16) KV16_LAUNCH(false, true); else KV16_LAUNCH(false, false); }
 #undef KV16_LAUNCH
     } else {
-        const dim3 grid(S * d->H), blk(256);
-#define ATT_LAUNCH(SRC_, NI_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step, d->att, S, d->H, d->T, src, frag_out)
-        if (d->key_mask_cur && !src) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
-#define ATT_LAUNCH_MASK(NI_) hipLaunchKernelGGL((attn_decode_kernel<false, NI_, true>), grid, blk, 0, st, d->qkv, 3 * D, kc, vc, d->step, d->att, S, d->H, d->T, \
-                                                  src, frag_out, d->key_mask_cur)
-            if (S * d->H <= 4096) ATT_LAUNCH_MASK(9); else ATT_LAUNCH_MASK(2);
-#undef ATT_LAUNCH_MASK
-        } else if (S * d->H <= 4096) { if (src) ATT_LAUNCH(true, 9); else ATT_LAUNCH(false, 9); }
-        else { if (src) ATT_LAUNCH(true, 2); else ATT_LAUNCH(false, 2); }
+        const dim3 grid(a.S * a.H), blk(256);
+        const int ni = a.ni ? a.ni : (a.S * a.H <= 4096 ? 9 : 2);
+        if (ni != 9 && ni != 2) { set_error("decode attention: %d keys per group, the kernel is built for 9 and 2", ni); return RGRG_EINVAL; }
+#define ATT_LAUNCH(SRC_, NI_, MASK_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_, MASK_>), grid, blk, 0, a.st, a.qkv, a.ld_qkv, static_cast<float*>(a.kc), \
+                                                       static_cast<float*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.frag_out, a.kmask)
+        if (a.kmask) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
+            if (ni == 9) ATT_LAUNCH(false, 9, true); else ATT_LAUNCH(false, 2, true);
+        } else if (ni == 9) { if (a.src) ATT_LAUNCH(true, 9, false); else ATT_LAUNCH(false, 9, false); }
+        else { if (a.src) ATT_LAUNCH(true, 2, false); else ATT_LAUNCH(false, 2, false); }
 #undef ATT_LAUNCH
     }
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
+}
+
+// r0: first sequence of the launch (the many-sequence step may run as two row ranges on two streams, enqueue_step); src / att16
+// are the caller's pointers for that first sequence already
+static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsigned short* att16, int frag_out = 0, int r0 = 0) {
+    const int D = d->D;
+    AttnDecodeLaunch a{};
+    a.ld_qkv = 3 * D; a.step = d->step; a.S = S; a.H = d->H; a.T = d->T; a.src = src; a.kmask = d->key_mask_cur;
+    a.frag_out = frag_out; a.st = d->stream; a.plane_elems = d->kv_kv_stride;
+    if (kv_is_bf16(d, S)) {
+        // RGRG_ATTN_WGS_PER_CU = n > 0: at most n * 256 workgroups, each wave walks several (sequence, head) items
+        static const int cap = [] { const char* e = getenv("RGRG_ATTN_WGS_PER_CU"); return e ? atoi(e) : 0; }();
+        u16* kc16r = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride + (size_t)r0 * d->H * d->T * 64;   // cache rows of sequence r0 (layout [sequence][head][slot][64])
+        a.kv16 = 1; a.f16 = d->f16(); a.max_wgs = cap > 0 ? cap * 256 : 0;
+        a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kc16r; a.vc = kc16r + d->kv_kv_stride;
+        a.out = d->att + (size_t)r0 * D; a.out16 = att16;
+    } else {
+        float* kc = d->kv + (size_t)l * d->kv_layer_stride;
+        a.qkv = d->qkv; a.kc = kc; a.vc = kc + d->kv_kv_stride; a.out = d->att;
+    }
+    return launch_attn_decode(a);
 }
 
 // One GEMM of the fused plan.  `a` arrives with the operand / output pointers and `act` set; the layer fills the rest.
@@ -1672,6 +1719,13 @@ extern "C" int rgrg_decoder_forward_cached(rgrg_decoder* d, const float* feats, 
     // past_key_values of shape [.., 1, 64], language_model.py:162-166 uses the supplied past and ignores the image then)
     RGRG_CHECK_ARG(past_len == 0 || feats == nullptr);
     RGRG_CHECK_ARG(past_len + T <= d->max_len);   // slot of the last token = past_len + T <= T_cache - 1
+    // The padding mask exists only in the fp32 attention kernel: in a 16-bit mode above the row limit the step reads the 16-bit
+    // cache with attn_decode_kv16_wave_kernel, which has no mask operand - refuse, rather than return unmasked logits
+    if (attention_mask && kv_is_bf16(d, S)) {
+        set_error("rgrg_decoder_forward_cached: attention_mask is not supported in precision mode %d for %d sequences (more than the "
+                  "%d rows of the fp32-cache path): call rgrg_decoder_set_precision(d, 0) first", d->bf16_gemms, S, decode_row_limit(d));
+        return RGRG_EINVAL;
+    }
     hipStream_t caller = as_stream(stream), st = d->stream;
     RGRG_HIP(hipEventRecord(d->ev_in, caller));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
@@ -1748,6 +1802,22 @@ extern "C" int rgrg_decoder_refresh_trainable(rgrg_decoder* d, void* stream) {
     RGRG_HIP(hipEventRecord(d->ev_in, st));
     RGRG_HIP(hipStreamWaitEvent(caller, d->ev_in, 0));
     return RGRG_OK;
+}
+
+// Test hook: ONE decode-attention launch on the caller's buffers, through the launcher of the product path (launch_attn_decode).
+extern "C" int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                                      uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int kv16,
+                                      int fp16, int ni, int frag_out, int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && step_dev && S > 0 && H > 0 && T_slots >= 2 && ld_qkv >= 3 * H * 64);
+    RGRG_CHECK_ARG(out || (kv16 && out16));
+    RGRG_CHECK_ARG(kv16 || (!out16 && max_workgroups == 0));
+    RGRG_CHECK_ARG(!kv16 || (ni == 0 && frag_out == 0));
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.src = src; a.kmask = kmask;
+    a.kv16 = kv16 ? 1 : 0; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.frag_out = frag_out ? 1 : 0; a.max_wgs = max_workgroups;
+    a.st = as_stream(stream);
+    return launch_attn_decode(a);
 }
 
 // Test hook: the weight side of the folded LayerNorm (ln_fold16_kernel, used by rgrg_decoder_set_precision).

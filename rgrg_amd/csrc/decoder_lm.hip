@@ -294,13 +294,23 @@ static bool prefill_stream_forced() {
     return v;
 }
 
+// Which kernel the attention of a T-token teacher-forced pass runs on: 1 = attn_prefill_kernel<3>, 2 = <8>, 3 = streaming
+static int attn_prefill_variant(int T) { return (T + 1 > 256 || prefill_stream_forced()) ? 3 : (T + 1 <= 96 ? 1 : 2); }
+
+// variant 0: the rule above; 1 / 2 / 3 force a kernel (test hook) and fail when its key tiles cannot hold T + 1 keys
 static int launch_attn_prefill(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, float* out, int S, int H,
-                               int T, float* lse, const DropoutParams& drop, hipStream_t st, unsigned short* out16 = nullptr, int f16 = 0) {
+                               int T, float* lse, const DropoutParams& drop, hipStream_t st, unsigned short* out16 = nullptr, int f16 = 0,
+                               int variant = 0) {
     const int items = S * H * ((T + 31) / 32);
     const dim3 grid((items + 3) / 4), block(256);
-    if (T + 1 > 256 || prefill_stream_forced())
+    if (!variant) variant = attn_prefill_variant(T);
+    if (T < 1 || T > TF_MAX_T || variant < 1 || variant > 3 || (variant == 1 && T + 1 > 96) || (variant == 2 && T + 1 > 256)) {
+        set_error("attention of the teacher-forced pass: %d keys do not fit kernel variant %d", T + 1, variant);
+        return RGRG_EINVAL;
+    }
+    if (variant == 3)
         hipLaunchKernelGGL(attn_prefill_stream_kernel, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
-    else if (T + 1 <= 96)
+    else if (variant == 1)
         hipLaunchKernelGGL(attn_prefill_kernel<3>, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
     else
         hipLaunchKernelGGL(attn_prefill_kernel<8>, grid, block, 0, st, qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, drop, out16, f16);
@@ -986,4 +996,14 @@ extern "C" int rgrg_decoder_time_train_gemms(rgrg_decoder* d, int S, int T, int 
     *flops_per_step = flops;
     *launches_per_step = launches;
     return RGRG_OK;
+}
+
+// Test hook: the attention of the teacher-forced / training forward pass alone, on the caller's buffers, through launch_attn_prefill.
+extern "C" int rgrg_debug_attn_prefill(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, float* out,
+                                       uint16_t* out16, float* lse, int S, int H, int T, int variant, uint64_t seed,
+                                       uint32_t stream_id, float p, int fp16, void* stream) {
+    RGRG_CHECK_ARG(qkv && ukv && out && S > 0 && H > 0 && kcol >= 0 && ld_ukv >= kcol + 2 * H * 64 && p >= 0.f && p < 1.f);
+    RGRG_CHECK_ARG(variant >= 0 && variant <= 3);
+    return launch_attn_prefill(qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, DropoutParams{seed, stream_id, p}, as_stream(stream), out16,
+                               fp16 ? 1 : 0, variant);
 }

@@ -745,3 +745,15 @@ extern "C" int rgrg_adamw_multi_step_f32(const void* items, int n_items, float l
     }
     return RGRG_OK;
 }
+
+// Test hook: the fp32 attention backward (attn_delta_kernel, attn_bwd_dq_kernel, attn_bwd_dkv_kernel) alone, through launch_attn_backward.
+extern "C" int rgrg_debug_attn_backward_f32(const float* qkv, const float* ukv, int ld_ukv, int kcol, const float* am, const float* d_att,
+                                            const float* att, const float* lse, float* delta, float* d_qkv, float* d_ukv,
+                                            uint16_t* d_qkv16, int S, int H, int T, uint64_t seed, uint32_t stream_id, float p,
+                                            int fp16, float ukv_scale, void* stream) {
+    // attn_delta_kernel covers a row of 1024 floats with its 256 threads: the model's 16 heads
+    RGRG_CHECK_ARG(qkv && ukv && d_att && d_ukv && (d_qkv || d_qkv16) && S > 0 && H == 16 && T >= 1 && T <= 1023 && kcol >= 0 &&
+                   ld_ukv >= kcol + 2 * H * 64 && p >= 0.f && p < 1.f);
+    return launch_attn_backward(qkv, ukv, ld_ukv, kcol, am, d_att, att, lse, delta, d_qkv, d_ukv, S, H, T, DropoutParams{seed, stream_id, p},
+                                as_stream(stream), d_qkv16, fp16 ? 1 : 0, ukv_scale);
+}
