@@ -182,6 +182,34 @@ void rgrg_decoder_destroy(rgrg_decoder* d);
  * before returning.  use_graph=0 launches the kernels eagerly (debug/profiling). */
 int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_length, int64_t* out_ids,
                           int out_ld, int* out_len, int use_graph, void* stream);
+/* ---- Sampling.  The sampler is a pure function of one fp32 logits row x[0..V), temperature > 0, top_k >= 0 (0 = off),
+ * 0 < top_p <= 1 (1 = off), a 64-bit seed, a row counter r and a step t:
+ *   temperature  z_i = x_i * inv_T, inv_T = 1.0f / temperature computed once on the host in fp32.
+ *   top-k        HF 4.19.2 TopKLogitsWarper: keep every token whose logit is >= the k-th largest logit (raw x, exact compare);
+ *                ties with the k-th value are all kept; k >= V is a no-op.
+ *   top-p        after top-k, on the distribution re-normalised over the top-k set: keep token i iff the total probability of
+ *                the kept tokens with a STRICTLY GREATER logit is <= top_p (TopPLogitsWarper with min_tokens_to_keep = 1,
+ *                stated through a threshold).  Tokens with equal logits are therefore kept or dropped TOGETHER; HF breaks
+ *                such ties by the order its sort happens to return.
+ *   draw         w = first output word of Philox4x32-10 with key = seed (low word, high word) and counter = (r, t, 0, 0);
+ *                u = (w >> 8) * 2^-24; the token is the first kept index j in VOCABULARY order whose running sum of
+ *                exp(z_i - max z) over the kept i <= j exceeds u times the kept total.  top_k = 1: the first kept index -
+ *                the first-occurrence arg-max, exactly what greedy returns.
+ *   log-prob     log q(token) under the distribution the token was drawn from (after temperature and filters), fp32.
+ * Deterministic: the same inputs give the same bits (masses are accumulated as 64-bit fixed-point integers, sample.hip).
+ *
+ * rgrg_decoder_sample: rgrg_decoder_generate with the arg-max replaced by that draw, row counter r = the row, t = the step
+ * (0 for the first generated token).  Same prefill, same out_ids / *out_len semantics (PAD after a row's EOS); out_logprobs
+ * f32 [S,out_ld] or NULL: log-prob of every generated token, 0 in the BOS column and for the PAD of finished rows.  Runs on
+ * every step plan and precision mode; the step is captured once per S and serves every seed and parameter set.  Afterwards
+ * rgrg_decoder_copy_last_logits returns the logits the last draw was made from. */
+int rgrg_decoder_sample(rgrg_decoder* d, const float* feats, int S, int max_length, float temperature, int top_k, float top_p,
+                        uint64_t seed, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph,
+                        void* stream);
+/* The same sampler on caller-provided logits [S][ld] (V <= 53248; 16-byte loads when ld % 4 == 0 and logits is 16-byte
+ * aligned): row s is drawn with the counter (row0 + s, step).  out_tok int32 [S], out_logprob f32 [S] or NULL. */
+int rgrg_sample_logits_f32(const float* logits, int64_t ld, int S, int V, float temperature, int top_k, float top_p,
+                           uint64_t seed, int step, int row0, int* out_tok, float* out_logprob, void* stream);
 /* Beam search (LanguageModel.generate num_beams > 1 -> beam_search, language_model.py:450-475,
  * :529-607, with transformers 4.19.2 BeamSearchScorer semantics; 1 <= num_return_sequences <= num_beams).
  * The decoder must have been created with max_seqs >= S*num_beams.  Any num_beams, as in the reference (up to 16 the row / item

@@ -758,10 +758,7 @@ __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__
 // bookkeeping (:629-650).  The lm_head GEMM already reduced every 16- / 32-column tile to one
 // (max, index) candidate (ties: lower index), so a row is NT <= 3142 candidates: a thread requests its
 // (up to 13) candidates up front with clamped indices - one memory latency instead of one per loop trip.
-// The LAST workgroup to arrive records the first length at which every row is finished and advances the
-// step counter: arrival and "this row is still unfinished" travel in ONE packed atomic (low 16 bits: tickets,
-// high 16 bits: unfinished rows; S < 65536), so no fence and no second atomic order the two - the integer
-// ticket keeps the result deterministic.  sync[0] = the packed word.
+// The bookkeeping (PAD / EOS / the packed arrival ticket) is record_step_token (decoder_internal.h).
 constexpr int ARGMAX_U = 13;
 __global__ __launch_bounds__(256) void argmax_update_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
                                                             int NT, long long* __restrict__ ids, int ld_ids,
@@ -801,20 +798,8 @@ __global__ __launch_bounds__(256) void argmax_update_kernel(const float* __restr
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        int tok = idx == 0x7fffffff ? 0 : idx;
-        int fin = finished[row];
-        if (fin) tok = PAD_ID;
-        ids[(size_t)row * ld_ids + t + 1] = tok;
-        if (tok == EOS_ID) fin = 1;
-        finished[row] = fin;
-        const unsigned mine = fin ? 0u : 0x10000u;
-        const unsigned old = atomicAdd(reinterpret_cast<unsigned*>(sync), 1u + mine);
-        if ((old & 0xffffu) == (unsigned)(S - 1)) {  // every row has been recorded
-            const unsigned unfinished = (old >> 16) + (mine >> 16);
-            if (unfinished == 0 && *done_len == 0) *done_len = t + 2;
-            *step = t + 1;
-            sync[0] = 0;
-        }
+        const StepBook bk{ids, ld_ids, finished, step, done_len, sync, S};
+        record_step_token(bk, row, t, idx == 0x7fffffff ? 0 : idx);
     }
 }
 
@@ -1610,32 +1595,37 @@ extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
     delete d;
 }
 
-extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_length, int64_t* out_ids,
-                                     int out_ld, int* out_len, int use_graph, void* stream) {
-    RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && S <= d->max_seqs);
-    int limit = (max_length > 0) ? max_length : d->max_len;
-    RGRG_CHECK_ARG(limit >= 2 && limit <= d->max_len && out_ld >= limit);
-    hipStream_t caller = as_stream(stream);
-    RGRG_HIP(hipEventRecord(d->ev_in, caller));
+namespace rgrg {
+// The decode loop that greedy search and sampling share.  decode_begin: d->stream waits for the caller's stream.
+// run_decode_loop: prefill, then `step` (one decode step ending in a kernel that calls record_step_token) limit - 1 times -
+// captured once per S under `graph_key` when use_graph -, the polling below, and the copies of ids [S, limit] (and of the
+// sampler's log-probs, d->sample_lp, when out_logprobs is given) before the one synchronise; *out_len as rgrg_decoder_generate
+// documents it.
+int decode_begin(rgrg_decoder* d, void* stream) {
+    RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(d->stream, d->ev_in, 0));
-    d->logits_valid = false;   // until this call has completed (an early error return leaves no logits to copy)
+    d->logits_valid = false;   // until the call has completed (an early error return leaves no logits to copy)
+    return RGRG_OK;
+}
+int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
+                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len) {
     int rc = enqueue_prefill(d, feats, S);
     if (rc) return rc;
 
     hipGraphExec_t exec = nullptr;
     if (use_graph) {
         for (auto& g : d->graphs)
-            if (g.S == S && g.key2 == 0) exec = g.exec;
+            if (g.S == S && g.key2 == graph_key) exec = g.exec;
         if (!exec) {
             hipGraph_t graph = nullptr;
             RGRG_HIP(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_step(d, S, true);
+            rc = step(d, S, true);
             hipError_t e = hipStreamEndCapture(d->stream, &graph);
             if (rc) return rc;
             if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
             RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
             (void)hipGraphDestroy(graph);
-            d->graphs.push_back({S, exec, 0, 0});
+            d->graphs.push_back({S, exec, graph_key, 0});
         }
     }
     const int steps = limit - 1;
@@ -1651,7 +1641,7 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
         if (exec) {
             RGRG_HIP(hipGraphLaunch(exec, d->stream));
         } else {
-            rc = enqueue_step(d, S, t == 0);
+            rc = step(d, S, t == 0);
             if (rc) return rc;
         }
         if ((t & 15) == 15 && t + 1 < steps) {
@@ -1669,11 +1659,28 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
     RGRG_HIP(hipMemcpyAsync(d->h_done, d->done_len, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), d->ids, (size_t)d->max_len * sizeof(long long),
                               (size_t)limit * sizeof(int64_t), S, hipMemcpyDeviceToDevice, d->stream));
+    if (out_logprobs)
+        RGRG_HIP(hipMemcpy2DAsync(out_logprobs, (size_t)out_ld * sizeof(float), d->sample_lp, (size_t)d->max_len * sizeof(float),
+                                  (size_t)limit * sizeof(float), S, hipMemcpyDeviceToDevice, d->stream));
     RGRG_HIP(hipStreamSynchronize(d->stream));
     done = *d->h_done;
     *out_len = (done > 0 && done < limit) ? done : limit;
-    d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
     d->logits_valid = true;
+    return RGRG_OK;
+}
+}  // namespace rgrg
+
+static int greedy_step(rgrg_decoder* d, int S, bool count) { return enqueue_step(d, S, count); }
+
+extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_length, int64_t* out_ids,
+                                     int out_ld, int* out_len, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && S <= d->max_seqs);
+    int limit = (max_length > 0) ? max_length : d->max_len;
+    RGRG_CHECK_ARG(limit >= 2 && limit <= d->max_len && out_ld >= limit);
+    int rc = decode_begin(d, stream);
+    if (rc) return rc;
+    if ((rc = run_decode_loop(d, feats, S, limit, 0, greedy_step, use_graph, out_ids, out_ld, nullptr, out_len))) return rc;
+    d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
     return RGRG_OK;
 }
 

@@ -14,6 +14,38 @@ constexpr int SKINNY_MAX_ROWS = 128;  // 4 row tiles of 32 sequences per weight-
 constexpr int BOS_ID = 50256, EOS_ID = 50256, PAD_ID = 50256;
 constexpr int BEAM_K = 32;  // max 2*num_beams candidates per row (num_beams <= 16)
 
+// The bookkeeping of one greedy_search step (:629-650) for one row, run by ONE thread of the row's workgroup: a finished row
+// takes PAD, the token goes to ids[row][t + 1], EOS finishes the row, and the LAST row to arrive records the first length
+// at which every row is finished and advances the step counter.  Arrival and "this row is still unfinished" travel in ONE
+// packed atomic (low 16 bits: tickets, high 16 bits: unfinished rows; S < 65536), so no fence and no second atomic order
+// the two - the integer ticket keeps the result deterministic.  sync[0] = the packed word.  Shared by argmax_update_kernel
+// (decoder.hip) and sample_kernel (sample.hip).  -> the token written; *was_finished: the row had finished before this step.
+struct StepBook {
+    long long* ids;   // [S][ld_ids]
+    int ld_ids;
+    int *finished, *step, *done_len, *sync;
+    int S;
+};
+#ifdef __HIPCC__
+__device__ __forceinline__ int record_step_token(const StepBook& bk, int row, int t, int tok, bool* was_finished = nullptr) {
+    int fin = bk.finished[row];
+    if (was_finished) *was_finished = fin != 0;
+    if (fin) tok = PAD_ID;
+    bk.ids[(size_t)row * bk.ld_ids + t + 1] = tok;
+    if (tok == EOS_ID) fin = 1;
+    bk.finished[row] = fin;
+    const unsigned mine = fin ? 0u : 0x10000u;
+    const unsigned old = atomicAdd(reinterpret_cast<unsigned*>(bk.sync), 1u + mine);
+    if ((old & 0xffffu) == (unsigned)(bk.S - 1)) {  // every row has been recorded
+        const unsigned unfinished = (old >> 16) + (mine >> 16);
+        if (unfinished == 0 && *bk.done_len == 0) *bk.done_len = t + 2;
+        *bk.step = t + 1;
+        bk.sync[0] = 0;
+    }
+    return tok;
+}
+#endif
+
 struct Lin {
     const float* w = nullptr;  // [N,K]
     const float* b = nullptr;  // [N]
@@ -45,7 +77,8 @@ struct LayerW {
 };
 
 struct GraphEntry {
-    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3)
+    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3),
+            // 3 = sampling step
     hipGraphExec_t exec;
     int key2 = 0, key3 = 0;
 };
@@ -72,6 +105,9 @@ struct rgrg_decoder {
     float *wide_val = nullptr, *wide_score = nullptr;   // more than 16 beams: [rows][K] row candidates, [items][num_beams * K] scores
     int* wide_tok = nullptr;
     size_t wide_cap = 0;                                 // rows * K the wide buffers were sized for
+    // sampling (decoder_sample.hip): device-side parameter block the captured step reads, log-probs [rows][max_len]
+    void* sample_prm = nullptr;
+    float* sample_lp = nullptr;
     int* h_done;  // pinned: [0] final read, [1..2] the two in-flight "all finished" polls of the greedy loop
     hipEvent_t ev_poll[2] = {nullptr, nullptr};
     // Token-id validation of the teacher-forced passes, without a host round trip.  id_error[0]: raised by the CURRENT
@@ -187,5 +223,8 @@ int launch_ln_rows(const float* x, const float* g, const float* b, float* xn, in
 int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = nullptr, const int* src = nullptr,
                  bool beam = false);
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1);
+int decode_begin(rgrg_decoder* d, void* stream);
+int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
+                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len);
 
 }  // namespace rgrg

@@ -104,15 +104,7 @@ __device__ __forceinline__ f32x4 box_encode1(const f32x4 r, const f32x4 p, float
 
 // Philox4x32-10 (Salmon et al., SC'11), first output word; counter = (element, image, stage, 0), key = the call's seed.
 __device__ __forceinline__ unsigned philox_key(unsigned c0, unsigned c1, unsigned c2, unsigned k0, unsigned k1) {
-    unsigned c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
+    return philox4x32_10_first(c0, c1, c2, 0u, k0, k1);   // common.h
 }
 
 // label of candidate i from its match code: RPN (gt_labels == NULL) 1 / 0 / -1 (custom_rpn -> assign_targets_to_anchors);

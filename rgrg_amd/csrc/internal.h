@@ -63,4 +63,13 @@ int launch_attn16_backward(const unsigned short* qkv16, const unsigned short* uk
                            const unsigned short* d_att16, const unsigned short* att16, const float* lse, unsigned short* d_qkv16,
                            float* d_ukv, int S, int H, int T, DropoutParams drop, float ukv_scale, int f16, hipStream_t st);
 
+
+// ------------------------------------------------------------------ sample.hip (the token sampler; contract: rgrg_hip.h "Sampling")
+size_t sample_params_bytes();
+// validates and writes the device-side parameter block the sample step reads (so a captured step serves every call)
+int enqueue_sample_params(void* prm_dev, float temperature, int top_k, float top_p, unsigned long long seed, hipStream_t st);
+// one decode step's draw for rows [0, S) of logits + the greedy bookkeeping (record_step_token); lp [S][ld_lp] or null
+int launch_sample_step(const float* logits, int ld, int S, int V, const void* prm_dev, long long* ids, int ld_ids, int* finished,
+                       int* step, int* done_len, int* sync, float* lp, int ld_lp, hipStream_t st);
+
 }  // namespace rgrg

@@ -1,0 +1,342 @@
+// Token sampling on the device: temperature, top-k, top-p, one inverse-CDF draw and its log-probability per logits row, in
+// ONE launch (contract: include/rgrg_hip.h "Sampling").  One 1024-thread workgroup per row.
+//
+// * Every logit is read from memory once, with 16-byte loads, and stays in registers: wave w owns the contiguous vocabulary
+//   segment [3328 w, 3328 (w + 1)), a lane holds 13 vectors of 4 (vector lane + 64 u of the segment), so a wave-load is 1 KiB
+//   contiguous and "vocabulary order" is wave -> vector u -> lane -> element: the inverse-CDF scan needs one wave's prefix only.
+// * Both filters are one routine.  With keys that order the logits DESCENDING (flipped IEEE bits, exact), "keep the tokens
+//   whose weight of strictly greater logits is <= P" is: delta = max{d : W(d) <= P}, W(d) = weight of the keys < d, keep
+//   key <= delta.  Top-k: weight 1, P = k - 1 (the k-th largest logit and everything tied with it).  Top-p: weight = the
+//   token's probability mass among the top-k set, P = top_p x total.  delta is found by a radix descent, 8 bits per pass,
+//   over a 256-bin histogram in LDS; a thread adds a RUN of equal digits with one atomic, so a peaked row, whose keys share
+//   their leading bits, does not serialise 50 000 adds on one bin.
+// * DETERMINISM: there is no floating-point atomic and no floating-point sum whose order could vary.  A token's mass is the
+//   64-bit fixed-point integer floor(2^40 exp(z - z_max)) (z_max has mass 2^40 exactly, a row's total stays below 2^56), and
+//   every accumulation of masses - histogram bins, wave and row totals, the running sums of the scan - is an integer add:
+//   integer adds commute, so the result does not depend on the order in which waves or atomics arrive.  exp is evaluated by
+//   the same expression on the same input wherever a mass is needed again, which is what lets the masses stay out of
+//   registers.  The draw compares integers: running sum > floor(w24 x total / 2^24), u = w24 2^-24.
+#include "decoder_internal.h"
+
+namespace rgrg {
+
+constexpr int SM_THREADS = 1024, SM_WAVES = 16, SM_NV = 13;
+constexpr int SM_SEG = 64 * SM_NV * 4;   // vocabulary entries per wave
+constexpr float SM_FIX = 1099511627776.0f;   // 2^40
+
+struct SampleParams {   // the device-side block a captured step reads: one graph serves every seed and parameter set
+    unsigned long long seed;
+    float inv_T;
+    int top_k;     // 0: off
+    float top_p;   // 1: off
+    int pad_;
+};
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ unsigned desc_key(float x) {   // ascending key <=> descending logit; -0 == +0
+    const unsigned b = __float_as_uint(x + 0.0f);
+    return (b & 0x80000000u) ? b : (b ^ 0x7fffffffu);
+}
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ u64 wave_scan_u64(u64 v, int lane) {   // inclusive
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 n = __shfl_up(v, o, 64);
+        if (lane >= o) v += n;
+    }
+    return v;
+}
+
+__device__ __forceinline__ float key_logit(unsigned k) {   // the inverse of desc_key
+    return __uint_as_float((k & 0x80000000u) ? k : (k ^ 0x7fffffffu));
+}
+constexpr unsigned SM_NO_TOKEN = 0xffffffffu;   // key of the slots behind the vocabulary (no finite or infinite logit maps to it)
+constexpr unsigned SM_KEEP_ALL = 0xfffffffeu;   // "no filter": every key but that one
+
+// z = fp32(x * inv_T), the contract's product: formed with __fmul_rn so that it is never contracted into the subtraction below
+__device__ __forceinline__ float token_z(unsigned k, float inv_T) { return __fmul_rn(key_logit(k), inv_T); }
+// Fixed-point mass of the token with key k: floor(2^40 exp(z - z_max)).  The ONE definition, called wherever a mass is needed
+// (histogram weights, wave totals, vector sums, the element walk): equal inputs give equal bits, which DETERMINISM above and
+// the agreement of the vector sums with the element walk rest on.
+__device__ __forceinline__ u64 token_mass(unsigned k, float inv_T, float zmax) {
+    asm volatile("" : "+v"(k));   // evaluated where it is used: the compiler otherwise keeps all 52 masses of a thread live from
+                                  // one use to the next (104 registers) and spills
+    const float z = token_z(k, inv_T);
+    const float ev = (z == zmax) ? 1.0f : expf(__fsub_rn(z, zmax));
+    return (u64)(ev * SM_FIX);
+}
+
+// A thread's 52 logits, held as their keys: the filters compare keys, and a logit is two instructions away from its key
+struct RowRegs {
+    unsigned k[SM_NV][4];
+    int base;   // vocabulary index of k[0][0]; k[u][e] is base + 256 u + e
+    float inv_T, zmax;
+    __device__ __forceinline__ u64 mass(int u, int e) const { return token_mass(k[u][e], inv_T, zmax); }
+};
+
+// delta = max{d : W(d) <= P} (see the head of the file); w(u, e) is the weight of a token that takes part, called only for
+// tokens with key <= limit
+template <class WF>
+__device__ __forceinline__ unsigned radix_threshold(const RowRegs& r, unsigned limit, u64 P, WF&& w, u64* hist, u64* sh_a,
+                                                    unsigned* sh_prefix) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned prefix = 0;
+    u64 A = 0;   // weight of the keys below the prefix
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const unsigned himask = pass ? (0xffffffffu << (shift + 8)) : 0u;
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        unsigned lim = limit;
+        asm volatile("" : "+v"(lim));   // opaque per pass: hoisting the 52 pass-invariant compares out of the loop spills their masks
+        int cur = 0;
+        u64 acc = 0;
+#pragma unroll
+        for (int u = 0; u < SM_NV; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned k = r.k[u][e];
+                if (k <= lim && (k & himask) == prefix) {
+                    const int b = (int)((k >> shift) & 255u);
+                    if (b != cur) {
+                        if (acc) atomicAdd(&hist[cur], acc);
+                        cur = b;
+                        acc = 0;
+                    }
+                    acc += w(u, e);
+                }
+            }
+        if (acc) atomicAdd(&hist[cur], acc);
+        __syncthreads();
+        if (wave == 0) {   // the largest bin b with A + (weight of the bins below b) <= P; bin 0 always qualifies
+            const u64 h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+            const u64 s = (h0 + h1) + (h2 + h3);
+            const u64 below = A + (wave_scan_u64(s, lane) - s);
+            const u64 m = __ballot(below <= P);
+            const int L = 63 - __clzll((long long)m);
+            if (lane == L) {
+                u64 a = below;
+                int b = 4 * lane;
+                if (a + h0 <= P) { a += h0; ++b;
+                    if (a + h1 <= P) { a += h1; ++b;
+                        if (a + h2 <= P) { a += h2; ++b; } } }
+                *sh_a = a;
+                *sh_prefix = prefix | ((unsigned)b << shift);
+            }
+        }
+        __syncthreads();
+        A = *sh_a;
+        prefix = *sh_prefix;
+    }
+    return prefix;
+}
+
+// logits [S][ld]; prm_dev (or, when null, prm_val) = the parameters; the Philox counter is (row0 + row, t) with t = *bk.step in
+// a decode step (bk.ids != null: the token and its log-prob go through record_step_token into ids / lp[row][t + 1]) and
+// t = step otherwise (out_tok / out_lp [S]).
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, size_t ld, int V,
+                                                            const SampleParams* __restrict__ prm_dev, SampleParams prm_val, int step,
+                                                            int row0, int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                                            StepBook bk, float* __restrict__ lp, int ld_lp) {
+    __shared__ u64 hist[256];
+    __shared__ u64 sh_w[SM_WAVES];
+    __shared__ unsigned sh_k[SM_WAVES];
+    __shared__ u64 sh_a;
+    __shared__ unsigned sh_prefix;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SampleParams prm = prm_dev ? *prm_dev : prm_val;
+    const int t = bk.ids ? *bk.step : step;
+    const float* __restrict__ x = logits + (size_t)row * ld;
+
+    RowRegs r;
+    r.base = wave * SM_SEG + lane * 4;
+    r.inv_T = prm.inv_T;
+#pragma unroll
+    for (int u = 0; u < SM_NV; ++u) {
+        const int i = r.base + 256 * u;
+        if (VEC && i + 3 < V) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r.k[u][e] = desc_key(v[e]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r.k[u][e] = (i + e < V) ? desc_key(x[i + e]) : SM_NO_TOKEN;
+        }
+    }
+    // row maximum = the smallest key (exact, any order)
+    unsigned kmin = SM_NO_TOKEN;
+#pragma unroll
+    for (int u = 0; u < SM_NV; ++u) kmin = min(min(kmin, min(r.k[u][0], r.k[u][1])), min(r.k[u][2], r.k[u][3]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o, 64));
+    if (lane == 0) sh_k[wave] = kmin;
+    __syncthreads();
+    kmin = sh_k[0];
+#pragma unroll
+    for (int w = 1; w < SM_WAVES; ++w) kmin = min(kmin, sh_k[w]);
+    r.zmax = token_z(kmin, r.inv_T);
+
+    // top-k: the k-th largest logit and its ties
+    unsigned limit = SM_KEEP_ALL;
+    if (prm.top_k == 1) limit = kmin;
+    else if (prm.top_k > 1 && prm.top_k < V)
+        limit = min(limit, radix_threshold(r, limit, (u64)(prm.top_k - 1), [](int, int) -> u64 { return 1; }, hist, &sh_a, &sh_prefix));
+
+    // masses of the kept tokens per wave -> row total
+    auto wave_totals = [&](unsigned lim) -> u64 {
+        u64 s = 0;
+#pragma unroll
+        for (int u = 0; u < SM_NV; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (r.k[u][e] <= lim) s += r.mass(u, e);
+        s = wave_sum_u64(s);
+        __syncthreads();   // the previous readers of sh_w are done
+        if (lane == 0) sh_w[wave] = s;
+        __syncthreads();
+        u64 tot = 0;
+#pragma unroll
+        for (int w = 0; w < SM_WAVES; ++w) tot += sh_w[w];
+        return tot;
+    };
+    u64 total = wave_totals(limit);
+    if (prm.top_p < 1.0f) {   // top-p on the distribution re-normalised over the top-k set
+        const u64 P = (u64)((double)total * (double)prm.top_p);
+        const unsigned dp = radix_threshold(r, limit, P, [&](int u, int e) -> u64 { return r.mass(u, e); }, hist, &sh_a, &sh_prefix);
+        limit = dp < limit ? dp : limit;
+        total = wave_totals(limit);
+    }
+
+    // the draw: first kept token, in vocabulary order, whose running mass exceeds u x total.  top_k == 1: the first kept token
+    // (first-occurrence arg-max, what greedy returns)
+    const unsigned rr = (unsigned)(row0 + row);
+    const unsigned w24 = prm.top_k == 1 ? 0u
+                                        : philox4x32_10_first(rr, (unsigned)t, 0u, 0u, (unsigned)prm.seed, (unsigned)(prm.seed >> 32)) >> 8;
+    const u64 T = (__umul64hi(total, (u64)w24) << 40) | ((total * (u64)w24) >> 24);   // floor(w24 total / 2^24) < total
+    u64 run = 0;
+    int wsel = 0;
+#pragma unroll
+    for (int w = 0; w < SM_WAVES; ++w) {
+        const bool before = run + sh_w[w] <= T;   // the crossing is behind wave w
+        if (before && wsel == w) { run += sh_w[w]; wsel = w + 1; }
+    }
+    if (wave != wsel) return;   // (wsel < SM_WAVES: the running mass reaches total > T)
+    u64 s[SM_NV];
+#pragma unroll
+    for (int u = 0; u < SM_NV; ++u) {
+        s[u] = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (r.k[u][e] <= limit) s[u] += r.mass(u, e);
+    }
+    int usel = 0;
+    u64 lane_s = 0;
+    bool open = true;
+#pragma unroll
+    for (int u = 0; u < SM_NV; ++u) {
+        const u64 c = wave_sum_u64(s[u]);
+        if (open) {
+            if (run + c <= T) run += c;
+            else { open = false; usel = u; lane_s = s[u]; }
+        }
+    }
+    const u64 incl = run + wave_scan_u64(lane_s, lane);
+    const u64 hit = __ballot(incl > T);
+    const int L = __ffsll((long long)hit) - 1;
+    if (lane != L) return;
+    u64 c = incl - lane_s;
+    unsigned kv[4];
+#pragma unroll
+    for (int u = 0; u < SM_NV; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (u == 0 || u == usel) kv[e] = r.k[u][e];
+    // The lane's kept tokens sum to lane_s (token_mass both times) and c + lane_s = incl > T, so the walk crosses T at one of
+    // them; should it ever not, the lane's LAST kept token is taken - a kept token, never an index outside the kept set.
+    int tok = 0;
+    unsigned ksel = SM_NO_TOKEN;
+    bool found = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (!found && kv[e] <= limit) {
+            c += token_mass(kv[e], r.inv_T, r.zmax);
+            tok = r.base + 256 * usel + e;
+            ksel = kv[e];
+            found = c > T;
+        }
+    const float z = token_z(ksel, r.inv_T);
+    // log q(token) under the distribution it was drawn from
+    // (one lane, once per row: in double, so that the fp32 result carries one rounding and not those of z - z_max, of the
+    // conversion of the total and of logf - together 2 ulp, measured against the float64 reference)
+    const double logq_d = ((z == r.zmax) ? 0.0 : ((double)z - (double)r.zmax)) - (log((double)total) - 40.0 * 0.6931471805599453);
+    const float logq = (float)logq_d;
+    if (bk.ids) {
+        bool was_finished;
+        record_step_token(bk, row, t, tok, &was_finished);
+        if (lp) lp[(size_t)row * ld_lp + t + 1] = was_finished ? 0.0f : logq;
+    } else {
+        out_tok[row] = tok;
+        if (out_lp) out_lp[row] = logq;
+    }
+}
+
+static int launch_sample(const float* logits, size_t ld, int S, int V, const SampleParams* prm_dev, SampleParams prm_val, int step,
+                         int row0, int* out_tok, float* out_lp, StepBook bk, float* lp, int ld_lp, hipStream_t st) {
+    RGRG_CHECK_ARG(logits && S > 0 && V > 0 && V <= SM_WAVES * SM_SEG && ld >= (size_t)V);
+    const bool vec = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(S), dim3(SM_THREADS), 0, st, logits, ld, V, prm_dev, prm_val, step, row0, out_tok,
+                           out_lp, bk, lp, ld_lp);
+    else
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(S), dim3(SM_THREADS), 0, st, logits, ld, V, prm_dev, prm_val, step, row0, out_tok,
+                           out_lp, bk, lp, ld_lp);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+__global__ void sample_set_params_kernel(SampleParams* dst, SampleParams v) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
+}
+
+static int check_sample_args(float temperature, int top_k, float top_p) {
+    RGRG_CHECK_ARG(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.0f);
+    return RGRG_OK;
+}
+
+size_t sample_params_bytes() { return sizeof(SampleParams); }
+
+int enqueue_sample_params(void* prm_dev, float temperature, int top_k, float top_p, unsigned long long seed, hipStream_t st) {
+    int rc = check_sample_args(temperature, top_k, top_p);
+    if (rc) return rc;
+    const SampleParams v{seed, 1.0f / temperature, top_k, top_p, 0};
+    hipLaunchKernelGGL(sample_set_params_kernel, dim3(1), dim3(64), 0, st, static_cast<SampleParams*>(prm_dev), v);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+int launch_sample_step(const float* logits, int ld, int S, int V, const void* prm_dev, long long* ids, int ld_ids, int* finished,
+                       int* step, int* done_len, int* sync, float* lp, int ld_lp, hipStream_t st) {
+    RGRG_CHECK_ARG(prm_dev && ids && finished && step && done_len && sync);
+    const StepBook bk{ids, ld_ids, finished, step, done_len, sync, S};
+    return launch_sample(logits, (size_t)ld, S, V, static_cast<const SampleParams*>(prm_dev), SampleParams{}, 0, 0, nullptr, nullptr, bk,
+                         lp, ld_lp, st);
+}
+
+}  // namespace rgrg
+
+using namespace rgrg;
+
+extern "C" int rgrg_sample_logits_f32(const float* logits, int64_t ld, int S, int V, float temperature, int top_k, float top_p,
+                                      uint64_t seed, int step, int row0, int* out_tok, float* out_logprob, void* stream) {
+    RGRG_CHECK_ARG(out_tok && ld > 0 && step >= 0 && row0 >= 0);
+    int rc = check_sample_args(temperature, top_k, top_p);
+    if (rc) return rc;
+    const SampleParams v{seed, 1.0f / temperature, top_k, top_p, 0};
+    return launch_sample(logits, (size_t)ld, S, V, nullptr, v, step, row0, out_tok, out_logprob, StepBook{}, nullptr, 0, as_stream(stream));
+}

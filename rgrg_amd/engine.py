@@ -725,6 +725,47 @@ class HipEngine:
                    "rgrg_decoder_generate")
         return out[:, :out_len.value].contiguous()
 
+    def sample_decode(self, feats: Tensor, max_length: Optional[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                      seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True) -> Tuple[Tensor, Tensor]:
+        """LanguageModel.sample: feats [S,1024] -> (ids int64 [S*n, L'], log-probs f32 [S*n, L']); n = num_return_sequences
+        hypotheses per row are decoded as S*n rows with ``feats`` repeated row-wise (output row s*n + j, the order beam search
+        uses).  Row r draws step t from the Philox counter (r, t) under ``seed`` (include/rgrg_hip.h "Sampling")."""
+        _require_gpu(feats.device)
+        n = int(num_return_sequences)
+        feats = feats.to(torch.float32)
+        if n > 1:
+            feats = feats.repeat_interleave(n, dim=0)
+        feats = feats.contiguous()
+        S = feats.shape[0]
+        limit = int(max_length) if max_length else 1024
+        dec = self._get_decoder(S, limit)
+        self._cached = None   # as in greedy_decode
+        _hip.check(self.lib.rgrg_decoder_set_precision(dec, int(bf16)), "rgrg_decoder_set_precision")
+        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
+        lp = torch.empty((S, limit), dtype=torch.float32, device=feats.device)
+        out_len = C.c_int(0)
+        _hip.check(self.lib.rgrg_decoder_sample(dec, _hip.ptr(feats), S, limit, float(temperature), int(top_k), float(top_p),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(out), limit, _hip.ptr(lp), C.byref(out_len),
+                                                1 if use_graph else 0, self._s()),
+                   "rgrg_decoder_sample")
+        return out[:, :out_len.value].contiguous(), lp[:, :out_len.value].contiguous()
+
+    def sample_logits(self, logits: Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                      step: int = 0, row0: int = 0, ld: Optional[int] = None, vocab: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+        """The decoder's sampler on caller-provided fp32 logits [S, ld] (the first ``vocab`` columns of a row are the logits):
+        -> (tokens int32 [S], log-probs f32 [S]); row s draws with the Philox counter (row0 + s, step)."""
+        _require_gpu(logits.device)
+        assert logits.dtype == torch.float32 and logits.dim() == 2
+        S = logits.shape[0]
+        ld = int(logits.shape[1]) if ld is None else int(ld)
+        V = ld if vocab is None else int(vocab)
+        tok = torch.empty((S,), dtype=torch.int32, device=logits.device)
+        lp = torch.empty((S,), dtype=torch.float32, device=logits.device)
+        _hip.check(self.lib.rgrg_sample_logits_f32(_hip.ptr(logits), ld, S, V, float(temperature), int(top_k), float(top_p),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(row0), _hip.ptr(tok), _hip.ptr(lp),
+                                                   self._s()), "rgrg_sample_logits_f32")
+        return tok, lp
+
     def beam_search(self, feats: Tensor, max_length: int, num_beams: int, early_stopping: bool = False,
                     length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1) -> Tensor:
         """LanguageModel.generate(num_beams>1): feats [S,1024] -> int64 [S * num_return_sequences, L]."""

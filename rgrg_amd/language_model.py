@@ -101,6 +101,18 @@ class _TeacherForcedLoss(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(g * grad_out for g in ctx.grads)
 
 
+def check_sample_args(temperature, top_k, top_p, num_return_sequences) -> None:
+    """Argument errors of ``sample`` (LanguageModel, ReportGenerationModel): raised before any GPU work."""
+    if not temperature > 0:
+        raise ValueError(f"temperature has to be > 0, but is {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k has to be a non-negative integer (0 = off), but is {top_k}")
+    if not (0 < top_p <= 1):
+        raise ValueError(f"top_p has to be in (0, 1], but is {top_p}")
+    if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+        raise ValueError(f"num_return_sequences has to be a positive integer, but is {num_return_sequences}")
+
+
 class LanguageModel(EngineOwner):
     _engine_prefix = "language_model."
 
@@ -233,6 +245,28 @@ class LanguageModel(EngineOwner):
         logits, _ = self.engine().lm_forward(image_hidden_states, input_ids, attention_mask, want_logits=True, want_loss=False,
                                              position_ids=position_ids)
         return logits
+
+    @torch.no_grad()
+    def sample(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, *, temperature: float = 1.0,
+               top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
+               return_logprobs: bool = False):
+        """Draws from the model's distribution instead of its arg-max (``generate`` keeps raising for ``do_sample=True``, as the
+        reference does): int64 ids [S*n, L'] incl. the leading BOS, rows s*n + j for the n = num_return_sequences hypotheses
+        of input row s; with ``return_logprobs`` also fp32 [S*n, L'], the log-probability of every token under the
+        distribution it was drawn from (0 for BOS and for the PAD of finished rows).  temperature > 0; top_k >= 0 (0 = off)
+        and 0 < top_p <= 1 (1 = off) are HF 4.19.2's warpers, top-k first, tied logits kept or dropped together
+        (include/rgrg_hip.h "Sampling").  ``seed=None`` draws the seed from torch's CPU generator (``torch.manual_seed``
+        governs it); the same seed gives the same ids.  torch.autocast opts into the 16-bit modes as for ``generate``."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        from .engine import _require_gpu
+        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
+        self.sync_trainable_if_stale()
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        low = _hip.autocast_mode()
+        ids, logprobs = self.engine().sample_decode(image_hidden_states, max_length, temperature, int(top_k), top_p, int(seed),
+                                                    int(num_return_sequences), bf16=low)
+        return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
     def generate(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, num_beams: int = 1,

@@ -14,7 +14,7 @@ from torch import Tensor
 from . import _hip
 from ._owner import EngineOwner
 from .binary_classifier import BinaryClassifierRegionAbnormal, BinaryClassifierRegionSelection
-from .language_model import LanguageModel
+from .language_model import LanguageModel, check_sample_args
 from .object_detector import ObjectDetector
 
 _LM = "language_model."
@@ -188,3 +188,21 @@ class ReportGenerationModel(EngineOwner):
                                                   do_sample, num_return_sequences, early_stopping)
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def sample(self, images: torch.FloatTensor, max_length: int = None, *, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None, return_logprobs: bool = False):
+        """``generate`` with the sentences drawn by ``LanguageModel.sample``: the same 4-tuple (``output_ids`` replaced by the
+        sampler's return: ids, or (ids, logprobs) with ``return_logprobs``) and the same ``-1`` when no region is selected."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        output = self.language_model.sample(selected_region_features, max_length, temperature=temperature, top_k=top_k, top_p=top_p,
+                                            num_return_sequences=num_return_sequences, seed=seed, return_logprobs=return_logprobs)
+        del selected_region_features
+        return output, selected_regions, detections, class_detected
