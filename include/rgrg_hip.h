@@ -228,6 +228,18 @@ int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num
  * 0 = fp32.  NOT bit-exact with the fp32 reference; the <= 128-sequence decode path (launch-latency bound) always stays
  * fp32.  May allocate and synchronise (a change of the 16-bit type re-converts the weight copies). */
 int rgrg_decoder_set_precision(rgrg_decoder* d, int mode);
+/* Opt-in 8-bit K/V cache for the many-sequence decode step: fmt 1 keeps the cache as plain OCP e4m3fn bytes (no scales)
+ * WHEREVER THE 16-BIT CACHE WOULD BE USED - precision mode 1 / 2 with more rows than rgrg_decoder_row_limit(), in
+ * rgrg_decoder_generate / _sample / _beam_search; fmt 0 (default): the cache follows the precision mode.  Anything else is
+ * RGRG_EINVAL.  fp32 mode, the fused plans of <= row-limit rows, rgrg_decoder_forward_cached and the teacher-forced passes are
+ * not affected by the setting.  k / v (and the image key / value of slot 0) are clamped to +-448 and rounded ONCE from fp32 to
+ * nearest even; the softmax, the accumulation and the output stay as in the 16-bit mode (what the reference's
+ * GPT2PseudoAttention does with `present`, src/language_model/language_model.py:162-166, in a narrower storage type).  The setting
+ * survives rgrg_decoder_set_precision; a change drops the captured step graphs and invalidates rgrg_decoder_copy_last_logits. */
+int rgrg_decoder_set_kv_format(rgrg_decoder* d, int fmt);
+/* The cache format a decode step over `rows` token rows uses in the decoder's current modes: 0 fp32, 1 bf16, 2 fp16, 3 e4m3
+ * (-1 for a null handle or rows <= 0). */
+int rgrg_decoder_kv_format_in_use(rgrg_decoder* d, int rows);
 /* Replaces LanguageModel.forward(input_ids, attention_mask, image_hidden_states, return_loss, use_cache=False)
  * in eval mode (src/language_model/language_model.py:258-399): one teacher-forced pass over
  * T tokens per sequence - feature_space_transformation_nn, wte[ids] + wte[arange(T)] (:298-307), 24 blocks of
@@ -414,6 +426,13 @@ int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t* Wb, const 
 int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
                            uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int kv16, int fp16,
                            int ni, int frag_out, int max_workgroups, void* stream);
+/* rgrg_debug_attn_decode_kv8: the same step on an e4m3 cache (rgrg_decoder_set_kv_format), attn_decode_kv8_wave_kernel<src, fp16>:
+ * kcache / vcache [S][H][T_slots][64] BYTES; the new k / v are stored to slot t + 1 as clamp(+-448) + one rounding to nearest even;
+ * the result goes to out16 (fp16 = 0 bf16 / 1 IEEE half) when given, else to out (fp32); max_workgroups > 0 caps the grid.
+ *   RGRG_EINVAL: kmask, H % 4, a plane of 2 GiB or more. */
+int rgrg_debug_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kcache, uint8_t* vcache, const int* step_dev, float* out,
+                               uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int fp16,
+                               int max_workgroups, void* stream);
 /* rgrg_debug_attn_prefill: the attention without layer_past over T tokens (:135-157, :84-122) of rgrg_decoder_lm_forward and
  * the forward half of rgrg_decoder_lm_loss_grad.  qkv [S*T][3*H*64]; ukv [S][ld_ukv], image key at column kcol, image value at
  * kcol + H*64; am [S][T] or NULL; out f32 [S*T][H*64]; out16 (optional) the same as 16 bit; lse (optional) [S*T][H];
@@ -492,7 +511,7 @@ int rgrg_decoder_copy_last_logits(rgrg_decoder* d, float* dst, int S, void* stre
  * decode step for S token rows as the step would launch them, (b) its 24 single-query attention launches at `nkeys`
  * keys per sequence, each family between one pair of HIP events on the decoder's stream.  Returns total ms of each,
  * the algorithmic flops and weight bytes of the GEMMs of ONE step, the K/V cache bytes ONE step reads at `nkeys`
- * keys (24 x 2 x S x 1024 x nkeys x element size), and the GEMM launches per step.  Call after a generate() so that
+ * keys (24 x 2 x S x 1024 x nkeys x element size - 1 byte when the e4m3 cache is in force), and the GEMM launches per step.  Call after a generate() so that
  * the decoder exists in the wanted precision mode.  one_range != 0: every launch covers all S rows (each kernel alone on the
  * GPU at the step's full size - what a serialising profiler sees of a 1-range step); 0: as the step launches them (the
  * many-sequence 16-bit step runs as concurrent row ranges on forked streams, whose launches overlap). */

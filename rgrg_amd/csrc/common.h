@@ -91,6 +91,18 @@ __device__ __forceinline__ float from16(unsigned h) {
 }
 __device__ __forceinline__ unsigned to16_rt(float f, int f16) { return f16 ? f32_to_f16_bits(f) : f32_to_bf16_bits(f); }
 __device__ __forceinline__ float from16_rt(unsigned h, int f16) { return f16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h); }
+// OCP e4m3fn, the opt-in 8-bit K/V cache (attn_kv8.hip, kv_slot0_kernel): fp32 -> e4m3 is ONE rounding to nearest even of the fp32
+// value (v_cvt_pk_fp8_f32; never through the 16-bit type), clamped to +-448 in fp32 first so that the result does not depend on the
+// instruction's overflow rule and a finite input never becomes NaN.  Byte i of a word = element i (memory order).
+__device__ __forceinline__ float e4m3_clamp(float f) { return fminf(fmaxf(f, -448.0f), 448.0f); }
+__device__ __forceinline__ unsigned f32x4_to_e4m3_bits(float a, float b, float c, float d) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(a), e4m3_clamp(b), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(c), e4m3_clamp(d), w, true);
+    return (unsigned)w;
+}
+__device__ __forceinline__ unsigned f32_to_e4m3_bits(float f) {
+    return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(f), 0.0f, 0, false) & 0xffu;
+}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

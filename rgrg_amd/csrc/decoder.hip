@@ -734,7 +734,7 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
 }
 
 // image key/value (uk/uv outputs) -> cache slot 0 of every layer
-template <typename KV>  // float, or u16 (bf16 cache)
+template <typename KV>  // float, u16 (16-bit cache) or uint8_t (e4m3 cache: clamp and one rounding, common.h)
 __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__ ukv, int ld, KV* __restrict__ kv_all,
                                                        size_t layer_stride, size_t kv_stride, int S, int H, int T,
                                                        int L, int row_mul, int f16) {
@@ -749,7 +749,8 @@ __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__
         const int hd = d >> 6, e = d & 63;
         const float val = ukv[(size_t)s * ld + ((size_t)l * 2 + kv) * D + d];
         const size_t o = (size_t)l * layer_stride + (size_t)kv * kv_stride + (((size_t)s * row_mul * H + hd) * T) * 64 + e;
-        if constexpr (sizeof(KV) == 2) kv_all[o] = (KV)to16_rt(val, f16);
+        if constexpr (sizeof(KV) == 1) kv_all[o] = (KV)f32_to_e4m3_bits(val);
+        else if constexpr (sizeof(KV) == 2) kv_all[o] = (KV)to16_rt(val, f16);
         else kv_all[o] = val;
     }
 }
@@ -995,6 +996,11 @@ static int skinny_max_rows16(bool w16) {
 }
 static int decode_row_limit(const rgrg_decoder* d) { return d->bf16_gemms ? skinny_max_rows16(d->w16_fused) : skinny_max_rows(); }
 static bool kv_is_bf16(const rgrg_decoder* d, int rows) { return d->bf16_gemms && rows > decode_row_limit(d); }
+// ... and what that step's cache holds: e4m3 bytes replace the 16-bit type where rgrg_decoder_set_kv_format asked for them
+static KvFormat kv_format(const rgrg_decoder* d, int rows) {
+    if (!kv_is_bf16(d, rows)) return KV_F32;
+    return d->kv8 ? KV_E4M3 : (d->f16() ? KV_F16 : KV_BF16);
+}
 
 // Y[:M] = act(X W^T + b + R).  Prefill GEMMs (packed, <= 128 rows): LDS-staged weight-streaming kernel (+ a small
 // reduce kernel when the layer splits K over workgroups); everything else: tiled MFMA GEMM (fp32, or the bf16-weight
@@ -1071,35 +1077,45 @@ static bool lm_head_cand_path(const rgrg_decoder* d, int S) {
 // it from the decoder object, the test hook rgrg_debug_attn_decode from its arguments - the rules exist once, here.
 struct AttnDecodeLaunch {
     const float* qkv; int ld_qkv;          // [S][ld_qkv]: q | k | v of the current token, D floats each
-    void *kc, *vc;                         // K / V plane [rows][H][T][64]: fp32, or 16 bit (kv16)
-    size_t plane_elems;                    // elements of one plane (kv16: bounds the 32-bit byte offsets of the buffer loads)
+    void *kc, *vc;                         // K / V plane [rows][H][T][64]: fp32, 16 bit or e4m3 bytes (fmt)
+    size_t plane_elems;                    // elements of one plane (16 bit / e4m3: bounds the 32-bit byte offsets of the buffer loads)
     const int* step;
     float* out; unsigned short* out16;
     int S, H, T;
     const int* src;                        // beam search: [S][T] ancestor table, or NULL
     const float* kmask;                    // [S][T] additive padding mask of the cache slots, or NULL (fp32 kernel without src only)
-    int kv16, f16;
+    KvFormat fmt;                          // KV_F32, KV_BF16 / KV_F16 (one kernel; the type is f16), KV_E4M3
+    int f16;                               // the 16-bit type of a 16-bit cache and of out16 (0 bf16, 1 fp16)
     int ni;                                // fp32 kernel: 9 / 2 keys per group and chunk; 0 = S * H <= 4096 ? 9 : 2
     int frag_out;
-    int max_wgs;                           // kv16 kernel: > 0 caps the grid, each wave then walks several (sequence, head) items
+    int max_wgs;                           // wave kernels (16 bit, e4m3): > 0 caps the grid, each wave then walks several (sequence, head) items
     hipStream_t st;
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
-    if (a.kmask && (a.kv16 || a.src)) {
+    if (a.kmask && (a.fmt != KV_F32 || a.src)) {
         set_error("decode attention: the padding mask exists only in the fp32 kernel without an ancestor table (%s)",
-                  a.kv16 ? "16-bit K/V cache" : "beam search");
+                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.fmt != KV_F32 ? "16-bit K/V cache" : "beam search");
         return RGRG_EINVAL;
     }
-    if (a.kv16) {
+    if (a.fmt != KV_F32) {
         // one wave per (sequence, head); the cache rows are addressed with 32-bit byte offsets into one layer's K (V)
-        // plane through a buffer descriptor, which bounds a plane at 2 GiB (8128 sequences at max_length 128)
-        if ((a.H & 3) != 0 || a.plane_elems * sizeof(u16) >= ((size_t)1 << 31)) {
-            set_error("decoder: the bf16 K/V cache plane of one layer (%zu bytes) exceeds the 2 GiB the attention kernel addresses: "
-                      "lower the batch or max_length", a.plane_elems * sizeof(u16));
+        // plane through a buffer descriptor, which bounds a plane at 2 GiB (8128 sequences at max_length 128 in 16 bit)
+        const size_t plane_bytes = a.plane_elems * (a.fmt == KV_E4M3 ? 1 : sizeof(u16));
+        if ((a.H & 3) != 0) {
+            set_error("decode attention: %d heads - the %s K/V cache kernel takes 4 heads per workgroup, the head count must be a multiple of 4",
+                      a.H, a.fmt == KV_E4M3 ? "e4m3" : "16-bit");
+            return RGRG_EINVAL;
+        }
+        if (plane_bytes >= ((size_t)1 << 31)) {
+            set_error("decoder: the %s K/V cache plane of one layer (%zu bytes) exceeds the 2 GiB the attention kernel addresses: "
+                      "lower the batch or max_length", a.fmt == KV_E4M3 ? "e4m3" : "16-bit", plane_bytes);
             return RGRG_EINVAL;
         }
         const int wgs = a.S * a.H / 4;
         const dim3 wgrid(a.max_wgs > 0 ? std::min(wgs, a.max_wgs) : wgs), wblk(256);
+        if (a.fmt == KV_E4M3)
+            return launch_attn_decode_kv8(a.qkv, a.ld_qkv, static_cast<uint8_t*>(a.kc), static_cast<uint8_t*>(a.vc), a.step, a.out, a.out16,
+                                          a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
 #define KV16_LAUNCH(SRC_, F16_) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<SRC_, F16_>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
                                                   static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.out16)
         if (a.src) { if (a.f16) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
@@ -1128,12 +1144,16 @@ static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsig
     AttnDecodeLaunch a{};
     a.ld_qkv = 3 * D; a.step = d->step; a.S = S; a.H = d->H; a.T = d->T; a.src = src; a.kmask = d->key_mask_cur;
     a.frag_out = frag_out; a.st = d->stream; a.plane_elems = d->kv_kv_stride;
-    if (kv_is_bf16(d, S)) {
+    a.fmt = kv_format(d, S);
+    if (a.fmt != KV_F32) {
         // RGRG_ATTN_WGS_PER_CU = n > 0: at most n * 256 workgroups, each wave walks several (sequence, head) items
         static const int cap = [] { const char* e = getenv("RGRG_ATTN_WGS_PER_CU"); return e ? atoi(e) : 0; }();
-        u16* kc16r = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride + (size_t)r0 * d->H * d->T * 64;   // cache rows of sequence r0 (layout [sequence][head][slot][64])
-        a.kv16 = 1; a.f16 = d->f16(); a.max_wgs = cap > 0 ? cap * 256 : 0;
-        a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kc16r; a.vc = kc16r + d->kv_kv_stride;
+        // cache rows of sequence r0 (layout [sequence][head][slot][64]): every format lives in the same allocation with the same
+        // ELEMENT strides, so the byte offset of a plane / of row r0 scales with the element size
+        const size_t esz = a.fmt == KV_E4M3 ? 1 : sizeof(u16);
+        unsigned char* kcr = reinterpret_cast<unsigned char*>(d->kv) + ((size_t)l * d->kv_layer_stride + (size_t)r0 * d->H * d->T * 64) * esz;
+        a.f16 = d->f16(); a.max_wgs = cap > 0 ? cap * 256 : 0;
+        a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kcr; a.vc = kcr + d->kv_kv_stride * esz;
         a.out = d->att + (size_t)r0 * D; a.out16 = att16;
     } else {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
@@ -1426,8 +1446,12 @@ int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
     if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, S, D, RGRG_ACT_NONE, false))) return rc;
     // uk / uv of all layers in one GEMM, then scatter to cache slot 0
     if ((rc = linear(d, d->ukv, d->img, nullptr, d->ukv_out, S, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
-    // the bf16 cache lives in the same allocation with the same ELEMENT strides (half the bytes used)
-    if (kv_is_bf16(d, S * row_mul))
+    // the 16-bit / e4m3 cache lives in the same allocation with the same ELEMENT strides (half / a quarter of the bytes used)
+    const KvFormat fmt = kv_format(d, S * row_mul);
+    if (fmt == KV_E4M3)
+        hipLaunchKernelGGL(kv_slot0_kernel<uint8_t>, dim3(1024), dim3(256), 0, st, d->ukv_out, d->ld_ukv,
+                           reinterpret_cast<uint8_t*>(d->kv), d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, 0);
+    else if (fmt != KV_F32)
         hipLaunchKernelGGL(kv_slot0_kernel<u16>, dim3(1024), dim3(256), 0, st, d->ukv_out, d->ld_ukv,
                            reinterpret_cast<u16*>(d->kv), d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, d->f16());
     else
@@ -1822,8 +1846,21 @@ extern "C" int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache
     AttnDecodeLaunch a{};
     a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
     a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.src = src; a.kmask = kmask;
-    a.kv16 = kv16 ? 1 : 0; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.frag_out = frag_out ? 1 : 0; a.max_wgs = max_workgroups;
+    a.fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.frag_out = frag_out ? 1 : 0; a.max_wgs = max_workgroups;
     a.st = as_stream(stream);
+    return launch_attn_decode(a);
+}
+
+// Test hook: the same launcher on an e4m3 cache (attn_decode_kv8_wave_kernel): K / V planes of bytes, out (fp32) or out16 (bf16 / fp16 by
+// `fp16`), exactly as launch_attention fills it for a decoder in that format.
+extern "C" int rgrg_debug_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kcache, uint8_t* vcache, const int* step_dev, float* out,
+                                          uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int fp16,
+                                          int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && step_dev && S > 0 && H > 0 && T_slots >= 2 && ld_qkv >= 3 * H * 64 && (out || out16));
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.src = src; a.kmask = kmask;
+    a.fmt = KV_E4M3; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream);
     return launch_attn_decode(a);
 }
 
@@ -1953,6 +1990,20 @@ static int set_precision_impl(rgrg_decoder* d, int mode) {
     d->graphs.clear();
     return RGRG_OK;
 }
+
+extern "C" int rgrg_decoder_set_kv_format(rgrg_decoder* d, int fmt) {
+    RGRG_CHECK_ARG(d && (fmt == 0 || fmt == 1));
+    if (fmt == d->kv8) return RGRG_OK;
+    RGRG_HIP(hipStreamSynchronize(d->stream));
+    d->kv8 = fmt;
+    d->logits_valid = false;
+    // captured graphs bake the attention kernel and the cache addresses in: drop them
+    for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);
+    d->graphs.clear();
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_kv_format_in_use(rgrg_decoder* d, int rows) { return d && rows > 0 ? (int)kv_format(d, rows) : -1; }
 
 extern "C" int rgrg_decoder_copy_last_logits(rgrg_decoder* d, float* dst, int S, void* stream) {
     RGRG_CHECK_ARG(d && dst && S > 0 && S <= d->max_seqs);
@@ -2142,7 +2193,7 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     *ms_attn = ta;
     if (gemm_flops) *gemm_flops = d->gemm_flops_per_step;
     if (gemm_weight_bytes) *gemm_weight_bytes = (double)d->gemm_bytes_per_step;
-    if (kv_bytes) *kv_bytes = (double)d->n_layer * 2.0 * S * D * nkeys * (bf ? 2.0 : 4.0);
+    if (kv_bytes) *kv_bytes = (double)d->n_layer * 2.0 * S * D * nkeys * (kv_format(d, S) == KV_E4M3 ? 1.0 : bf ? 2.0 : 4.0);
     if (gemm_launches) *gemm_launches = d->gemm_launches_per_step;
     return RGRG_OK;
 }

@@ -13,6 +13,10 @@ constexpr int PAD_ROWS = 32;
 constexpr int SKINNY_MAX_ROWS = 128;  // 4 row tiles of 32 sequences per weight-streaming launch (RGRG_SKINNY_MAX_ROWS)
 constexpr int BOS_ID = 50256, EOS_ID = 50256, PAD_ID = 50256;
 constexpr int BEAM_K = 32;  // max 2*num_beams candidates per row (num_beams <= 16)
+// What a decode step keeps its K/V cache in (rgrg_decoder_kv_format_in_use returns these values): fp32, the 16-bit type of the
+// precision mode, or - opt-in, wherever the 16-bit cache would be used - OCP e4m3fn bytes (attn_kv8.hip)
+enum KvFormat { KV_F32 = 0, KV_BF16 = 1, KV_F16 = 2, KV_E4M3 = 3 };
+constexpr int KV8_CHUNK_KEYS = 144;   // keys of a full chunk of attn_decode_kv8_wave_kernel (9 loads x 16 groups)
 
 // The bookkeeping of one greedy_search step (:629-650) for one row, run by ONE thread of the row's workgroup: a finished row
 // takes PAD, the token goes to ids[row][t + 1], EOS finishes the row, and the LAST row to arrive records the first length
@@ -204,6 +208,8 @@ struct rgrg_decoder {
     // enqueue_step: extra streams + fork / join events of the multi-range many-sequence step (RGRG_DECODE_CHAINS)
     hipStream_t streams_x[rgrg::MAX_CHAINS - 1] = {};
     hipEvent_t ev_fork = nullptr, ev_join[rgrg::MAX_CHAINS - 1] = {};
+    int kv8 = 0;      // rgrg_decoder_set_kv_format: 1 = the many-sequence 16-bit step keeps its K/V cache as e4m3 bytes (attn_kv8.hip); survives
+                      // precision changes and has no effect where the cache is fp32 (fp32 mode, the fused plans, forward_cached)
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
                       // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
@@ -224,6 +230,9 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = n
                  bool beam = false);
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1);
 int decode_begin(rgrg_decoder* d, void* stream);
+// attn_kv8.hip: attn_decode_kv8_wave_kernel on `workgroups` workgroups of 4 waves (grid and argument rules: launch_attn_decode)
+int launch_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kc, uint8_t* vc, const int* step, float* out, unsigned short* out16,
+                           int S, int H, int T, const int* src, int f16, int workgroups, hipStream_t st);
 int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
                     int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len);
 

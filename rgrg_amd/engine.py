@@ -707,16 +707,32 @@ class HipEngine:
             self._decoder, self._decoder_caps, self._kv = h, (cap_s, cap_l), kv
         return self._decoder
 
-    def greedy_decode(self, feats: Tensor, max_length: Optional[int], use_graph: bool = True, bf16=False) -> Tensor:
+    def _set_modes(self, dec, bf16, kv_fp8: bool) -> None:
+        """Precision mode and K/V cache format of the decode call that follows (the decoder object may be a new one)."""
+        _hip.check(self.lib.rgrg_decoder_set_precision(dec, int(bf16)), "rgrg_decoder_set_precision")
+        _hip.check(self.lib.rgrg_decoder_set_kv_format(dec, 1 if kv_fp8 else 0), "rgrg_decoder_set_kv_format")
+
+    def kv_format_in_use(self, rows: int) -> int:
+        """What a decode step over ``rows`` token rows keeps its K/V cache in, in the modes the last decode call set:
+        0 fp32, 1 bf16, 2 fp16, 3 e4m3 (rgrg_decoder_kv_format_in_use).  ``rows`` must be positive (ValueError)."""
+        if self._decoder is None:
+            raise RuntimeError("no decoder yet: call generate() / sample() first")
+        fmt = int(self.lib.rgrg_decoder_kv_format_in_use(self._decoder, int(rows)))
+        if fmt < 0:
+            raise ValueError(f"kv_format_in_use: rows must be positive, got {rows}")
+        return fmt
+
+    def greedy_decode(self, feats: Tensor, max_length: Optional[int], use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.generate(num_beams=1): feats [S,1024] -> int64 [S, L'].  bf16 = precision mode (opt-in through
         torch.autocast: False / 0 fp32, True / 1 bfloat16, 2 float16): lets the > 128-sequence path use 16-bit-weight MFMA GEMMs
-        and a 16-bit K/V cache of that type (not bit-exact)."""
+        and a 16-bit K/V cache of that type (not bit-exact).  kv_fp8: that cache holds e4m3 bytes instead (no effect where the
+        cache is fp32: without autocast, or at <= rgrg_decoder_row_limit() rows)."""
         _require_gpu(feats.device)
         S = feats.shape[0]
         limit = int(max_length) if max_length else 1024  # reference has no bound when None; positions stop at 1024
         dec = self._get_decoder(S, limit)
         self._cached = None   # the K/V cache and the step counter are rewritten: presents of an earlier forward(use_cache=True) are stale
-        _hip.check(self.lib.rgrg_decoder_set_precision(dec, int(bf16)), "rgrg_decoder_set_precision")
+        self._set_modes(dec, bf16, kv_fp8)
         feats = feats.to(torch.float32).contiguous()
         out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
         out_len = C.c_int(0)
@@ -726,7 +742,8 @@ class HipEngine:
         return out[:, :out_len.value].contiguous()
 
     def sample_decode(self, feats: Tensor, max_length: Optional[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-                      seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True) -> Tuple[Tensor, Tensor]:
+                      seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True,
+                      kv_fp8: bool = False) -> Tuple[Tensor, Tensor]:
         """LanguageModel.sample: feats [S,1024] -> (ids int64 [S*n, L'], log-probs f32 [S*n, L']); n = num_return_sequences
         hypotheses per row are decoded as S*n rows with ``feats`` repeated row-wise (output row s*n + j, the order beam search
         uses).  Row r draws step t from the Philox counter (r, t) under ``seed`` (include/rgrg_hip.h "Sampling")."""
@@ -740,7 +757,7 @@ class HipEngine:
         limit = int(max_length) if max_length else 1024
         dec = self._get_decoder(S, limit)
         self._cached = None   # as in greedy_decode
-        _hip.check(self.lib.rgrg_decoder_set_precision(dec, int(bf16)), "rgrg_decoder_set_precision")
+        self._set_modes(dec, bf16, kv_fp8)
         out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
         lp = torch.empty((S, limit), dtype=torch.float32, device=feats.device)
         out_len = C.c_int(0)
@@ -767,14 +784,14 @@ class HipEngine:
         return tok, lp
 
     def beam_search(self, feats: Tensor, max_length: int, num_beams: int, early_stopping: bool = False,
-                    length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1) -> Tensor:
+                    length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.generate(num_beams>1): feats [S,1024] -> int64 [S * num_return_sequences, L]."""
         _require_gpu(feats.device)
         S = feats.shape[0]
         limit = int(max_length)
         dec = self._get_decoder(S * num_beams, limit)
         self._cached = None   # as in greedy_decode
-        _hip.check(self.lib.rgrg_decoder_set_precision(dec, int(bf16)), "rgrg_decoder_set_precision")
+        self._set_modes(dec, bf16, kv_fp8)
         feats = feats.to(torch.float32).contiguous()
         out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
         out_len = C.c_int(0)

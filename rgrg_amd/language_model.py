@@ -246,6 +246,26 @@ class LanguageModel(EngineOwner):
                                              position_ids=position_ids)
         return logits
 
+    KV_CACHE_DTYPES = (None, "fp8_e4m3")
+
+    def set_kv_cache_dtype(self, name: Optional[str]) -> None:
+        """Storage type of the decode K/V cache of ``generate`` (greedy and beam search) and ``sample``: None (default) = the cache
+        follows the precision mode; "fp8_e4m3" = plain OCP e4m3fn bytes (no scales; k / v clamped to +-448 and rounded once from
+        fp32) wherever the 16-bit cache would be used, i.e. under torch.autocast with more token rows than the fused plans take
+        (rgrg_decoder_row_limit(): 64).  WITHOUT autocast, or at fewer rows, the setting has NO effect - the fp32 paths and
+        their bit-exactness with the reference do not depend on it.  ``forward(use_cache=True)`` and training are not affected.
+        The setting lives on the outermost module (not a parameter or buffer: state dicts are untouched) and survives
+        ``load_state_dict`` / ``.to()``.  Any other value raises ValueError."""
+        if name not in self.KV_CACHE_DTYPES:
+            raise ValueError(f"kv cache dtype must be one of {self.KV_CACHE_DTYPES}, got {name!r}")
+        self._root().__dict__["_kv_cache_dtype"] = name
+
+    def kv_cache_dtype(self) -> Optional[str]:
+        return self._root().__dict__.get("_kv_cache_dtype")
+
+    def _kv_fp8(self) -> bool:
+        return self.kv_cache_dtype() == "fp8_e4m3"
+
     @torch.no_grad()
     def sample(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, *, temperature: float = 1.0,
                top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
@@ -265,7 +285,7 @@ class LanguageModel(EngineOwner):
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         low = _hip.autocast_mode()
         ids, logprobs = self.engine().sample_decode(image_hidden_states, max_length, temperature, int(top_k), top_p, int(seed),
-                                                    int(num_return_sequences), bf16=low)
+                                                    int(num_return_sequences), bf16=low, kv_fp8=self._kv_fp8())
         return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
@@ -289,7 +309,7 @@ class LanguageModel(EngineOwner):
             # like the reference's scripts, callers may wrap generate() in torch.autocast: a reduced-precision
             # autocast dtype opts the many-sequence decode GEMMs into the bf16 MFMA path
             low = _hip.autocast_mode()
-            return self.engine().greedy_decode(image_hidden_states, max_length, bf16=low)
+            return self.engine().greedy_decode(image_hidden_states, max_length, bf16=low, kv_fp8=self._kv_fp8())
         if num_beams > 1 and single_group:
             if do_sample is True:
                 raise NotImplementedError("Beam-search multinomial sampling is not implemented.")
@@ -300,5 +320,5 @@ class LanguageModel(EngineOwner):
             # length_penalty = 1.0 as in the reference (language_model.py:461)
             low = _hip.autocast_mode()
             return self.engine().beam_search(image_hidden_states, max_length, num_beams, early_stopping, 1.0, bf16=low,
-                                             num_return_sequences=num_return_sequences)
+                                             num_return_sequences=num_return_sequences, kv_fp8=self._kv_fp8())
         raise NotImplementedError("Diverse beam-search decoding is not implemented.")

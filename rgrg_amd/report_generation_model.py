@@ -189,6 +189,11 @@ class ReportGenerationModel(EngineOwner):
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
 
+    def set_kv_cache_dtype(self, name: Optional[str]) -> None:
+        """``LanguageModel.set_kv_cache_dtype``: None, or "fp8_e4m3" for an e4m3 decode K/V cache under torch.autocast with more than
+        64 token rows (no effect otherwise)."""
+        self.language_model.set_kv_cache_dtype(name)
+
     @torch.no_grad()
     def sample(self, images: torch.FloatTensor, max_length: int = None, *, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None, return_logprobs: bool = False):
