@@ -402,6 +402,12 @@ int rgrg_debug_ln_fold16(const float* w, const float* gain, const float* beta, c
 int rgrg_debug_linear_bf16_ln(const uint16_t* A16, const uint16_t* Wb, const float* shift, const float* R, float* Y,
                               uint16_t* Yb16, float* stats_out, const float* ln_stats, const float* ln_colsum, int M, int N,
                               int K, int ldy, int act, int fp16, void* stream);
+/* rgrg_debug_linear_bf16_ln_kv: the CONSUMER as the many-sequence decode step launches c_attn (N = 3 * H * 64, K == 1024): the q
+ * columns go to Y [M, ldy] as fp32; the k / v columns (GPT2PseudoAttention's `present`, :162-166) are rounded to the 16-bit type
+ * and stored to slot *step_dev + 1 of kcache / vcache [rows][H][T_slots][64] (row m of the GEMM = cache row m), not to Y. */
+int rgrg_debug_linear_bf16_ln_kv(const uint16_t* A16, const uint16_t* Wb, const float* shift, float* Y, const float* ln_stats,
+                                 const float* ln_colsum, uint16_t* kcache, uint16_t* vcache, const int* step_dev, int M, int H,
+                                 int T_slots, int K, int ldy, int fp16, void* stream);
 /* The same GEMM variants (plus the plain one with a 16-bit output Y16; exactly one of Y / Y16) on the K-parity ping-pong kernel
  * (csrc/gemm_kp.inc, round 6) when kp != 0 - the kernel the decoder selects for the per-layer projections of the many-sequence
  * 16-bit decode step (GPT2Block's c_attn / c_proj / c_fc / mlp.c_proj, src/language_model/language_model.py:338-366): its tile
@@ -426,6 +432,11 @@ int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t* Wb, const 
 int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
                            uint16_t* out16, int S, int H, int T_slots, const int* src, const float* kmask, int kv16, int fp16,
                            int ni, int frag_out, int max_workgroups, void* stream);
+/* rgrg_debug_attn_decode_qonly: the 16-bit kernel's q-only variant, attn_decode_kv16_wave_kernel<false, fp16, true> - the step behind
+ * rgrg_debug_linear_bf16_ln_kv: q [S][ld_q] fp32 (ld_q >= H * 64); the keys are slots 0 .. t + 1 of the cache, slot t + 1 included;
+ * nothing is stored to the cache. */
+int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void* kcache, const void* vcache, const int* step_dev, float* out,
+                                 uint16_t* out16, int S, int H, int T_slots, int fp16, int max_workgroups, void* stream);
 /* rgrg_debug_attn_decode_kv8: the same step on an e4m3 cache (rgrg_decoder_set_kv_format), attn_decode_kv8_wave_kernel<src, fp16>:
  * kcache / vcache [S][H][T_slots][64] BYTES; the new k / v are stored to slot t + 1 as clamp(+-448) + one rounding to nearest even;
  * the result goes to out16 (fp16 = 0 bf16 / 1 IEEE half) when given, else to out (fp32); max_workgroups > 0 caps the grid.

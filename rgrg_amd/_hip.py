@@ -16,7 +16,7 @@ c_float_p = C.c_void_p  # device pointers travel as void*
 _i, _f, _p = C.c_int, C.c_float, C.c_void_p
 
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
-ABI_VERSION = 24  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
+ABI_VERSION = 25  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
 
 
 class RgrgHipError(RuntimeError):
@@ -87,6 +87,8 @@ SIGNATURES = {
     "rgrg_debug_linear_bf16_ln": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln_kp": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_linear_bf16_ln_kv": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_attn_decode_qonly": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_kv8": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "rgrg_debug_attn_prefill": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _i, _p]),
     "rgrg_debug_attn_backward_f32": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, C.c_uint32, _f,

@@ -568,7 +568,9 @@ __device__ __forceinline__ u32x4 kv16_pack_round(const f32x4& lo, const f32x4& h
 }
 
 // FIRST: the first chunk of a wave turns the raw q / k / v into q[8] and the packed bf16 kn16 / vn16 (after its loads)
-template <int NI, bool HAS_SRC, bool FIRST, bool F16>
+// QONLY: c_attn's epilogue already stored the new token's k / v in cache slot t + 1 (gemm_bf16.hip, GemmBf16Params::kv_k): the
+// row brings q only, slot t + 1 is read like every other key - no k / v row, no kn16 / vn16, no patch
+template <int NI, bool HAS_SRC, bool FIRST, bool F16, bool QONLY>
 __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc, const __amdgpu_buffer_rsrc_t vc, const int* __restrict__ srow,
                                                 int s, int hd, int H, int T, int base, int nkeys, int slot, int g, int d8,
                                                 Kv16Row& r, float (&q)[8], u32x4& kn16, u32x4& vn16, float& m, float& l, float (&acc)[8]) {
@@ -593,19 +595,25 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (FIRST) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            asm volatile("" : "+v"(r.q0[e]), "+v"(r.q1[e]), "+v"(r.k0[e]), "+v"(r.k1[e]), "+v"(r.v0[e]), "+v"(r.v1[e]));
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (QONLY) asm volatile("" : "+v"(r.q0[e]), "+v"(r.q1[e]));
+            else asm volatile("" : "+v"(r.q0[e]), "+v"(r.q1[e]), "+v"(r.k0[e]), "+v"(r.k1[e]), "+v"(r.v0[e]), "+v"(r.v1[e]));
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) { q[e] = r.q0[e]; q[4 + e] = r.q1[e]; }
-        kn16 = kv16_pack_round<F16>(r.k0, r.k1);
-        vn16 = kv16_pack_round<F16>(r.v0, r.v1);
+        if constexpr (!QONLY) {
+            kn16 = kv16_pack_round<F16>(r.k0, r.k1);
+            vn16 = kv16_pack_round<F16>(r.v0, r.v1);
+        }
     }
     float sc[NI];
     float cmax = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int j = base + i * 8 + g;
-        if (j == slot) { kk[i] = kn16; vv[i] = vn16; }
+        if constexpr (!QONLY) {
+            if (j == slot) { kk[i] = kn16; vv[i] = vn16; }
+        }
         float dot = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -637,7 +645,7 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
     m = m_new;
 }
 
-template <bool HAS_SRC, bool F16>
+template <bool HAS_SRC, bool F16, bool QONLY = false>
 __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                                     u16* __restrict__ kc, u16* __restrict__ vc,
                                                                     const int* __restrict__ step, float* __restrict__ out,
@@ -659,16 +667,18 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     Kv16Row r;
     r.q0 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8);
     r.q1 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8 + 4);
-    r.k0 = *reinterpret_cast<const f32x4*>(row + D + hd * 64 + d8 * 8);
-    r.k1 = *reinterpret_cast<const f32x4*>(row + D + hd * 64 + d8 * 8 + 4);
-    r.v0 = *reinterpret_cast<const f32x4*>(row + 2 * D + hd * 64 + d8 * 8);
-    r.v1 = *reinterpret_cast<const f32x4*>(row + 2 * D + hd * 64 + d8 * 8 + 4);
+    if constexpr (!QONLY) {
+        r.k0 = *reinterpret_cast<const f32x4*>(row + D + hd * 64 + d8 * 8);
+        r.k1 = *reinterpret_cast<const f32x4*>(row + D + hd * 64 + d8 * 8 + 4);
+        r.v0 = *reinterpret_cast<const f32x4*>(row + 2 * D + hd * 64 + d8 * 8);
+        r.v1 = *reinterpret_cast<const f32x4*>(row + 2 * D + hd * 64 + d8 * 8 + 4);
+    }
     float m = -INFINITY, l = 0.f, acc[8], q[8];
     u32x4 kn16, vn16;
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #define KV16_CHUNK(NI_, FIRST_, BASE_) \
-    kv16_wave_chunk<NI_, HAS_SRC, FIRST_, F16>(rk, rv, srow, s, hd, H, T, BASE_, nkeys, slot, g, d8, r, q, kn16, vn16, m, l, acc)
+    kv16_wave_chunk<NI_, HAS_SRC, FIRST_, F16, QONLY>(rk, rv, srow, s, hd, H, T, BASE_, nkeys, slot, g, d8, r, q, kn16, vn16, m, l, acc)
     // chunks of 72 keys while more than 72 remain, then ONE chunk sized to what is left in steps of 8 keys (a wave-uniform
     // switch around fully unrolled, unconditional, clamped load blocks - never a branch around a single load).  Round 4:
     // the tail used to be 24 / 48 / 72 keys, i.e. 18 % more rows requested (and exponentiated) than a 128-token decode
@@ -696,10 +706,12 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     }
 #undef KV16_TAIL
 #undef KV16_CHUNK
-    if (g == 0) {  // the new token's key / value -> cache slot t + 1 (8 lanes x 16 B = the 128-byte row)
-        const size_t o = (((size_t)s * H + hd) * T + slot) * 64 + d8 * 8;
-        *reinterpret_cast<u32x4*>(kc + o) = kn16;
-        *reinterpret_cast<u32x4*>(vc + o) = vn16;
+    if constexpr (!QONLY) {
+        if (g == 0) {  // the new token's key / value -> cache slot t + 1 (8 lanes x 16 B = the 128-byte row)
+            const size_t o = (((size_t)s * H + hd) * T + slot) * 64 + d8 * 8;
+            *reinterpret_cast<u32x4*>(kc + o) = kn16;
+            *reinterpret_cast<u32x4*>(vc + o) = vn16;
+        }
     }
     // merge the 8 groups (lanes with equal d8): global max, rescale, sums
     float M = fmaxf(m, dpp_get<0x128, 0xf>(m));  // row_ror:8 = lane ^ 8 inside a 16-lane row
@@ -1090,6 +1102,8 @@ struct AttnDecodeLaunch {
     int frag_out;
     int max_wgs;                           // wave kernels (16 bit, e4m3): > 0 caps the grid, each wave then walks several (sequence, head) items
     hipStream_t st;
+    bool q_only = false;                   // 16-bit cache without src: slot t + 1 already holds the new k / v (c_attn's K/V-cache epilogue) -
+                                           // the kernel reads q only and stores nothing to the cache
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
     if (a.kmask && (a.fmt != KV_F32 || a.src)) {
@@ -1113,15 +1127,22 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
         }
         const int wgs = a.S * a.H / 4;
         const dim3 wgrid(a.max_wgs > 0 ? std::min(wgs, a.max_wgs) : wgs), wblk(256);
+        if (a.q_only && (a.fmt == KV_E4M3 || a.src)) {
+            set_error("decode attention: the q-only variant exists for the 16-bit K/V cache without an ancestor table (%s)",
+                      a.src ? "beam search" : "e4m3 K/V cache");
+            return RGRG_EINVAL;
+        }
         if (a.fmt == KV_E4M3)
             return launch_attn_decode_kv8(a.qkv, a.ld_qkv, static_cast<uint8_t*>(a.kc), static_cast<uint8_t*>(a.vc), a.step, a.out, a.out16,
                                           a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
-#define KV16_LAUNCH(SRC_, F16_) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<SRC_, F16_>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
+#define KV16_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<__VA_ARGS__>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
                                                   static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.out16)
-        if (a.src) { if (a.f16) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
+        if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true); else KV16_LAUNCH(false, false, true); }
+        else if (a.src) { if (a.f16) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
         else { if (a.f16) KV16_LAUNCH(false, true); else KV16_LAUNCH(false, false); }
 #undef KV16_LAUNCH
     } else {
+        if (a.q_only) { set_error("decode attention: the q-only variant exists for the 16-bit K/V cache only"); return RGRG_EINVAL; }
         const dim3 grid(a.S * a.H), blk(256);
         const int ni = a.ni ? a.ni : (a.S * a.H <= 4096 ? 9 : 2);
         if (ni != 9 && ni != 2) { set_error("decode attention: %d keys per group, the kernel is built for 9 and 2", ni); return RGRG_EINVAL; }
@@ -1139,9 +1160,12 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
 
 // r0: first sequence of the launch (the many-sequence step may run as two row ranges on two streams, enqueue_step); src / att16
 // are the caller's pointers for that first sequence already
-static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsigned short* att16, int frag_out = 0, int r0 = 0) {
+// q_only: c_attn ran with the K/V-cache epilogue (step_qkv_cache / cons_kv_cache below)
+static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsigned short* att16, int frag_out = 0, int r0 = 0,
+                            bool q_only = false) {
     const int D = d->D;
     AttnDecodeLaunch a{};
+    a.q_only = q_only;
     a.ld_qkv = 3 * D; a.step = d->step; a.S = S; a.H = d->H; a.T = d->T; a.src = src; a.kmask = d->key_mask_cur;
     a.frag_out = frag_out; a.st = d->stream; a.plane_elems = d->kv_kv_stride;
     a.fmt = kv_format(d, S);
@@ -1337,6 +1361,26 @@ static int trace_mark(rgrg_decoder* d, int r0, int tag) {
     return RGRG_OK;
 }
 
+// The LayerNorm-folded 16-bit many-sequence step (see enqueue_step) ...
+static bool step_ln_fold(const rgrg_decoder* d, int S) {
+    return kv_is_bf16(d, S) && d->xn16 && d->ln_fold && d->ln_stat && d->layers[0].c_attn.wb_ln && d->D == 1024;
+}
+// ... whose c_attn writes the new token's k / v straight into slot t + 1 of the 16-bit cache and whose attention reads q only:
+// `plain` steps (the step's own token and cache rows: greedy and sampling; not beam search, not forward(use_cache=True)) on the
+// bf16 / fp16 cache (not e4m3), c_attn on the LDS-DMA kernel - the row-split kernel of RGRG_GEMM_KP=1/3 has no such epilogue and
+// keeps the fp32 q | k | v row.  RGRG_QKV_CACHE=0: the fp32 row everywhere (A/B, tests/test_gpu_qkv_cache.py).
+static bool step_qkv_cache(const rgrg_decoder* d, int S, bool plain) {
+    const KvFormat f = kv_format(d, S);
+    return d->qkv_cache && plain && step_ln_fold(d, S) && (f == KV_BF16 || f == KV_F16) && d->kp_gemms != 1 && d->kp_gemms != 3 && !d->key_mask_cur;
+}
+// the consumer fold of layer l's c_attn for the sequences from r0 on, with the cache planes launch_attention passes for them
+static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, int l, int r0) {
+    GemmLnFold f = cons;
+    u16* kcr = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride + (size_t)r0 * d->H * d->T * 64;
+    f.kv_k = kcr; f.kv_v = kcr + d->kv_kv_stride; f.kv_step = d->step; f.kv_H = d->H; f.kv_T = d->T;
+    return f;
+}
+
 // One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
 //   embed+ln1 | per layer: c_attn, attention, attn_proj (+ residual), ln2, c_fc+gelu, mlp_proj (+ residual),
 //   ln1 of the next layer / ln_f | lm_head, per-32-column arg-max candidates, argmax + bookkeeping
@@ -1358,7 +1402,9 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
     // (sum, sum of squares) slots in ln_stat; the GEMM behind the LayerNorm (c_attn, c_fc) multiplies the raw 16-bit x with
     // gain-scaled weights and finishes rstd (acc - mean colsum) + shift in its epilogue (gemm_bf16.hip).  ln_f in front of
     // the lm_head stays a launch: the slot reads cost its 3144 workgroups more than the one ln_rows per step
-    const bool fold = xn16 && d->ln_fold && d->ln_stat && d->layers[0].c_attn.wb_ln && D == 1024;
+    const bool fold = step_ln_fold(d, S);
+    // ... and c_attn's k / v columns go straight to cache slot t + 1 as 16 bit; the attention then reads q only (step_qkv_cache)
+    const bool qc = step_qkv_cache(d, S, !tok_override && !src);
     static const float cons_tag = 0.f;   // any non-null pointer: linear() substitutes the GEMM's own column sums
     GemmLnFold prod{}, cons{};
     prod.Yb16 = xn16; prod.stats_out = d->ln_stat;
@@ -1389,9 +1435,10 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
             const LayerW& w = d->layers[l];
             const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
             const float* nb = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_b : d->lnf_b;
-            if ((rc2 = linear(d, w.c_attn, xn, nullptr, d->qkv + 3 * o, rows, 3 * D, RGRG_ACT_NONE, count, xn16r, nullptr, cfr))) return rc2;
+            const GemmLnFold cons_kv = qc ? cons_kv_cache(d, cons_r, l, r0) : cons_r;
+            if ((rc2 = linear(d, w.c_attn, xn, nullptr, d->qkv + 3 * o, rows, 3 * D, RGRG_ACT_NONE, count, xn16r, nullptr, qc ? &cons_kv : cfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 0))) return rc2;
-            if ((rc2 = launch_attention(d, l, rows, src ? src + (size_t)r0 * d->T : nullptr, att16r, 0, r0))) return rc2;
+            if ((rc2 = launch_attention(d, l, rows, src ? src + (size_t)r0 * d->T : nullptr, att16r, 0, r0, qc))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 1))) return rc2;
             if ((rc2 = linear(d, w.attn_proj, d->att + o, x, x, rows, D, RGRG_ACT_NONE, count, att16r, nullptr, pfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 2))) return rc2;
@@ -1498,6 +1545,7 @@ extern "C" int rgrg_decoder_create_with_cache(const rgrg_decoder_weights* w, int
     }
     if (const char* e = getenv("RGRG_GEMM_KP")) d->kp_gemms = atoi(e);
     if (const char* e = getenv("RGRG_W16_FUSED")) d->w16_fused = atoi(e) != 0;
+    if (const char* e = getenv("RGRG_QKV_CACHE")) d->qkv_cache = atoi(e) != 0;
     if (const char* e = getenv("RGRG_DECODE_CHAINS")) {
         const int v = atoi(e);
         d->chains = (v >= -MAX_CHAINS && v <= MAX_CHAINS && v != 0 && v != -1) ? v : 1;
@@ -1851,6 +1899,18 @@ extern "C" int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache
     return launch_attn_decode(a);
 }
 
+// Test hook: the q-only variant of the 16-bit kernel (the many-sequence step behind c_attn's K/V-cache epilogue) through the same
+// launcher: q [S][ld_q] fp32, every key including slot *step_dev + 1 comes from the cache, nothing is stored to it.
+extern "C" int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void* kcache, const void* vcache, const int* step_dev, float* out,
+                                            uint16_t* out16, int S, int H, int T_slots, int fp16, int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(q && kcache && vcache && step_dev && S > 0 && H > 0 && T_slots >= 2 && ld_q >= H * 64 && (out || out16));
+    AttnDecodeLaunch a{};
+    a.qkv = q; a.ld_qkv = ld_q; a.kc = const_cast<void*>(kcache); a.vc = const_cast<void*>(vcache);
+    a.plane_elems = (size_t)S * H * T_slots * 64; a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots;
+    a.fmt = fp16 ? KV_F16 : KV_BF16; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream); a.q_only = true;
+    return launch_attn_decode(a);
+}
+
 // Test hook: the same launcher on an e4m3 cache (attn_decode_kv8_wave_kernel): K / V planes of bytes, out (fp32) or out16 (bf16 / fp16 by
 // `fp16`), exactly as launch_attention fills it for a decoder in that format.
 extern "C" int rgrg_debug_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kcache, uint8_t* vcache, const int* step_dev, float* out,
@@ -2046,8 +2106,9 @@ extern "C" int rgrg_decoder_attention_only(rgrg_decoder* d, int S, int nkeys, in
     hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, nkeys - 2);
     int rc = RGRG_OK;
     unsigned short* att16 = (kv_is_bf16(d, S) && d->xn16) ? d->att16 : nullptr;
+    const bool qc = step_qkv_cache(d, S, true);   // the variant the greedy step launches
     for (int it = 0; it < iters && !rc; ++it)
-        for (int l = 0; l < d->n_layer && !rc; ++l) rc = launch_attention(d, l, S, nullptr, att16, 0, 0);
+        for (int l = 0; l < d->n_layer && !rc; ++l) rc = launch_attention(d, l, S, nullptr, att16, 0, 0, qc);
     hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, 0);
     d->stream = keep;
     return rc;
@@ -2108,7 +2169,8 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     unsigned short* att16 = xn16 ? d->att16 : nullptr;
     unsigned short* ff16 = xn16 ? d->ff16 : nullptr;
     // the folded-LayerNorm variants the step launches in the 16-bit mode
-    const bool fold = xn16 && d->ln_fold && d->ln_stat && d->layers[0].c_attn.wb_ln && D == 1024;
+    const bool fold = step_ln_fold(d, S);
+    const bool qc = step_qkv_cache(d, S, true);   // c_attn with the K/V-cache epilogue, q-only attention: as the greedy step
     static const float cons_tag = 0.f;
     GemmLnFold prod{}, cons{};
     prod.Yb16 = xn16; prod.stats_out = d->ln_stat;
@@ -2118,6 +2180,8 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     int rc = RGRG_OK;
     float tg = 0.f, ta = 0.f;
     d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0;
+    // (c_attn's K/V-cache epilogue stores to slot *step + 1: the slot the attention replays below read last)
+    if (qc) hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, nkeys - 2);
     // ONE event pair around all `iters` replays (plus an untimed one in front): a pair per replay with a host wait in
     // between lets the GPU go idle between replays, and each then starts on ramping clocks (read 3-6 % slow)
     for (int it = -1; it < iters && !rc; ++it) {
@@ -2143,7 +2207,8 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
                     if ((rc2 = enqueue_layer_gemms(d, l, S, c, nullptr, d->x, d->x2, 1))) break;
                     continue;
                 }
-                if ((rc2 = linear(d, w.c_attn, d->xn + o, nullptr, d->qkv + 3 * o, rows, 3 * D, RGRG_ACT_NONE, c, xn16r, nullptr, cfr))) break;
+                const GemmLnFold cons_kv = qc ? cons_kv_cache(d, cons_r, l, r0) : cons_r;
+                if ((rc2 = linear(d, w.c_attn, d->xn + o, nullptr, d->qkv + 3 * o, rows, 3 * D, RGRG_ACT_NONE, c, xn16r, nullptr, qc ? &cons_kv : cfr))) break;
                 if ((rc2 = linear(d, w.attn_proj, d->att + o, d->x + o, d->h1 + o, rows, D, RGRG_ACT_NONE, c, att16r, nullptr, pfr))) break;
                 if ((rc2 = linear(d, w.c_fc, d->xn + o, nullptr, d->ff + 4 * o, rows, 4 * D, RGRG_ACT_GELU_NEW, c, xn16r, ff16r, cfr))) break;
                 if ((rc2 = linear(d, w.mlp_proj, d->ff + 4 * o, d->x + o, d->h1 + o, rows, D, RGRG_ACT_NONE, c, ff16r, nullptr, pfr))) break;
@@ -2174,7 +2239,7 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
             rc = run_row_ranges(d, S, fused ? 1 : step_chains(d, S, true, fold), [&](int r0, int rows) -> int {
                 int rc2 = RGRG_OK;
                 for (int l = 0; l < d->n_layer && !rc2; ++l)
-                    rc2 = launch_attention(d, l, rows, nullptr, att16 ? att16 + (size_t)r0 * D : nullptr, fused ? 1 : 0, r0);
+                    rc2 = launch_attention(d, l, rows, nullptr, att16 ? att16 + (size_t)r0 * D : nullptr, fused ? 1 : 0, r0, qc);
                 return rc2;
             });
         }

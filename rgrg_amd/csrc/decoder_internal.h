@@ -194,6 +194,8 @@ struct rgrg_decoder {
     std::vector<TraceMark>* trace = nullptr;
     bool w16_fused = true;      // under autocast 33-128 rows run the fused plan on 16-bit weights (skinny_direct.inc W16); RGRG_W16_FUSED=0: the
                                 // many-sequence 16-bit path from 33 rows on (A/B)
+    bool qkv_cache = true;      // plain 16-bit many-sequence steps: c_attn stores k / v into cache slot t + 1, the attention reads q only
+                                // (decoder.hip step_qkv_cache); RGRG_QKV_CACHE=0: the fp32 q | k | v row and the attention's own cache store (A/B)
     int kp_gemms = 2;           // ... and run on the K-parity ping-pong kernel (gemm_kp.inc, round 6): RGRG_GEMM_KP = 0 none (the LDS-DMA kernel), 1 all four,
                                 // 2 (default) the producers only (attn_proj / mlp_proj, N = 1024), 3 the consumers only (c_attn / c_fc, 128 x 128 row-split kernel).
                                 // Measured per mode: profiles/r06_step_trace_v3.log

@@ -44,6 +44,13 @@ struct GemmBf16Params {
     float* stats_out = nullptr;
     const float* ln_stats = nullptr;
     const float* ln_colsum = nullptr;
+    //  * consumer with the K/V-cache epilogue (c_attn of the many-sequence decode step, N = 3 D, D = kv_H * 64): a 32-column
+    //    block at column >= D is half a head of K (< 2 D) or of V; row m of it is stored - rounded to the 16-bit type f16, the one
+    //    rounding the attention kernel used to apply to the fp32 row - into the 128-byte cache row
+    //    ((m * kv_H + head) * kv_T + *kv_step + 1) * 64 of kv_k / kv_v and NOT to Y; the q columns (< D) go to Y as fp32.
+    u16 *kv_k = nullptr, *kv_v = nullptr;
+    const int* kv_step = nullptr;
+    int kv_H = 0, kv_T = 0;
     // training pass (round 5, LDS-DMA kernel, plain variant): Ypre16 [M, ldy] receives the 16-bit PRE-activation value next to
     // the activated Y16 (c_fc keeps what gelu_new' needs); G16 [M, ldy] holds 16-bit pre-activations whose gelu_new' multiplies
     // the result (the dgrad of mlp_proj lands directly as d(c_fc output))
@@ -374,7 +381,8 @@ __device__ __forceinline__ void glds_compute(const unsigned char* sa, const unsi
 // (oy * stride + kh - pad, ox * stride + kw - pad): still one contiguous 128-byte line per row, so the LDS-DMA path is
 // unchanged; only the per-lane source offset is recomputed per K tile (tap = kt * 64 / Cin, a handful of integer
 // instructions), and taps outside the image read the zero line that precedes the tensor.
-// LNF: 0 plain; 1 producer of a folded LayerNorm (Yb16 + stats_out); 2 consumer (ln_stats + ln_colsum) - GemmBf16Params.
+// LNF: 0 plain; 1 producer of a folded LayerNorm (Yb16 + stats_out); 2 consumer (ln_stats + ln_colsum); 3 consumer whose k / v
+// columns go to the 16-bit K/V cache (kv_k / kv_v / kv_step) - GemmBf16Params.
 // Compile-time so that the plain kernel carries none of it (as runtime branches the conditional loads made hipcc drain
 // the whole operand prologue - vmcnt(0) - at the join in front of the K loop of EVERY variant).
 template <int BM, int BN, int NST, bool CONV, bool F16, int LNF>
@@ -386,6 +394,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     constexpr int STAGE = (BM + BN) * 128;      // bytes per stage
     static_assert((NST - 2) * LPW < 64, "counted vmcnt out of range");
     static_assert(NST >= 2 && NST <= 4, "tail is written for up to 3 trailing tiles");
+    constexpr bool CONS = LNF >= 2, KVC = LNF == 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char glds_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -480,9 +489,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
         for (int ni = 0; ni < NI; ++ni) {
             const int colc = min(n0 + wn * (BN / 2) + ni * 32 + ccol, p.N - 1);
             sh_pre[mi][ni] = p.shift ? p.shift[colc] : 0.f;
-            cs_pre[mi][ni] = LNF == 2 ? p.ln_colsum[colc] : 0.f;
+            cs_pre[mi][ni] = CONS ? p.ln_colsum[colc] : 0.f;
         }
-    constexpr bool PRE_R = MI * NI == 1 && LNF != 2;   // (a consumer of a folded LayerNorm has no residual: the launcher checks)
+    constexpr bool PRE_R = MI * NI == 1 && !CONS;   // (a consumer of a folded LayerNorm has no residual: the launcher checks)
     float rv_pre[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rv_pre[r] = 0.f;
@@ -504,7 +513,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     // 256 / BM threads share a row, each adds its slots in index order.
     constexpr int TPR = 256 / BM, PER = 16 / TPR;   // 16 slots per row (64-column blocks of the 1024-wide producer)
     f32x4 lsq[PER / 2];
-    if constexpr (LNF == 2) {
+    // K/V-cache epilogue: the step counter is one scalar load per workgroup, requested here - never on the epilogue's critical path
+    int kv_slot = 0;
+    if constexpr (KVC) kv_slot = *p.kv_step + 1;
+    if constexpr (CONS) {
         const int srow = min(m0 + tid / TPR, p.M - 1);
         const f32x4* sp = reinterpret_cast<const f32x4*>(p.ln_stats + ((size_t)srow * 16 + (tid % TPR) * PER) * 2);
 #pragma unroll
@@ -591,7 +603,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     // folded LayerNorm: (mean, rstd) of the tile's rows -> LDS behind the stages (the last stage may still be read by slower
     // waves), from where the epilogue fetches the 16 rows of its C layout
     float2* row_stat = reinterpret_cast<float2*>(glds_smem + NST * STAGE);   // [BM]
-    if constexpr (LNF == 2) {
+    if constexpr (CONS) {
         // ONE summation order for every tile shape (a row's result must not depend on the tile the launcher picks for M): the 16
         // slots are added in groups of four (slot order, from zero), the groups pairwise: (G0 + G1) + (G2 + G3).  64-row tiles:
         // a thread owns one group, the butterfly below adds them; 128-row tiles: a thread owns two groups and adds them first.
@@ -628,14 +640,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
             float rv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) rv[r] = rv_pre[r];   // 64 x 64 tiles: the residual prefetched above (zeros otherwise)
-            if (!PRE_R && LNF != 2 && p.R) {
+            if (!PRE_R && !CONS && p.R) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
                     rv[r] = p.R[(size_t)row * p.ldy + colc];
                 }
             }
-            if (LNF != 2 && p.R16) {
+            if (!CONS && p.R16) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
@@ -643,7 +655,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
                 }
             }
             float vv[16];
-            if constexpr (LNF == 2) {
+            if constexpr (CONS) {
                 const float cs = cs_pre[mi][ni];
                 const int lrow0 = wm * (BM / 2) + mi * 32 + crow4;
 #pragma unroll
@@ -676,7 +688,22 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
 #pragma unroll
                 for (int r = 0; r < 16; ++r) vv[r] = apply_act_fast(acc[mi][ni][r] + sh + rv[r], p.act);
             }
-            if (col < p.N) {
+            bool to_cache = false;
+            if constexpr (KVC) to_cache = n0 + wn * (BN / 2) + ni * 32 >= p.kv_H * 64;   // wave-uniform: a 32-column block is q, k or v
+            if (to_cache) {
+                // k / v of the current token -> slot *kv_step + 1 of this head's cache row: 32 lanes x 2 B = half of the 128-byte row
+                // (N = 3 D: col < N here; a slot outside the plane stores nothing)
+                const int Dm = p.kv_H * 64, c = col - Dm, isv = c >= Dm ? 1 : 0, ch = c - isv * Dm;
+                u16* plane = isv ? p.kv_v : p.kv_k;
+                const size_t o0 = ((size_t)(ch >> 6) * p.kv_T + kv_slot) * 64 + (ch & 63);
+                if (kv_slot < p.kv_T) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rbase + (r & 3) + 8 * (r >> 2);
+                        if (row < p.M) plane[(size_t)row * p.kv_H * p.kv_T * 64 + o0] = (u16)to16<F16>(vv[r]);
+                    }
+                }
+            } else if (col < p.N) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int dr = (r & 3) + 8 * (r >> 2);
@@ -1146,6 +1173,7 @@ static int glds_attr() {
 #define RGRG_G_ATTR(...) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_glds_kernel<BM, BN, NST, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
     RGRG_G_ATTR(false, false, 0); RGRG_G_ATTR(true, false, 0); RGRG_G_ATTR(false, true, 0); RGRG_G_ATTR(true, true, 0);
     RGRG_G_ATTR(false, false, 1); RGRG_G_ATTR(false, true, 1); RGRG_G_ATTR(false, false, 2); RGRG_G_ATTR(false, true, 2);
+    RGRG_G_ATTR(false, false, 3); RGRG_G_ATTR(false, true, 3);
 #undef RGRG_G_ATTR
     return RGRG_OK;
 }
@@ -1194,6 +1222,7 @@ static int launch_glds_cfg(const GemmBf16Params& p0, hipStream_t st) {
 #define RGRG_G_LAUNCH(CONV_, F16_, LNF_) hipLaunchKernelGGL((gemm_bf16_glds_kernel<BM, BN, NST, CONV_, F16_, LNF_>), dim3(mtiles * ntiles * ks), dim3(256), NST * (BM + BN) * 128 + BM * 16, st, p, mtiles, ntiles)
     if (p.cCin) { if (p.f16) RGRG_G_LAUNCH(true, true, 0); else RGRG_G_LAUNCH(true, false, 0); }
     else if (p.Yb16) { if (p.f16) RGRG_G_LAUNCH(false, true, 1); else RGRG_G_LAUNCH(false, false, 1); }
+    else if (p.ln_colsum && p.kv_k) { if (p.f16) RGRG_G_LAUNCH(false, true, 3); else RGRG_G_LAUNCH(false, false, 3); }
     else if (p.ln_colsum) { if (p.f16) RGRG_G_LAUNCH(false, true, 2); else RGRG_G_LAUNCH(false, false, 2); }
     else { if (p.f16) RGRG_G_LAUNCH(false, true, 0); else RGRG_G_LAUNCH(false, false, 0); }
 #undef RGRG_G_LAUNCH
@@ -1250,6 +1279,7 @@ static bool pp_lm_head() {   // RGRG_GEMM_PP_LMHEAD=0: keep the decode lm_head o
 // 10 = 64x64x3, 11 = its (N, K) heuristic; 12 = the 128 x 128 row-split ping-pong kernel (gemm_kp.inc)
 static int launch_glds(const GemmBf16Params& p, int tile, hipStream_t st) {
     int shape = tile & 15, nst = tile >> 4;
+    if (p.kv_k && shape >= 5) { set_error("bf16 GEMM: only the LDS-DMA kernel has the K/V-cache epilogue (tile %d)", tile); return RGRG_EINVAL; }
     switch (shape) {
         case 6: return launch_kp_cfg<128, 128, 2>(p, st);
         case 7: return launch_kp_cfg<64, 64, 4>(p, st);
@@ -1326,6 +1356,15 @@ int launch_gemm_bf16w_ex(const float* A, const void* A16, const void* Wb, const 
         RGRG_CHECK_ARG(!ln->ln_colsum || (ln->ln_stats && K == 1024 && !R));
         p.Yb16 = reinterpret_cast<u16*>(ln->Yb16); p.stats_out = ln->stats_out;
         p.ln_stats = ln->ln_stats; p.ln_colsum = ln->ln_colsum;
+        if (ln->kv_k) {   // c_attn with the K/V-cache epilogue: consumer on the LDS-DMA kernel (no K-parity kernel, no split-K), fp32 q, no activation
+            RGRG_CHECK_ARG(ln->ln_colsum && ln->kv_v && ln->kv_step && ln->kv_H > 0 && ln->kv_T >= 2 && N == 3 * ln->kv_H * 64 && Y && !Y16 && !ln->kp &&
+                           ln->ksplit <= 1 && act == RGRG_ACT_NONE);
+            p.kv_k = reinterpret_cast<u16*>(ln->kv_k); p.kv_v = reinterpret_cast<u16*>(ln->kv_v);
+            p.kv_step = ln->kv_step; p.kv_H = ln->kv_H; p.kv_T = ln->kv_T;
+        }
+    } else if (ln && ln->kv_k) {
+        set_error("bf16 GEMM: the K/V-cache epilogue belongs to the folded-LayerNorm consumer");
+        return RGRG_EINVAL;
     }
     if (ln && ln->ksplit > 1) { p.ksplit = ln->ksplit; p.sk_ws = ln->sk_ws; p.sk_cnt = ln->sk_cnt; }   // split-K (LDS-DMA kernel)
     if (ln && ln->cand_val) {   // arg-max candidates instead of logits: 256 x 256 ping-pong kernel only
@@ -1438,6 +1477,20 @@ extern "C" int rgrg_debug_linear_bf16_ln(const uint16_t* A16, const uint16_t* Wb
     GemmLnFold f{};
     f.Yb16 = Yb16; f.stats_out = stats_out; f.ln_stats = ln_stats; f.ln_colsum = ln_colsum;
     return launch_gemm_bf16w_ex(nullptr, A16, Wb, shift, R, Y, nullptr, M, N, K, ldy, act, as_stream(stream), fp16, &f);
+}
+
+// Test hook for the consumer with the K/V-cache epilogue (c_attn of the many-sequence decode step), through the launcher the
+// decoder uses: q columns -> Y fp32 [M, ldy], k / v columns -> slot *step_dev + 1 of kcache / vcache [rows][H][T_slots][64].
+extern "C" int rgrg_debug_linear_bf16_ln_kv(const uint16_t* A16, const uint16_t* Wb, const float* shift, float* Y, const float* ln_stats,
+                                            const float* ln_colsum, uint16_t* kcache, uint16_t* vcache, const int* step_dev, int M, int H,
+                                            int T_slots, int K, int ldy, int fp16, void* stream) {
+    int rc = init_gemm_bf16_attrs();
+    if (rc) return rc;
+    RGRG_CHECK_ARG(A16 && Wb && Y && ln_stats && ln_colsum && kcache && vcache && step_dev && H > 0);
+    GemmLnFold f{};
+    f.ln_stats = ln_stats; f.ln_colsum = ln_colsum;
+    f.kv_k = kcache; f.kv_v = vcache; f.kv_step = step_dev; f.kv_H = H; f.kv_T = T_slots;
+    return launch_gemm_bf16w_ex(nullptr, A16, Wb, shift, nullptr, Y, nullptr, M, 3 * H * 64, K, ldy, RGRG_ACT_NONE, as_stream(stream), fp16, &f);
 }
 
 // The same on the K-parity ping-pong kernel (gemm_kp.inc), which the decoder selects for the many-sequence step: kp != 0.

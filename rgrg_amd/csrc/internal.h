@@ -25,6 +25,12 @@ struct GemmLnFold {   // LayerNorm folded around the 16-bit GEMMs (gemm_bf16.hip
     float* cand_val = nullptr;          // 256 x 256 kernel: per-row (maximum, column) of every column tile instead of Y (greedy lm_head)
     int* cand_idx = nullptr;
     int kp = 0;                         // the K-parity ping-pong kernel (gemm_kp.inc), tile from (N, K) only
+    // consumer, c_attn of the many-sequence decode step (N = 3 * kv_H * 64): the k / v columns go to slot *kv_step + 1 of the 16-bit
+    // cache planes [rows][kv_H][kv_T][64] (already offset to the launch's first sequence), rounded to the GEMM's 16-bit type, instead
+    // of to Y; the q columns go to Y as fp32.  LDS-DMA kernel only.
+    void *kv_k = nullptr, *kv_v = nullptr;
+    const int* kv_step = nullptr;
+    int kv_H = 0, kv_T = 0;
 };
 int init_gemm_bf16_attrs();
 bool gemm_bf16_cand_epilogue_ok(int M, int N, int K);   // would launch_gemm_bf16w_ex pick the 256 x 256 kernel for this lm_head?
