@@ -182,6 +182,24 @@ void rgrg_decoder_destroy(rgrg_decoder* d);
  * before returning.  use_graph=0 launches the kernels eagerly (debug/profiling). */
 int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_length, int64_t* out_ids,
                           int out_ld, int* out_len, int use_graph, void* stream);
+/* LanguageModel.greedy_search with a prompt (language_model.py:609-652): rgrg_decoder_generate that continues input_ids int64 [S,T]
+ * (any ids inside the vocabulary; an EOS inside the prompt finishes nothing) instead of a BOS column.  Slot 0 of the cache is the
+ * image as in rgrg_decoder_generate; ONE teacher-forced pass over the S x T prompt rows in the current precision mode stores the
+ * keys / values of every prompt token in slots 1 .. T of the decode cache (fp32, or the 16-bit type where the decode steps of S rows
+ * keep a 16-bit cache) and yields the first generated token from the S last-position rows (no [S,T,V] logits exist); the decode
+ * loop runs from step T on.  attention_mask f32 [S,T] of zeros and ones, or NULL = all ones: zeros are LEFT padding; padded slots
+ * stay out of every later step (the reference's additive -1e4, :316-334), the image key and generated tokens never do, and row s
+ * embeds its tokens at cumsum(mask) - 1 continued per row (prepare_inputs_for_generation, :498-520), padded slots at 1.
+ * max_length is the reference's: cur_len starts at T, one token is always produced, the loop ends at cur_len >= max_length or when
+ * every row has emitted EOS among its GENERATED tokens; <= 0 = bounded by the decoder's max_len.  out_ids [S,out_ld] receives the
+ * prompt, the generated ids and PAD behind a row's EOS; *out_len = L' >= T + 1.  A mask of ones replays the captured step of
+ * rgrg_decoder_generate, a padded prompt its own.  Afterwards rgrg_decoder_copy_last_logits works as after rgrg_decoder_generate.
+ *   RGRG_EINVAL (with a message): T + 1 > max_len of the decoder; max_length > max_len; a mask row of zeros only; a zero behind a
+ *   one (not left padding); mask values other than 0 and 1; the e4m3 K/V cache in use for S rows (rgrg_decoder_set_kv_format).
+ * There is no flag for "no mask given": the reference's greedy_search cannot run without one (its forward dereferences the mask,
+ * :281), so the host mirror refuses that call and NULL here simply means ones. */
+int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
+                                   int T, int max_length, int64_t* out_ids, int out_ld, int* out_len, int use_graph, void* stream);
 /* ---- Sampling.  The sampler is a pure function of one fp32 logits row x[0..V), temperature > 0, top_k >= 0 (0 = off),
  * 0 < top_p <= 1 (1 = off), a 64-bit seed, a row counter r and a step t:
  *   temperature  z_i = x_i * inv_T, inv_T = 1.0f / temperature computed once on the host in fp32.
@@ -437,6 +455,13 @@ int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache, void* vca
  * nothing is stored to the cache. */
 int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void* kcache, const void* vcache, const int* step_dev, float* out,
                                  uint16_t* out16, int S, int H, int T_slots, int fp16, int max_workgroups, void* stream);
+/* rgrg_debug_attn_decode_first: the 16-bit kernel's padded-prompt variant, attn_decode_kv16_wave_kernel<false, fp16, q_only, true> - the
+ * steps of rgrg_decoder_generate_prompted behind a left-padded prompt: first int32 [S], cache slots 1 .. first[s] of row s are left
+ * out of the softmax (slot 0, the image, and every later slot are not).  q_only = 0: qkv [S][ld_qkv >= 3*H*64] as in
+ * rgrg_debug_attn_decode (the new k / v are stored to slot t + 1); q_only = 1: q [S][ld_qkv >= H*64] as in rgrg_debug_attn_decode_qonly. */
+int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                                 uint16_t* out16, int S, int H, int T_slots, const int* first, int fp16, int q_only,
+                                 int max_workgroups, void* stream);
 /* rgrg_debug_attn_decode_kv8: the same step on an e4m3 cache (rgrg_decoder_set_kv_format), attn_decode_kv8_wave_kernel<src, fp16>:
  * kcache / vcache [S][H][T_slots][64] BYTES; the new k / v are stored to slot t + 1 as clamp(+-448) + one rounding to nearest even;
  * the result goes to out16 (fp16 = 0 bf16 / 1 IEEE half) when given, else to out (fp32); max_workgroups > 0 caps the grid.

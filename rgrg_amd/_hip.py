@@ -16,7 +16,7 @@ c_float_p = C.c_void_p  # device pointers travel as void*
 _i, _f, _p = C.c_int, C.c_float, C.c_void_p
 
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
-ABI_VERSION = 25  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
+ABI_VERSION = 26  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
 
 
 class RgrgHipError(RuntimeError):
@@ -56,6 +56,7 @@ SIGNATURES = {
     "rgrg_decoder_kv_cache_bytes": (C.c_size_t, [_i, _i, _i]),
     "rgrg_decoder_destroy": (None, [_p]),
     "rgrg_decoder_generate": (_i, [_p, _p, _i, _i, _p, _i, C.POINTER(_i), _i, _p]),
+    "rgrg_decoder_generate_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i, C.POINTER(_i), _i, _p]),
     "rgrg_decoder_sample": (_i, [_p, _p, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_sample_logits_f32": (_i, [_p, C.c_int64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p]),
     "rgrg_decoder_beam_search": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "rgrg_debug_attn_decode": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln_kv": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_qonly": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_attn_decode_first": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_kv8": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "rgrg_debug_attn_prefill": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _i, _p]),
     "rgrg_debug_attn_backward_f32": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, C.c_uint32, _f,

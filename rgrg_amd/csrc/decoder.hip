@@ -570,10 +570,14 @@ __device__ __forceinline__ u32x4 kv16_pack_round(const f32x4& lo, const f32x4& h
 // FIRST: the first chunk of a wave turns the raw q / k / v into q[8] and the packed bf16 kn16 / vn16 (after its loads)
 // QONLY: c_attn's epilogue already stored the new token's k / v in cache slot t + 1 (gemm_bf16.hip, GemmBf16Params::kv_k): the
 // row brings q only, slot t + 1 is read like every other key - no k / v row, no kn16 / vn16, no patch
-template <int NI, bool HAS_SRC, bool FIRST, bool F16, bool QONLY>
+// HAS_FIRST (rgrg_decoder_generate_prompted, a left-padded prompt): cache slots 1 .. npad of the row are padding and are left out
+// (score -inf); the reference adds -1e4 to their scores (language_model.py:316-334), whose weight next to the never-masked image
+// key is exp(-1e4 + O(10)) = 0 in fp32 - the same result
+template <int NI, bool HAS_SRC, bool FIRST, bool F16, bool QONLY, bool HAS_FIRST = false>
 __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc, const __amdgpu_buffer_rsrc_t vc, const int* __restrict__ srow,
                                                 int s, int hd, int H, int T, int base, int nkeys, int slot, int g, int d8,
-                                                Kv16Row& r, float (&q)[8], u32x4& kn16, u32x4& vn16, float& m, float& l, float (&acc)[8]) {
+                                                Kv16Row& r, float (&q)[8], u32x4& kn16, u32x4& vn16, float& m, float& l, float (&acc)[8],
+                                                int npad = 0) {
     int rowi[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) rowi[i] = HAS_SRC ? srow[min(base + i * 8 + g, nkeys - 1)] : s;
@@ -621,7 +625,8 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
         dot += dpp_get<0xB1, 0xf>(dot);
         dot += dpp_get<0x4E, 0xf>(dot);
         dot += dpp_get<0x141, 0xf>(dot);  // row_half_mirror: sum over the 8 lanes of the group
-        sc[i] = j < nkeys ? dot / 8.0f : -INFINITY;
+        if constexpr (HAS_FIRST) sc[i] = (j < nkeys && (j == 0 || j > npad)) ? dot / 8.0f : -INFINITY;
+        else sc[i] = j < nkeys ? dot / 8.0f : -INFINITY;
         cmax = fmaxf(cmax, sc[i]);
     }
     const float m_new = fmaxf(m, cmax);
@@ -645,7 +650,9 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
     m = m_new;
 }
 
-template <bool HAS_SRC, bool F16, bool QONLY = false>
+// HAS_FIRST (never with HAS_SRC): `src` is [S], the padded prompt slots of every sequence (kv16_wave_chunk) - the operand list, and
+// with it every other instantiation, is the one it was
+template <bool HAS_SRC, bool F16, bool QONLY = false, bool HAS_FIRST = false>
 __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                                     u16* __restrict__ kc, u16* __restrict__ vc,
                                                                     const int* __restrict__ step, float* __restrict__ out,
@@ -664,6 +671,7 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     const int s = item / H, hd = item - s * H;
     const float* row = qkv + (size_t)s * ld_qkv;
     const int* srow = HAS_SRC ? src + (size_t)s * T : nullptr;
+    const int npad = HAS_FIRST ? src[s] : 0;
     Kv16Row r;
     r.q0 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8);
     r.q1 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8 + 4);
@@ -678,7 +686,7 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #define KV16_CHUNK(NI_, FIRST_, BASE_) \
-    kv16_wave_chunk<NI_, HAS_SRC, FIRST_, F16, QONLY>(rk, rv, srow, s, hd, H, T, BASE_, nkeys, slot, g, d8, r, q, kn16, vn16, m, l, acc)
+    kv16_wave_chunk<NI_, HAS_SRC, FIRST_, F16, QONLY, HAS_FIRST>(rk, rv, srow, s, hd, H, T, BASE_, nkeys, slot, g, d8, r, q, kn16, vn16, m, l, acc, npad)
     // chunks of 72 keys while more than 72 remain, then ONE chunk sized to what is left in steps of 8 keys (a wave-uniform
     // switch around fully unrolled, unconditional, clamped load blocks - never a branch around a single load).  Round 4:
     // the tail used to be 24 / 48 / 72 keys, i.e. 18 % more rows requested (and exponentiated) than a 128-token decode
@@ -1080,7 +1088,7 @@ int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float*
 
 
 // Greedy many-sequence step in 16-bit mode: the lm_head leaves per-tile arg-max candidates instead of logits (gemm_bf16.hip)
-static bool lm_head_cand_path(const rgrg_decoder* d, int S) {
+bool lm_head_cand_path(const rgrg_decoder* d, int S) {
     return S > decode_row_limit(d) && kv_is_bf16(d, S) && d->xn16 && d->lm_head.wb && d->lm_head.K % 256 == 0 &&
            gemm_bf16_cand_epilogue_ok(S, d->lm_head.N, d->lm_head.K);
 }
@@ -1104,11 +1112,17 @@ struct AttnDecodeLaunch {
     hipStream_t st;
     bool q_only = false;                   // 16-bit cache without src: slot t + 1 already holds the new k / v (c_attn's K/V-cache epilogue) -
                                            // the kernel reads q only and stores nothing to the cache
+    const int* first = nullptr;            // 16-bit cache without src: [S] padded prompt slots, cache slots 1 .. first[s] are left out
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
     if (a.kmask && (a.fmt != KV_F32 || a.src)) {
         set_error("decode attention: the padding mask exists only in the fp32 kernel without an ancestor table (%s)",
                   a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.fmt != KV_F32 ? "16-bit K/V cache" : "beam search");
+        return RGRG_EINVAL;
+    }
+    if (a.first && ((a.fmt != KV_BF16 && a.fmt != KV_F16) || a.src)) {
+        set_error("decode attention: the padded-prompt variant exists for the 16-bit K/V cache without an ancestor table (%s)",
+                  a.src ? "beam search" : a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "fp32 K/V cache: pass the additive mask");
         return RGRG_EINVAL;
     }
     if (a.fmt != KV_F32) {
@@ -1136,8 +1150,11 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
             return launch_attn_decode_kv8(a.qkv, a.ld_qkv, static_cast<uint8_t*>(a.kc), static_cast<uint8_t*>(a.vc), a.step, a.out, a.out16,
                                           a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
 #define KV16_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<__VA_ARGS__>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
-                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.out16)
-        if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true); else KV16_LAUNCH(false, false, true); }
+                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.first ? a.first : a.src, a.out16)
+        if (a.first) {
+            if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true, true); else KV16_LAUNCH(false, false, true, true); }
+            else { if (a.f16) KV16_LAUNCH(false, true, false, true); else KV16_LAUNCH(false, false, false, true); }
+        } else if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true); else KV16_LAUNCH(false, false, true); }
         else if (a.src) { if (a.f16) KV16_LAUNCH(true, true); else KV16_LAUNCH(true, false); }
         else { if (a.f16) KV16_LAUNCH(false, true); else KV16_LAUNCH(false, false); }
 #undef KV16_LAUNCH
@@ -1179,6 +1196,7 @@ static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsig
         a.f16 = d->f16(); a.max_wgs = cap > 0 ? cap * 256 : 0;
         a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kcr; a.vc = kcr + d->kv_kv_stride * esz;
         a.out = d->att + (size_t)r0 * D; a.out16 = att16;
+        a.first = d->kv_first_cur ? d->kv_first_cur + r0 : nullptr;
     } else {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
         a.qkv = d->qkv; a.kc = kc; a.vc = kc + d->kv_kv_stride; a.out = d->att;
@@ -1381,6 +1399,37 @@ static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, i
     return f;
 }
 
+// The end of a step: lm_head over the ln_f rows (d->xn, or xn16 where the step's GEMMs read 16-bit activations).  Beam search and
+// sampling rank the logits themselves; greedy: per-tile arg-max candidates, arg-max and the bookkeeping.
+static int enqueue_head(rgrg_decoder* d, int S, bool count, bool beam, unsigned short* xn16) {
+    hipStream_t st = d->stream;
+    int rc;
+    if (!beam && xn16 && lm_head_cand_path(d, S)) {
+        // greedy: the 256 x 256 lm_head leaves one (maximum, column) pair per row and column tile; no logits, no candidates pass
+        GemmLnFold ce{};
+        ce.cand_val = d->cand_val; ce.cand_idx = d->cand_idx;
+        if ((rc = linear(d, d->lm_head, d->xn, nullptr, nullptr, S, d->ld_logits, RGRG_ACT_NONE, count, xn16, nullptr, &ce))) return rc;
+        if ((rc = trace_mark(d, 0, 1002))) return rc;
+        hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, (d->lm_head.N + 255) / 256, d->ids,
+                           d->max_len, d->finished, d->step, d->done_len, d->sync, S);
+        RGRG_LAUNCH_CHECK();
+        return trace_mark(d, 0, 1003);
+    }
+    if ((rc = linear(d, d->lm_head, d->xn, nullptr, d->logits, S, d->ld_logits, RGRG_ACT_NONE, count, xn16))) return rc;
+    if (beam) return RGRG_OK;  // the caller ranks the logits (beam_row_topk / beam_merge)
+    const int cand_nt = (d->V + 31) / 32;  // ld_logits >= 32 * cand_nt, and the candidate buffers hold lm_head.NT >= cand_nt per row
+    hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, S), dim3(256), 0, st, d->logits, d->ld_logits, d->V,
+                       cand_nt, d->cand_val, d->cand_idx);
+    RGRG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, cand_nt, d->ids,
+                       d->max_len, d->finished, d->step, d->done_len, d->sync, S);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int enqueue_head_argmax(rgrg_decoder* d, int S) {
+    return enqueue_head(d, S, false, false, (kv_is_bf16(d, S) && d->xn16) ? d->xn16 : nullptr);
+}
+
 // One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
 //   embed+ln1 | per layer: c_attn, attention, attn_proj (+ residual), ln2, c_fc+gelu, mlp_proj (+ residual),
 //   ln1 of the next layer / ln_f | lm_head, per-32-column arg-max candidates, argmax + bookkeeping
@@ -1388,7 +1437,6 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
     if (S <= decode_row_limit(d)) return enqueue_step_fused(d, S, count, tok_override, src, beam);
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     d->step_rows = S;
-    hipStream_t st = d->stream;
     const int D = d->D;
     int rc;
     // bf16 many-sequence mode: the GEMM inputs (LayerNorm output, attention output, GELU output) are written ONCE as
@@ -1457,27 +1505,7 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
         return RGRG_OK;
     };
     if ((rc = run_row_ranges(d, S, step_chains(d, S, !beam && !tok_override && !src, fold), run_rows))) return rc;
-    if (!beam && xn16 && lm_head_cand_path(d, S)) {
-        // greedy: the 256 x 256 lm_head leaves one (maximum, column) pair per row and column tile; no logits, no candidates pass
-        GemmLnFold ce{};
-        ce.cand_val = d->cand_val; ce.cand_idx = d->cand_idx;
-        if ((rc = linear(d, d->lm_head, d->xn, nullptr, nullptr, S, d->ld_logits, RGRG_ACT_NONE, count, xn16, nullptr, &ce))) return rc;
-        if ((rc = trace_mark(d, 0, 1002))) return rc;
-        hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, (d->lm_head.N + 255) / 256, d->ids,
-                           d->max_len, d->finished, d->step, d->done_len, d->sync, S);
-        RGRG_LAUNCH_CHECK();
-        return trace_mark(d, 0, 1003);
-    }
-    if ((rc = linear(d, d->lm_head, d->xn, nullptr, d->logits, S, d->ld_logits, RGRG_ACT_NONE, count, xn16))) return rc;
-    if (beam) return RGRG_OK;  // the caller ranks the logits (beam_row_topk / beam_merge)
-    const int cand_nt = (d->V + 31) / 32;  // ld_logits >= 32 * cand_nt, and the candidate buffers hold lm_head.NT >= cand_nt per row
-    hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, S), dim3(256), 0, st, d->logits, d->ld_logits, d->V,
-                       cand_nt, d->cand_val, d->cand_idx);
-    RGRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, cand_nt, d->ids,
-                       d->max_len, d->finished, d->step, d->done_len, d->sync, S);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    return enqueue_head(d, S, count, beam, xn16);
 }
 
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
@@ -1680,9 +1708,10 @@ int decode_begin(rgrg_decoder* d, void* stream) {
     return RGRG_OK;
 }
 int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
-                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len) {
+                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, const DecodePrologue* prologue) {
     int rc = enqueue_prefill(d, feats, S);
     if (rc) return rc;
+    if (prologue && (rc = prologue->fn(d, S, prologue->arg))) return rc;
 
     hipGraphExec_t exec = nullptr;
     if (use_graph) {
@@ -1700,7 +1729,7 @@ int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int g
             d->graphs.push_back({S, exec, graph_key, 0});
         }
     }
-    const int steps = limit - 1;
+    const int steps = limit - 1 - (prologue ? prologue->steps_done : 0);
     int done = 0;
     // "every row has emitted EOS" is polled WITHOUT draining the pipeline: every 16 steps the device-side length word is
     // copied to a pinned slot behind the step that produced it, and the host then waits for the copy it queued 16 steps
@@ -1908,6 +1937,20 @@ extern "C" int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void
     a.qkv = q; a.ld_qkv = ld_q; a.kc = const_cast<void*>(kcache); a.vc = const_cast<void*>(vcache);
     a.plane_elems = (size_t)S * H * T_slots * 64; a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots;
     a.fmt = fp16 ? KV_F16 : KV_BF16; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream); a.q_only = true;
+    return launch_attn_decode(a);
+}
+
+// Test hook: the padded-prompt variant of the 16-bit kernel (attn_decode_kv16_wave_kernel<false, fp16, q_only, true>, the steps of
+// rgrg_decoder_generate_prompted behind a left-padded prompt) through the same launcher: first [S] = padded prompt slots of every row.
+extern "C" int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                                            uint16_t* out16, int S, int H, int T_slots, const int* first, int fp16, int q_only,
+                                            int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && step_dev && first && S > 0 && H > 0 && T_slots >= 2 && (out || out16));
+    RGRG_CHECK_ARG(ld_qkv >= (q_only ? 1 : 3) * H * 64);
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.first = first;
+    a.fmt = fp16 ? KV_F16 : KV_BF16; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream); a.q_only = q_only != 0;
     return launch_attn_decode(a);
 }
 

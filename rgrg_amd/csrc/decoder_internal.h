@@ -82,7 +82,7 @@ struct LayerW {
 
 struct GraphEntry {
     int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3),
-            // 3 = sampling step
+            // 3 = sampling step, 4 = greedy step behind a left-padded prompt (decoder_prompt.hip)
     hipGraphExec_t exec;
     int key2 = 0, key3 = 0;
 };
@@ -202,6 +202,12 @@ struct rgrg_decoder {
     int gemm_launches_per_step = 0;
     const int* pos_override_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached: per-row embedding positions
     int* row_pos = nullptr;                  // [rows] buffer behind it
+    // rgrg_decoder_generate_prompted with a left-padded prompt (decoder_prompt.hip): padded prompt slots of every row, the
+    // prompt's position ids, and - set around the steps on the 16-bit cache, whose kernel skips cache slots 1 .. prompt_pad[s]
+    // instead of adding a mask - the pointer launch_attention hands to attn_decode_kv16_wave_kernel<.., HAS_FIRST>
+    int* prompt_pad = nullptr;               // [rows]
+    long long* prompt_pos = nullptr;         // [rows][max_len]
+    const int* kv_first_cur = nullptr;
     // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
     // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
     int logits_stale_rows = 0;
@@ -235,7 +241,22 @@ int decode_begin(rgrg_decoder* d, void* stream);
 // attn_kv8.hip: attn_decode_kv8_wave_kernel on `workgroups` workgroups of 4 waves (grid and argument rules: launch_attn_decode)
 int launch_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kc, uint8_t* vc, const int* step, float* out, unsigned short* out16,
                            int S, int H, int T, const int* src, int f16, int workgroups, hipStream_t st);
+// prologue: work enqueued between the prefill and the first step that already produced the tokens of steps 0 .. steps_done - 1
+// (a prompt pass, decoder_prompt.hip); the loop then runs the remaining limit - 1 - steps_done steps
+struct DecodePrologue { int (*fn)(rgrg_decoder*, int S, const void* arg); const void* arg; int steps_done; };
 int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
-                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len);
+                    int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len,
+                    const DecodePrologue* prologue = nullptr);
+bool lm_head_cand_path(const rgrg_decoder* d, int S);   // greedy many-sequence 16-bit step: the lm_head leaves arg-max candidates, no logits
+// the end of a greedy step on its own: lm_head over the ln_f rows in d->xn (and d->xn16 where the step plan of S rows reads 16-bit
+// activations), arg-max, record_step_token at *d->step
+int enqueue_head_argmax(rgrg_decoder* d, int S);
+
+// decoder_lm.hip: embedding .. ln_f of the teacher-forced pass over S x T token rows; leaves the ln_f rows in d->tf.xn (the image
+// key / value of every layer must be in d->ukv_out, the work space reserved with tf_reserve).  after_qkv (or NULL) runs behind
+// every layer's c_attn with that layer's q | k | v rows [S*T][3D] (fp32).
+int tf_reserve(rgrg_decoder* d, size_t rows);
+int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
+                   int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr);
 
 }  // namespace rgrg

@@ -426,7 +426,7 @@ static int id_error_end(rgrg_decoder* d) {
 }
 constexpr int TF_LOGIT_ROWS = 2048;  // lm_head + cross entropy run over chunks of this many token rows (412 MB of logits)
 
-static int tf_reserve(rgrg_decoder* d, size_t rows) {
+int tf_reserve(rgrg_decoder* d, size_t rows) {
     if (rows <= d->tf.rows) return RGRG_OK;
     d->tf.free();
     const size_t D = (size_t)d->D;
@@ -469,6 +469,31 @@ static int tf_linear(rgrg_decoder* d, const Lin& l, const float* X, const float*
         return bf16_linear_f32in(d, X, l.wb, l.b, R, Y, M, l.N, l.K, ldy, act);
     return launch_gemm_dense(X, l.w, l.b, R, Y, M, l.N, l.K, ldy, act, d->tf.ws, d->tf.ws_floats, d->stream);
 }
+int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
+                   int (*after_qkv)(rgrg_decoder*, int, const float*, const void*), const void* arg) {
+    const int D = d->D, M = S * T;
+    hipStream_t st = d->stream;
+    int rc;
+    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
+                       d->tf.x, d->tf.xn, D, d->V, d->id_error, pos, pos_rows);
+    RGRG_LAUNCH_CHECK();
+    for (int l = 0; l < d->n_layer; ++l) {
+        const LayerW& w = d->layers[l];
+        const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
+        const float* nb = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_b : d->lnf_b;
+        if ((rc = tf_linear(d, w.c_attn, d->tf.xn, nullptr, d->tf.qkv, M, 3 * D, RGRG_ACT_NONE))) return rc;
+        if (after_qkv && (rc = after_qkv(d, l, d->tf.qkv, arg))) return rc;
+        if ((rc = launch_attn_prefill(d->tf.qkv, d->ukv_out, d->ld_ukv, l * 2 * D, attention_mask, d->tf.att, S, d->H, T, nullptr,
+                                      DropoutParams{0ull, 0u, 0.f}, st)))
+            return rc;
+        if ((rc = tf_linear(d, w.attn_proj, d->tf.att, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
+        if ((rc = launch_ln_rows(d->tf.x, w.ln2_g, w.ln2_b, d->tf.xn, D, nullptr, 0, M, st))) return rc;
+        if ((rc = tf_linear(d, w.c_fc, d->tf.xn, nullptr, d->tf.ff, M, 4 * D, RGRG_ACT_GELU_NEW))) return rc;
+        if ((rc = tf_linear(d, w.mlp_proj, d->tf.ff, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
+        if ((rc = launch_ln_rows(d->tf.x, ng, nb, d->tf.xn, D, nullptr, 0, M, st))) return rc;
+    }
+    return RGRG_OK;
+}
 }  // namespace rgrg
 
 // position_ids of the teacher-forced passes (language_model.py:293-307): `pos` = int64 device array of S * T entries (per sentence)
@@ -502,24 +527,9 @@ extern "C" int rgrg_decoder_lm_forward(rgrg_decoder* d, const float* feats, cons
     if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, S, D, RGRG_ACT_NONE, false))) return rc;
     if ((rc = linear(d, d->ukv, d->img, nullptr, d->ukv_out, S, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
     const long long* ids = reinterpret_cast<const long long*>(input_ids);
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       d->tf.x, d->tf.xn, D, d->V, d->id_error, d->tf.pos, d->tf.pos_rows);
-    RGRG_LAUNCH_CHECK();
+    rc = tf_hidden_pass(d, ids, attention_mask, d->tf.pos, d->tf.pos_rows, S, T);
     d->tf.pos = nullptr; d->tf.pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
-    for (int l = 0; l < d->n_layer; ++l) {
-        const LayerW& w = d->layers[l];
-        const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
-        const float* nb = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_b : d->lnf_b;
-        if ((rc = tf_linear(d, w.c_attn, d->tf.xn, nullptr, d->tf.qkv, M, 3 * D, RGRG_ACT_NONE))) return rc;
-        if ((rc = launch_attn_prefill(d->tf.qkv, d->ukv_out, d->ld_ukv, l * 2 * D, attention_mask, d->tf.att, S, d->H, T, nullptr,
-                                      DropoutParams{0ull, 0u, 0.f}, st)))
-            return rc;
-        if ((rc = tf_linear(d, w.attn_proj, d->tf.att, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
-        if ((rc = launch_ln_rows(d->tf.x, w.ln2_g, w.ln2_b, d->tf.xn, D, nullptr, 0, M, st))) return rc;
-        if ((rc = tf_linear(d, w.c_fc, d->tf.xn, nullptr, d->tf.ff, M, 4 * D, RGRG_ACT_GELU_NEW))) return rc;
-        if ((rc = tf_linear(d, w.mlp_proj, d->tf.ff, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
-        if ((rc = launch_ln_rows(d->tf.x, ng, nb, d->tf.xn, D, nullptr, 0, M, st))) return rc;
-    }
+    if (rc) return rc;
     // lm_head (tied to wte, no bias) and the loss, over chunks of token rows
     for (int r0 = 0; r0 < M; r0 += TF_LOGIT_ROWS) {
         const int rows = (M - r0 < TF_LOGIT_ROWS) ? M - r0 : TF_LOGIT_ROWS;

@@ -741,6 +741,46 @@ class HipEngine:
                    "rgrg_decoder_generate")
         return out[:, :out_len.value].contiguous()
 
+    def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
+                               use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.greedy_search with a prompt (rgrg_decoder_generate_prompted): feats [S,1024], input_ids int64 [S,T],
+        attention_mask [S,T] of zeros (left padding) and ones, or None = ones -> int64 [S, L'], the prompt in front.  One batched
+        pass over the S x T prompt rows fills the decode cache, the decode loop of ``greedy_decode`` continues from there.
+        Token ids are validated like ``forward_cached`` does (IndexError, one read-back); shapes raise ValueError; an all-zero
+        mask row, a mask that is not left padding and the e4m3 cache in use raise RgrgHipError."""
+        _require_gpu(feats.device)
+        _require_gpu(input_ids.device)
+        if input_ids.dim() != 2 or input_ids.shape[1] < 1:
+            raise ValueError(f"input_ids must be [S, T] with T >= 1, got {tuple(input_ids.shape)}")
+        S, T = input_ids.shape
+        if feats.dim() != 2 or feats.shape[0] != S:
+            raise ValueError(f"image_hidden_states must be [S, 1024] with S = {S} rows, got {tuple(feats.shape)}")
+        if input_ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"input_ids must be an integer tensor, got {input_ids.dtype}")
+        ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
+        if bool(((ids < 0) | (ids >= self.vocab)).any()):
+            raise IndexError(f"index out of range in self: a token id is outside [0, {self.vocab})")
+        am = None
+        if attention_mask is not None:
+            _require_gpu(attention_mask.device)
+            if tuple(attention_mask.shape) != (S, T):
+                raise ValueError(f"attention_mask has shape {tuple(attention_mask.shape)}, input_ids {(S, T)}")
+            am = attention_mask.to(device=self.device, dtype=torch.float32).contiguous()
+        limit = int(max_length) if max_length else 1024
+        limit = max(limit, T + 1)   # the reference's loop always produces one token (language_model.py:624-650)
+        if limit > 1024:
+            raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
+        dec = self._get_decoder(S, limit)
+        self._cached = None   # as in greedy_decode
+        self._set_modes(dec, bf16, kv_fp8)
+        feats = feats.to(torch.float32).contiguous()
+        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
+        out_len = C.c_int(0)
+        _hip.check(self.lib.rgrg_decoder_generate_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, _hip.ptr(out),
+                                                           limit, C.byref(out_len), 1 if use_graph else 0, self._s()),
+                   "rgrg_decoder_generate_prompted")
+        return out[:, :out_len.value].contiguous()
+
     def sample_decode(self, feats: Tensor, max_length: Optional[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                       seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True,
                       kv_fp8: bool = False) -> Tuple[Tensor, Tensor]:

@@ -289,6 +289,36 @@ class LanguageModel(EngineOwner):
         return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
+    def greedy_search(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int],
+                      **model_kwargs) -> torch.LongTensor:
+        """language_model.py:609-652 with a prompt: continues ``input_ids`` [S,T] greedily and returns int64 [S, L'], the prompt in
+        front, PAD behind a row's EOS; ``cur_len`` starts at T, one token is always produced, the loop ends at
+        ``cur_len >= max_length`` or when every row has emitted EOS among its GENERATED tokens.  ``model_kwargs`` are the
+        reference's: ``attention_mask`` [S,T] (zeros = LEFT padding; positions are ``cumsum(mask) - 1`` per row as in
+        ``prepare_inputs_for_generation``, :498-520, padded keys stay masked in every later step) and ``use_cache`` (anything
+        but True raises ValueError: the reference's loop feeds one token per step, which needs the cache); any other keyword
+        raises TypeError.  ``attention_mask`` is REQUIRED, as it is in the reference - its ``forward`` dereferences the mask
+        (:281) and ``_update_model_kwargs_for_generation`` indexes it (:524), so a call without one fails there with the
+        AttributeError raised here.  The prompt is run as ONE batched pass into the decode cache (DESIGN.md 7.9);
+        torch.autocast opts into the 16-bit plans exactly as for ``generate``.  A BOS column with a mask of ones IS
+        ``generate()``."""
+        unknown = set(model_kwargs) - {"attention_mask", "use_cache"}
+        if unknown:
+            raise TypeError(f"greedy_search() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+        if model_kwargs.get("use_cache", True) is not True:
+            raise ValueError("greedy_search needs use_cache=True: its loop feeds one token per step on top of the cached keys / values")
+        attention_mask = model_kwargs.get("attention_mask")
+        if attention_mask is None:
+            raise AttributeError("'NoneType' object has no attribute 'to' (greedy_search needs model_kwargs['attention_mask'], like the "
+                                 "reference's forward, language_model.py:281)")
+        from .engine import _require_gpu
+        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
+        self.sync_trainable_if_stale()
+        low = _hip.autocast_mode()
+        return self.engine().greedy_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, bf16=low,
+                                                    kv_fp8=self._kv_fp8())
+
+    @torch.no_grad()
     def generate(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, num_beams: int = 1,
                  num_beam_groups: int = 1, do_sample: bool = False, num_return_sequences: int = 1,
                  early_stopping: bool = False) -> torch.LongTensor:

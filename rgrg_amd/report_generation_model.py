@@ -189,6 +189,31 @@ class ReportGenerationModel(EngineOwner):
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
 
+    @torch.no_grad()
+    def generate_from_prompts(self, images: torch.FloatTensor, region_prompts: torch.LongTensor, region_prompt_mask: torch.Tensor,
+                              max_length: int = None):
+        """``generate`` with every region's sentence started from a prefix: region_prompts int64 [B,29,T] and region_prompt_mask
+        [B,29,T] (zeros = left padding) hold one prompt per region; the prompts of the SELECTED regions are continued by
+        ``LanguageModel.greedy_search``.  Returns the 4-tuple of ``generate`` (output_ids [S,L'] with the prompts in front) or
+        ``-1`` when no region is selected."""
+        B = images.shape[0]
+        if region_prompts.dim() != 3 or tuple(region_prompts.shape[:2]) != (B, 29):
+            raise ValueError(f"region_prompts must be [B, 29, T] with B = {B}, got {tuple(region_prompts.shape)}")
+        if tuple(region_prompt_mask.shape) != tuple(region_prompts.shape):
+            raise ValueError(f"region_prompt_mask has shape {tuple(region_prompt_mask.shape)}, region_prompts {tuple(region_prompts.shape)}")
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        prompts, mask = self.get_valid_decoder_input_for_evaluation(selected_regions, region_prompts.reshape(B * 29, -1),
+                                                                    region_prompt_mask.reshape(B * 29, -1))
+        output_ids = self.language_model.greedy_search(prompts, selected_region_features, max_length, attention_mask=mask, use_cache=True)
+        del selected_region_features
+        return output_ids, selected_regions, detections, class_detected
+
     def set_kv_cache_dtype(self, name: Optional[str]) -> None:
         """``LanguageModel.set_kv_cache_dtype``: None, or "fp8_e4m3" for an e4m3 decode K/V cache under torch.autocast with more than
         64 token rows (no effect otherwise)."""
