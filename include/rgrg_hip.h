@@ -492,6 +492,37 @@ int rgrg_debug_attn_backward_f32(const float* qkv, const float* ukv, int ld_ukv,
 int rgrg_debug_attn_train16(int backward, const uint16_t* qkv16, const uint16_t* ukv16, int ld_ukv, int kcol, const float* am,
                             uint16_t* att16, float* lse, const uint16_t* d_att16, uint16_t* d_qkv16, float* d_ukv, int S, int H,
                             int T, uint64_t seed, uint32_t stream_id, float p, float ukv_scale, int fp16, void* stream);
+/* Test hooks for the row kernels of the training pass (loss.backward() of train_full_model.py:208 through the frozen GPT-2 blocks,
+ * src/language_model/language_model.py:338-399).  As above: the product's own launchers on the caller's device buffers, no decoder
+ * object; rows are 1024 floats.  Dropout (seed, stream_id, p) as rgrg_dropout_mask_f32 with row_len = 0, indexed by flat element.
+ * rgrg_debug_resid_dropout_ln16: resid_dropout_ln16_kernel - x = (resid or 0) + y * mask stored fp32 (y fp32, or y16 in the 16-bit
+ *   type; exactly one of them; y may alias x), xn16 = round16(LayerNorm(x) * g + b).
+ * rgrg_debug_ln_backward: out = (accumulate ? out : 0) + d(LayerNorm input) for the output gradient dy (fp32) or dy16 (exactly one).
+ *   wave_kernel = 0: ln_backward_kernel of the fp32 flow (dy16, out16 or p > 0: RGRG_EINVAL); 1: ln_backward16_kernel, which also
+ *   writes out16 = round16(out * mask) when out16 is given.
+ * rgrg_debug_ce_rows: the shifted cross entropy (:368-396) on rows [row0, row0 + rows) of M = S * T token rows - ce_valid_kernel over
+ *   all M rows, then ce_rows_kernel over the chunk.  logits [rows][ld] = the chunk; ids int64 [M]; am [M] or NULL; row_loss,
+ *   row_valid [M]; row_lse [M] or NULL; *id_error is OR-ed with 1 when a label lies outside [0, V).
+ * rgrg_debug_ce_finalize: loss = sum(row_loss) / sum(row_valid) (NaN when *id_error), *n_scored = sum(row_valid); either may be NULL.
+ * rgrg_debug_ce_backward: d(logits) = (softmax - onehot) * scale / *n_scored on the scored rows of the chunk, 0 on the others, NaN
+ *   when *id_error; out16 == NULL: ce_backward_kernel, in place on logits; else ce_backward16_kernel into out16 [rows][ld] (ld % 4 == 0).
+ *   Columns [V, ld) are never written.
+ * rgrg_debug_gelu: out given: out = gelu_new(pre); d given: d *= gelu_new'(pre); exactly one; n % 4 == 0.
+ * rgrg_debug_dropout_add: out = (resid or 0) + src * mask. */
+int rgrg_debug_resid_dropout_ln16(const float* y, const uint16_t* y16, const float* resid, float* x, const float* g, const float* b,
+                                  uint16_t* xn16, int rows, uint64_t seed, uint32_t stream_id, float p, int fp16, void* stream);
+int rgrg_debug_ln_backward(const float* dy, const uint16_t* dy16, const float* x, const float* g, float* out, uint16_t* out16, int rows,
+                           int accumulate, uint64_t seed, uint32_t stream_id, float p, int fp16, int wave_kernel, void* stream);
+int rgrg_debug_ce_rows(const float* logits, int64_t ld, int V, int row0, int rows, const int64_t* ids, const float* am, int T, int M,
+                       float* row_loss, int* row_valid, float* row_lse, int* id_error, void* stream);
+int rgrg_debug_ce_finalize(const float* row_loss, const int* row_valid, int n, float* loss, int* n_scored, const int* id_error,
+                           void* stream);
+int rgrg_debug_ce_backward(float* logits, int64_t ld, int V, int row0, int rows, const int64_t* ids, const int* row_valid,
+                           const float* row_lse, const int* n_scored, float scale, const int* id_error, uint16_t* out16, int fp16,
+                           void* stream);
+int rgrg_debug_gelu(const float* pre, float* out, float* d, int64_t n, void* stream);
+int rgrg_debug_dropout_add(const float* src, const float* resid, float* out, int64_t n, uint64_t seed, uint32_t stream_id, float p,
+                           void* stream);
 /* ---- detector targets and losses: ObjectDetector.forward(images, targets), the detector half of
  * ReportGenerationModel.forward(images, image_targets, ...) (src/full_model/report_generation_model.py:55,91 ->
  * src/object_detector/object_detector.py:216-224 -> custom_rpn.py:74-83, custom_roi_heads.py:225-242, and underneath

@@ -16,7 +16,7 @@ c_float_p = C.c_void_p  # device pointers travel as void*
 _i, _f, _p = C.c_int, C.c_float, C.c_void_p
 
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
-ABI_VERSION = 26  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
+ABI_VERSION = 27  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
 
 
 class RgrgHipError(RuntimeError):
@@ -96,6 +96,13 @@ SIGNATURES = {
     "rgrg_debug_attn_backward_f32": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, C.c_uint32, _f,
                                           _i, _f, _p]),
     "rgrg_debug_attn_train16": (_i, [_i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _f, _i, _p]),
+    "rgrg_debug_resid_dropout_ln16": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, C.c_uint64, C.c_uint32, _f, _i, _p]),
+    "rgrg_debug_ln_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, C.c_uint64, C.c_uint32, _f, _i, _i, _p]),
+    "rgrg_debug_ce_rows": (_i, [_p, C.c_int64, _i, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "rgrg_debug_ce_finalize": (_i, [_p, _p, _i, _p, _p, _p, _p]),
+    "rgrg_debug_ce_backward": (_i, [_p, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _i, _p]),
+    "rgrg_debug_gelu": (_i, [_p, _p, _p, C.c_int64, _p]),
+    "rgrg_debug_dropout_add": (_i, [_p, _p, _p, C.c_int64, C.c_uint64, C.c_uint32, _f, _p]),
     "rgrg_decoder_copy_last_logits": (_i, [_p, _p, _i, _p]),
     "rgrg_box_match_f32": (_i, [_p, _p, _i, _p, C.c_int64, _p, _i, _i, _f, _f, _i, _p, _p, _p]),
     "rgrg_balanced_sample": (_i, [_p, _p, _i, _p, _p, C.c_uint64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

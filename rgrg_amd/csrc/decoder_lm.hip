@@ -393,6 +393,26 @@ __global__ __launch_bounds__(256) void ce_valid_kernel(const float* __restrict__
     }
 }
 
+// Launchers of the three cross-entropy kernels: the passes below and the test hooks at the end of this file share the grid rules.
+static int launch_ce_valid(const float* am, int T, int M, float* row_loss, int* row_valid, hipStream_t st) {
+    hipLaunchKernelGGL(ce_valid_kernel, dim3((M + 255) / 256), dim3(256), 0, st, am, T, M, row_loss, row_valid);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+// rows [row0, row0 + rows) of the M = S * T token rows; `logits` points at the chunk's first row
+static int launch_ce_rows(const float* logits, size_t ld, int V, int row0, int rows, const long long* ids, const float* am, int T,
+                          float* row_loss, int* row_valid, float* row_lse, int* id_error, hipStream_t st) {
+    hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, row0, ids, am, T, row_loss, row_valid, row_lse, id_error);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+static int launch_ce_finalize(const float* row_loss, const int* row_valid, int n, float* loss, int* n_scored, const int* id_error,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, row_loss, row_valid, n, loss, n_scored, id_error);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
 }  // namespace rgrg
 
 using namespace rgrg;
@@ -535,17 +555,11 @@ extern "C" int rgrg_decoder_lm_forward(rgrg_decoder* d, const float* feats, cons
         const int rows = (M - r0 < TF_LOGIT_ROWS) ? M - r0 : TF_LOGIT_ROWS;
         float* lg = logits_out ? logits_out + (size_t)r0 * d->V : d->tf.logits;
         if ((rc = tf_linear(d, d->lm_head, d->tf.xn + (size_t)r0 * D, nullptr, lg, rows, d->V, RGRG_ACT_NONE))) return rc;
-        if (loss_out) {
-            hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, lg, (size_t)d->V, d->V, r0, ids, attention_mask, T,
-                               d->tf.row_loss, d->tf.row_valid, (float*)nullptr, d->id_error);
-            RGRG_LAUNCH_CHECK();
-        }
+        if (loss_out && (rc = launch_ce_rows(lg, (size_t)d->V, d->V, r0, rows, ids, attention_mask, T, d->tf.row_loss, d->tf.row_valid,
+                                             nullptr, d->id_error, st)))
+            return rc;
     }
-    if (loss_out) {
-        hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf.row_loss, d->tf.row_valid, M, loss_out, (int*)nullptr,
-                           d->id_error);
-        RGRG_LAUNCH_CHECK();
-    }
+    if (loss_out && (rc = launch_ce_finalize(d->tf.row_loss, d->tf.row_valid, M, loss_out, nullptr, d->id_error, st))) return rc;
     if ((rc = id_error_end(d))) return rc;
     // the caller's stream continues after this pass (no host synchronisation)
     RGRG_HIP(hipEventRecord(d->ev_in, st));
@@ -748,26 +762,22 @@ static int tr_body16(rgrg_decoder* d, const long long* ids, const float* attenti
         if ((rc = launch_resid_dropout_ln16(nullptr, y16, xs(2 * l + 1), xs(2 * l + 2), ng, nb, d->tr.xn16, dp(l, 3), f16, M, D, st))) return rc;
     }
     // lm_head + loss + d(logits) + d(ln_f output), chunk by chunk
-    hipLaunchKernelGGL(ce_valid_kernel, dim3((M + 255) / 256), dim3(256), 0, st, attention_mask, T, M, d->tf.row_loss, d->tf.row_valid);
-    RGRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf.row_loss, d->tf.row_valid, M, (float*)nullptr, d->tr.count);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_ce_valid(attention_mask, T, M, d->tf.row_loss, d->tf.row_valid, st))) return rc;
+    if ((rc = launch_ce_finalize(d->tf.row_loss, d->tf.row_valid, M, nullptr, d->tr.count, nullptr, st))) return rc;
     const int chunk = (int)d->tr.chunk;
     for (int r0 = 0; r0 < M; r0 += chunk) {
         const int rows = (M - r0 < chunk) ? M - r0 : chunk;
         if ((rc = tr_lin16(d, d->lm_head, false, d->tr.xn16 + (size_t)r0 * D, nullptr, d->tr.logits, nullptr, rows, VP))) return rc;
-        hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, d->tr.logits, (size_t)VP, V, r0, ids, attention_mask, T,
-                           d->tf.row_loss, d->tf.row_valid, d->tr.row_lse, d->id_error);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_ce_rows(d->tr.logits, (size_t)VP, V, r0, rows, ids, attention_mask, T, d->tf.row_loss, d->tf.row_valid,
+                                 d->tr.row_lse, d->id_error, st)))
+            return rc;
         if ((rc = launch_ce_backward16(d->tr.logits, (size_t)VP, V, r0, rows, ids, d->tf.row_valid, d->tr.row_lse, d->tr.count,
                                        loss_scale * s_int, d->id_error, d->tr.dl16, f16, st)))
             return rc;
         // (fp32: the 16-bit scratch still holds the ln_f rows the lm_head of later chunks reads)
         if ((rc = tr_lin16(d, d->lm_head, true, d->tr.dl16, nullptr, d->tr.dxn + (size_t)r0 * D, nullptr, rows, D))) return rc;
     }
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf.row_loss, d->tf.row_valid, M, loss_out, (int*)nullptr,
-                       d->id_error);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_ce_finalize(d->tf.row_loss, d->tf.row_valid, M, loss_out, nullptr, d->id_error, st))) return rc;
     if ((rc = id_error_end(d))) return rc;
     // backward through ln_f and the 24 frozen blocks; dx16 always carries the mask of the branch the gradient enters next
     if ((rc = launch_ln_backward16(d->tr.dxn, nullptr, xs(2 * L), d->lnf_g, d->tr.dx, d->tr.dx16, M, D, 0, dp(L - 1, 3), f16, st))) return rc;
@@ -869,24 +879,20 @@ extern "C" int rgrg_decoder_lm_loss_grad(rgrg_decoder* d, const float* feats, co
         if ((rc = launch_ln_rows(xs(2 * l + 2), ng, nb, d->tf.xn, D, nullptr, 0, M, st))) return rc;
     }
     // ---------------- lm_head + loss + d(logits) + d(ln_f output), chunk by chunk (the logits never exist as a whole)
-    hipLaunchKernelGGL(ce_valid_kernel, dim3((M + 255) / 256), dim3(256), 0, st, attention_mask, T, M, d->tf.row_loss, d->tf.row_valid);
-    RGRG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf.row_loss, d->tf.row_valid, M, (float*)nullptr, d->tr.count);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_ce_valid(attention_mask, T, M, d->tf.row_loss, d->tf.row_valid, st))) return rc;
+    if ((rc = launch_ce_finalize(d->tf.row_loss, d->tf.row_valid, M, nullptr, d->tr.count, nullptr, st))) return rc;
     for (int r0 = 0; r0 < M; r0 += TF_LOGIT_ROWS) {
         const int rows = (M - r0 < TF_LOGIT_ROWS) ? M - r0 : TF_LOGIT_ROWS;
         if ((rc = tr_lin(d, d->lm_head, false, d->tf.xn + (size_t)r0 * D, nullptr, d->tr.logits, rows, VP))) return rc;
-        hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, st, d->tr.logits, (size_t)VP, V, r0, ids, attention_mask, T,
-                           d->tf.row_loss, d->tf.row_valid, d->tr.row_lse, d->id_error);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_ce_rows(d->tr.logits, (size_t)VP, V, r0, rows, ids, attention_mask, T, d->tf.row_loss, d->tf.row_valid,
+                                 d->tr.row_lse, d->id_error, st)))
+            return rc;
         if ((rc = launch_ce_backward(d->tr.logits, (size_t)VP, V, r0, rows, ids, d->tf.row_valid, d->tr.row_lse, d->tr.count,
                                      loss_scale, d->id_error, st)))
             return rc;
         if ((rc = tr_lin(d, d->lm_head, true, d->tr.logits, nullptr, d->tr.dxn + (size_t)r0 * D, rows, D))) return rc;
     }
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, d->tf.row_loss, d->tf.row_valid, M, loss_out, (int*)nullptr,
-                       d->id_error);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_ce_finalize(d->tf.row_loss, d->tf.row_valid, M, loss_out, nullptr, d->id_error, st))) return rc;
     if ((rc = id_error_end(d))) return rc;
     // ---------------- backward through ln_f and the 24 frozen blocks (activation gradients only)
     if ((rc = launch_ln_backward(d->tr.dxn, xs(2 * L), d->lnf_g, d->tr.dx, M, D, 0, st))) return rc;
@@ -1016,4 +1022,22 @@ extern "C" int rgrg_debug_attn_prefill(const float* qkv, const float* ukv, int l
     RGRG_CHECK_ARG(variant >= 0 && variant <= 3);
     return launch_attn_prefill(qkv, ukv, ld_ukv, kcol, am, out, S, H, T, lse, DropoutParams{seed, stream_id, p}, as_stream(stream), out16,
                                fp16 ? 1 : 0, variant);
+}
+
+// Test hooks: the cross-entropy kernels of the teacher-forced passes alone, through the launchers above.
+// rgrg_debug_ce_rows: ce_valid_kernel over all M rows (as the training pass does first), then ce_rows_kernel over the chunk.
+extern "C" int rgrg_debug_ce_rows(const float* logits, int64_t ld, int V, int row0, int rows, const int64_t* ids, const float* am, int T,
+                                  int M, float* row_loss, int* row_valid, float* row_lse, int* id_error, void* stream) {
+    RGRG_CHECK_ARG(logits && ids && row_loss && row_valid && id_error && V > 0 && ld >= V && T >= 2 && M > 0 && M % T == 0);
+    RGRG_CHECK_ARG(row0 >= 0 && rows > 0 && row0 <= M - rows);
+    int rc = launch_ce_valid(am, T, M, row_loss, row_valid, as_stream(stream));
+    if (rc) return rc;
+    return launch_ce_rows(logits, (size_t)ld, V, row0, rows, reinterpret_cast<const long long*>(ids), am, T, row_loss, row_valid, row_lse,
+                          id_error, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_ce_finalize(const float* row_loss, const int* row_valid, int n, float* loss, int* n_scored, const int* id_error,
+                                      void* stream) {
+    RGRG_CHECK_ARG(row_loss && row_valid && n > 0 && (loss || n_scored));
+    return launch_ce_finalize(row_loss, row_valid, n, loss, n_scored, id_error, as_stream(stream));
 }

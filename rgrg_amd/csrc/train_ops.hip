@@ -757,3 +757,49 @@ extern "C" int rgrg_debug_attn_backward_f32(const float* qkv, const float* ukv, 
     return launch_attn_backward(qkv, ukv, ld_ukv, kcol, am, d_att, att, lse, delta, d_qkv, d_ukv, S, H, T, DropoutParams{seed, stream_id, p},
                                 as_stream(stream), d_qkv16, fp16 ? 1 : 0, ukv_scale);
 }
+
+// Test hooks: the row kernels of the training pass alone, on the caller's buffers, through the launchers above.
+extern "C" int rgrg_debug_resid_dropout_ln16(const float* y, const uint16_t* y16, const float* resid, float* x, const float* g,
+                                             const float* b, uint16_t* xn16, int rows, uint64_t seed, uint32_t stream_id, float p,
+                                             int fp16, void* stream) {
+    RGRG_CHECK_ARG(g && b && p >= 0.f && p < 1.f);
+    return launch_resid_dropout_ln16(y, y16, resid, x, g, b, xn16, DropoutParams{seed, stream_id, p}, fp16 ? 1 : 0, rows, 1024,
+                                     as_stream(stream));
+}
+
+// wave_kernel = 0: ln_backward_kernel (fp32 flow, one workgroup per row); 1: ln_backward16_kernel (16-bit flow, one wave per row)
+extern "C" int rgrg_debug_ln_backward(const float* dy, const uint16_t* dy16, const float* x, const float* g, float* out, uint16_t* out16,
+                                      int rows, int accumulate, uint64_t seed, uint32_t stream_id, float p, int fp16, int wave_kernel,
+                                      void* stream) {
+    RGRG_CHECK_ARG(x && g && out && p >= 0.f && p < 1.f);
+    if (!wave_kernel) {
+        RGRG_CHECK_ARG(dy && !dy16 && !out16 && p == 0.f);
+        return launch_ln_backward(dy, x, g, out, rows, 1024, accumulate ? 1 : 0, as_stream(stream));
+    }
+    return launch_ln_backward16(dy, dy16, x, g, out, out16, rows, 1024, accumulate ? 1 : 0, DropoutParams{seed, stream_id, p},
+                                fp16 ? 1 : 0, as_stream(stream));
+}
+
+// out16 == NULL: ce_backward_kernel, in place on `logits`; else ce_backward16_kernel (its vector loads / stores need ld % 4 == 0)
+extern "C" int rgrg_debug_ce_backward(float* logits, int64_t ld, int V, int row0, int rows, const int64_t* ids, const int* row_valid,
+                                      const float* row_lse, const int* n_scored, float scale, const int* id_error, uint16_t* out16,
+                                      int fp16, void* stream) {
+    RGRG_CHECK_ARG(logits && ids && row_valid && row_lse && n_scored && id_error && V > 0 && ld >= V && row0 >= 0 && rows > 0);
+    const long long* tok = reinterpret_cast<const long long*>(ids);
+    if (!out16) return launch_ce_backward(logits, (size_t)ld, V, row0, rows, tok, row_valid, row_lse, n_scored, scale, id_error, as_stream(stream));
+    RGRG_CHECK_ARG(ld % 4 == 0);
+    return launch_ce_backward16(logits, (size_t)ld, V, row0, rows, tok, row_valid, row_lse, n_scored, scale, id_error, out16, fp16 ? 1 : 0,
+                                as_stream(stream));
+}
+
+// out: out = gelu_new(pre) (gelu_apply_kernel); d: d *= gelu_new'(pre) (gelu_backward_kernel).  Four elements per thread.
+extern "C" int rgrg_debug_gelu(const float* pre, float* out, float* d, int64_t n, void* stream) {
+    RGRG_CHECK_ARG(pre && ((out != nullptr) != (d != nullptr)) && n > 0 && n % 4 == 0);
+    return out ? launch_gelu_apply(pre, out, (size_t)n, as_stream(stream)) : launch_gelu_backward(d, pre, (size_t)n, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_dropout_add(const float* src, const float* resid, float* out, int64_t n, uint64_t seed, uint32_t stream_id,
+                                      float p, void* stream) {
+    RGRG_CHECK_ARG(src && out && n > 0 && p >= 0.f && p < 1.f);
+    return launch_dropout_add(src, resid, out, (size_t)n, DropoutParams{seed, stream_id, p}, as_stream(stream));
+}

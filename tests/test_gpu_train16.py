@@ -2,7 +2,8 @@
 torch.autocast, src/full_model/train_full_model.py:172-237) and the kernels under it - the 256 x 256 ping-pong GEMM with the
 training epilogues, the fused residual / dropout / LayerNorm and LayerNorm-backward kernels, the 16-bit cross-entropy
 gradient.  The fp32 pass (pinned against the real reference's autograd by tests/golden/lm_grads*.pt) is the yardstick of the
-16-bit passes; tolerances are the 16-bit noise levels written next to each check."""
+16-bit passes; tolerances are the 16-bit noise levels written next to each check.  The three row kernels named above are tested
+one by one against a float64 reference in tests/test_gpu_train_rows.py; here they run inside the whole pass."""
 import math
 
 import pytest
@@ -182,6 +183,37 @@ def test_fp16_training_gradients_keep_their_small_values():
     for k, r in g32.items():
         if r.dim() == 1 and r.numel() >= 1024:
             assert abs(g16[k].norm().item() / r.norm().item() - 1) <= 0.05, k
+    m.invalidate_engine()
+
+
+def test_fp16_flow_with_few_scored_tokens():
+    """Padding leaves few scored tokens among many rows: 29 sentences x 40 tokens = 1160 rows (the 16-bit flow), one sentence of
+    full length and 28 of length 2, so 39 + 28 = 67 tokens are scored.  d(logits) is proportional to 1 / n_scored and carries the
+    flow's internal 2^15 under float16: here the 16-bit gradients are 25 times larger than in the test above, the nearest the
+    flow comes to fp16's largest finite value.  Every gradient finite; cosine >= 0.99 and norms within 3 % of the fp32 pass, bias
+    norms within 5 % (the figures of the test above)."""
+    m = _lm_train_model()
+    m.language_model.train()
+    S, T = 29, 40
+    g = torch.Generator().manual_seed(29)
+    ids = torch.randint(0, 50257, (S, T), generator=g)
+    lens = torch.full((S,), 2)
+    lens[0] = T
+    am = (torch.arange(T)[None, :] < lens[:, None]).to(torch.int64)
+    feats = torch.randn((S, 1024), generator=g)
+    assert int(am[:, 1:].sum()) == 67
+    l32, g32 = _grads(m, ids, am, feats, None)
+    l16, g16 = _grads(m, ids, am, feats, torch.float16)
+    assert set(g16) == set(g32)
+    for k, v in g16.items():
+        assert bool(torch.isfinite(v).all()), k
+    bias = max(abs(g16[k].norm().item() / r.norm().item() - 1) for k, r in g32.items() if r.dim() == 1 and r.numel() >= 1024)
+    cos, nr, k = _compare(g16, g32, 0.0, math.inf)   # the figures first, then the assertions
+    print(f"TRAINROWS kernel=tr_body16 case=fp16,few_scored loss32={l32:.6f} loss16={l16:.6f} worst_cos={cos:.5f} its_norm_err={nr:.5f} "
+          f"tensor={k} worst_bias_norm_err={bias:.5f}")
+    assert math.isfinite(l16) and abs(l16 - l32) <= 3e-2
+    _compare(g16, g32, 0.99, 0.03)
+    assert bias <= 0.05
     m.invalidate_engine()
 
 

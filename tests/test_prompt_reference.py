@@ -78,10 +78,11 @@ def test_greedy_search_argument_errors_need_no_gpu():
 def test_header_declares_the_new_entries_like_the_binding():
     with open(os.path.join(REPO, "include", "rgrg_hip.h")) as f:
         header = f.read()
-    for name in ("rgrg_decoder_generate_prompted", "rgrg_debug_attn_decode_first"):
+    for name in ("rgrg_decoder_generate_prompted", "rgrg_debug_attn_decode_first", "rgrg_debug_resid_dropout_ln16", "rgrg_debug_ln_backward",
+                 "rgrg_debug_ce_rows", "rgrg_debug_ce_finalize", "rgrg_debug_ce_backward", "rgrg_debug_gelu", "rgrg_debug_dropout_add"):
         m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
         assert m, name
         assert len(m.group(1).split(",")) == len(_hip.SIGNATURES[name][1]), name
     declared = set(re.findall(r"\b(rgrg_[a-z0-9_]+)\s*\(", header))
     assert set(_hip.SIGNATURES) <= declared
-    assert _hip.ABI_VERSION == 26
+    assert _hip.ABI_VERSION == 27   # 26 brought the prompted entries, 27 the hooks of the training pass's row kernels
