@@ -433,6 +433,10 @@ int rgrg_debug_linear_bf16_ln_kv(const uint16_t* A16, const uint16_t* Wb, const 
 int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t* Wb, const float* shift, const float* R, float* Y,
                                  uint16_t* Y16, uint16_t* Yb16, float* stats_out, const float* ln_stats, const float* ln_colsum,
                                  int M, int N, int K, int ldy, int act, int fp16, int kp, void* stream);
+/* How many GEMM launches of this process took the staged epilogue (csrc/gemm_kp.inc, WIDE: the 64 x 64 producer leaves its tile in
+ * LDS and stores whole rows, 16 bytes per lane).  RGRG_WIDE_EPI=0, read per launch, keeps the epilogue that stores from the MFMA's
+ * C layout; a test that compares the two reads this counter to know which one a launch ran. */
+int rgrg_debug_wide_epilogue_launches(void);
 /* Test hooks for the attention kernels (GPT2PseudoAttention, src/language_model/language_model.py: _attn :84-122 - scores / 8,
  * future token columns replaced by -1e4, the additive padding mask (1 - [1 | attention_mask]) * -1e4 of :316-334, softmax,
  * attn_dropout :116, the product with V - and forward :124-160, which puts the image key / value uk(img) / uv(img) in front of

@@ -12,6 +12,8 @@
 // path is opt-in (torch.autocast) and its tests are tolerance-based.
 #include "internal.h"
 
+#include <atomic>
+
 namespace rgrg {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -1504,6 +1506,8 @@ extern "C" int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t*
     f.Yb16 = Yb16; f.stats_out = stats_out; f.ln_stats = ln_stats; f.ln_colsum = ln_colsum; f.kp = kp;
     return launch_gemm_bf16w_ex(nullptr, A16, Wb, shift, R, Y, Y16, M, N, K, ldy, act, as_stream(stream), fp16, &f);
 }
+
+extern "C" int rgrg_debug_wide_epilogue_launches(void) { return kp_wide_launches.load(std::memory_order_relaxed); }
 
 // nn.Conv2d (+ folded eval BatchNorm + residual + ReLU) as an implicit GEMM on the bf16 matrix core, for the detector
 // under torch.autocast (the reference runs trunk / RPN in half precision there, generate_reports_for_images.py:108).

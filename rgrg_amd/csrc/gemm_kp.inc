@@ -29,7 +29,25 @@
 // shapes.  128 KiB of LDS for the shapes that matter: one workgroup per CU.  Selected by the decoder for the many-sequence step
 // only (GemmLnFold::kp); the tile is a function of the GEMM, never of M, so a row's bits do not depend on the row range it is
 // launched in.
-template <int BM, int BN, int NST, bool F16, int LNF>
+//
+// WIDE (64 x 64 producer only: attn_proj / mlp_proj of the step): the epilogue goes through LDS instead of working straight from
+// the C layout of the 32x32 MFMA, where a lane owns 16 single elements and every load / store instruction moves 4 (fp32) or 2
+// (16-bit) bytes per lane.  Every one of the 512 threads requests 32 bytes of the residual tile (row tid / 8, 8 columns) ahead of
+// the operand stream; after the K loop the stages of group 0 are free and hold two 64 x 64 fp32 tiles, residual and result;
+// group 0 computes what it always computed (even + odd K tiles, + shift, + residual, to16, the statistics butterfly) but takes
+// the residual from the first tile and leaves the value in the second; after the barrier of the statistics exchange all eight
+// waves store whole rows, 16 bytes per lane.  ~44 vector-memory instructions per workgroup instead of ~260, same bytes, same
+// bits.  The launcher takes it only without an activation (a producer writes the residual stream), so the 16 scalar switches on
+// p.act per lane are gone as well - they cost as much as the narrow accesses did.  Measured (profiles/wide_epilogue_ab.md, cold
+// weights): attn_proj 9.8 -> 8.8 us and mlp_proj 20.4 -> 19.3 us on a 231-row range, 10.2 -> 9.4 / 20.9 -> 20.3 us at 923 rows;
+// the epilogue's share (RGRG_PP_DBG bit 8) 2.7 -> 1.7 / 2.7 -> 1.9 us; 77 -> 73 VGPRs.  RGRG_WIDE_EPI=0 (read per launch)
+// keeps the C-layout epilogue.  Tile image: rows of 256 B, the 16-byte chunk c of row r sits at chunk
+// c ^ (c >> 3 & 1) ^ (r >> 1 & 1): element accesses in C layout (32 lanes = 32 consecutive floats), the 16-byte writes of a row
+// (8 lanes, chunks 2 i + j) and the 16-byte reads (ds_read_b128: lane groups of 4 rows x 4 chunks) are all free of bank conflicts.
+__device__ __forceinline__ int kp_wide_off(int row, int chunk) {   // float index of the first element of a 16-byte chunk
+    return row * 64 + ((chunk ^ ((chunk >> 3) & 1) ^ ((row >> 1) & 1)) << 2);
+}
+template <int BM, int BN, int NST, bool F16, int LNF, bool WIDE = false>
 __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params p, const int mtiles, const int ntiles) {
     constexpr int BK = 64;
     constexpr int MI = BM / 64, NI = BN / 64;   // 32x32 MFMA blocks per wave
@@ -37,10 +55,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
     constexpr int PPW = LA + LB;
     constexpr int STAGE = (BM + BN) * 128;
     constexpr int GROUP = NST * STAGE;          // LDS of one group
-    constexpr int TAG = 2000 + (BM == 128 ? 512 : 0) + (BN == 128 ? 256 : 0) + LNF * 64 + NST * 4 + (F16 ? 1 : 0);
+    constexpr int TAG = 2000 + (BM == 128 ? 512 : 0) + (BN == 128 ? 256 : 0) + LNF * 64 + NST * 4 + (F16 ? 1 : 0) + (WIDE ? 2000 : 0);
     static_assert(NST >= 2 && NST <= 4, "tail is written for up to 3 trailing tiles");
     static_assert((NST - 2) * PPW < 64, "counted vmcnt out of range");
     static_assert(4 * MI * NI * 4096 <= GROUP, "group 1's accumulators must fit its own stages");
+    static_assert(!WIDE || (BM == 64 && BN == 64 && LNF == 1 && GROUP >= 2 * 64 * 256), "the staged epilogue is the 64 x 64 producer's");
     extern __shared__ __attribute__((aligned(16))) unsigned char kp_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -106,7 +125,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
             sh_pre[mi][ni] = p.shift ? p.shift[colc] : 0.f;
             cs_pre[mi][ni] = LNF == 2 ? p.ln_colsum[colc] : 0.f;
         }
-    constexpr bool PRE_R = MI * NI == 1 && LNF != 2;
+    constexpr bool PRE_R = MI * NI == 1 && LNF != 2 && !WIDE;
     float rv_pre[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) rv_pre[r] = 0.f;
@@ -120,6 +139,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                 rv_pre[r] = p.R[(size_t)row * p.ldy + colc];
             }
         }
+    }
+    // WIDE: this thread's 32 bytes of the residual tile (the launcher checks R, N % 64 == 0 and the alignment)
+    const int wrow = tid >> 3, wch = tid & 7;
+    f32x4 rw0 = {0.f, 0.f, 0.f, 0.f}, rw1 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (WIDE) {
+        const f32x4* rp = reinterpret_cast<const f32x4*>(p.R + (size_t)min(m0 + wrow, p.M - 1) * p.ldy + n0 + wch * 8);
+        rw0 = rp[0]; rw1 = rp[1];
     }
     constexpr int TPR = 256 / BM, PER = 16 / TPR;   // consumer of a folded LayerNorm: 16 statistics slots per row
     f32x4 lsq[PER / 2];
@@ -216,6 +242,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                     for (int q = 0; q < 4; ++q)
                         dump[((mi * NI + ni) * 4 + q) * 64] = f32x4{acc[mi][ni][4 * q], acc[mi][ni][4 * q + 1], acc[mi][ni][4 * q + 2], acc[mi][ni][4 * q + 3]};
         }
+        if constexpr (WIDE) {   // all eight waves: the residual tile into group 0's stages (its last read lies two barriers back)
+            if (!(dbg & 8)) {
+                float* rt = reinterpret_cast<float*>(kp_smem);
+                *reinterpret_cast<f32x4*>(rt + kp_wide_off(wrow, 2 * wch)) = rw0;
+                *reinterpret_cast<f32x4*>(rt + kp_wide_off(wrow, 2 * wch + 1)) = rw1;
+            }
+        }
         __syncthreads();
         if (g == 0) {
 #pragma unroll
@@ -256,6 +289,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
     float blk1[MI], blk2[MI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) { blk1[mi] = 0.f; blk2[mi] = 0.f; }
+    // WIDE: the lane's elements in the two LDS tiles (C layout: rows crow4 + dr of the wave's 32, column ccol); the row bit of
+    // the chunk swizzle is bit 1 of dr
+    float* const wide_res = reinterpret_cast<float*>(kp_smem);
+    float* const wide_out = wide_res + 64 * 64;
+    const int wide_c = wn * 8 + (ccol >> 2);
+    const int wide_e0 = (wm * 32 + crow4) * 64 + ((wide_c ^ wn) << 2) + (ccol & 3);
+    const int wide_e1 = (wm * 32 + crow4) * 64 + ((wide_c ^ wn ^ 1) << 2) + (ccol & 3);
     if (g == 0) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
@@ -268,7 +308,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                 float rv[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) rv[r] = rv_pre[r];
-                if (!PRE_R && LNF != 2 && p.R) {
+                if constexpr (WIDE) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) rv[r] = wide_res[((r & 2) ? wide_e1 : wide_e0) + ((r & 3) + 8 * (r >> 2)) * 64];
+                }
+                if (!PRE_R && !WIDE && LNF != 2 && p.R) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
@@ -284,11 +328,17 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                         const float2 st = row_stat[lrow0 + (r & 3) + 8 * (r >> 2)];
                         vv[r] = apply_act_fast(st.y * (acc[mi][ni][r] - st.x * cs) + sh + rv[r], p.act);
                     }
+                } else if constexpr (WIDE) {   // no activation (the launcher checks): 16 scalar switches on p.act less
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) vv[r] = acc[mi][ni][r] + sh + rv[r];
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) vv[r] = apply_act_fast(acc[mi][ni][r] + sh + rv[r], p.act);
                 }
-                if (col < p.N) {
+                if constexpr (WIDE) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) wide_out[((r & 2) ? wide_e1 : wide_e0) + ((r & 3) + 8 * (r >> 2)) * 64] = vv[r];
+                } else if (col < p.N) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int dr = (r & 3) + 8 * (r >> 2);
@@ -334,6 +384,22 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
             }
             __syncthreads();
         }
+        if constexpr (WIDE) {   // all eight waves: whole rows of the finished tile, 8 columns per thread
+            const f32x4 o0 = *reinterpret_cast<const f32x4*>(wide_out + kp_wide_off(wrow, 2 * wch));
+            const f32x4 o1 = *reinterpret_cast<const f32x4*>(wide_out + kp_wide_off(wrow, 2 * wch + 1));
+            if (m0 + wrow < p.M) {
+                const size_t o = (size_t)(m0 + wrow) * p.ldy + n0 + wch * 8;
+                *reinterpret_cast<f32x4*>(p.Y + o) = o0;
+                *reinterpret_cast<f32x4*>(p.Y + o + 4) = o1;
+                u32x4 h;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    h[e] = (unsigned)(u16)to16<F16>(o0[2 * e]) | ((unsigned)(u16)to16<F16>(o0[2 * e + 1]) << 16);
+                    h[2 + e] = (unsigned)(u16)to16<F16>(o1[2 * e]) | ((unsigned)(u16)to16<F16>(o1[2 * e + 1]) << 16);
+                }
+                *reinterpret_cast<u32x4*>(p.Yb16 + o) = h;
+            }
+        }
         if (g == 0 && !(lane & 1) && (NI == 2 || wn == 0)) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
@@ -355,6 +421,7 @@ static int kp_attr() {
     constexpr int lds = 2 * NST * (BM + BN) * 128 + BM * 16;
 #define RGRG_KP_ATTR(...) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kp_kernel<BM, BN, NST, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
     RGRG_KP_ATTR(false, 0); RGRG_KP_ATTR(true, 0); RGRG_KP_ATTR(false, 1); RGRG_KP_ATTR(true, 1); RGRG_KP_ATTR(false, 2); RGRG_KP_ATTR(true, 2);
+    if constexpr (BM == 64 && BN == 64) { RGRG_KP_ATTR(false, 1, true); RGRG_KP_ATTR(true, 1, true); }
 #undef RGRG_KP_ATTR
     return RGRG_OK;
 }
@@ -364,6 +431,20 @@ static int kp_attr() {
 static bool kp_eligible(const GemmBf16Params& p, int nst) {
     return !p.cCin && !p.R16 && !p.Ypre16 && !p.G16 && !p.cand_val && p.ksplit <= 1 && p.K % 128 == 0 && p.K / 128 >= nst &&
            !(p.ln_colsum && p.R);
+}
+
+// RGRG_WIDE_EPI, read per launch like RGRG_PP_DBG (A/B runs and tests compare both epilogues in one process): unset or 1 = the
+// 64 x 64 producer stages its tile in LDS and stores whole rows (WIDE above), 0 = the epilogue that works from the C layout
+static std::atomic<int> kp_wide_launches{0};   // rgrg_debug_wide_epilogue_launches
+static bool kp_wide_enabled() {
+    const char* e = getenv("RGRG_WIDE_EPI");
+    return !e || (atoi(e) & 1) != 0;
+}
+// the staged epilogue moves 16-byte pieces of whole 64-column rows: fp32 residual in, fp32 and 16-bit result out, no activation
+// (a producer writes the residual stream)
+static bool kp_wide_ok(const GemmBf16Params& p) {
+    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    return p.Yb16 && p.stats_out && p.R && p.Y && !p.Y16 && p.act == RGRG_ACT_NONE && p.N % 64 == 0 && p.ldy % 8 == 0 && al16(p.R) && al16(p.Y) && al16(p.Yb16);
 }
 
 template <int BM, int BN, int NST>
@@ -377,8 +458,14 @@ static int launch_kp_cfg(const GemmBf16Params& p0, hipStream_t st) {
     }
     { const char* e = getenv("RGRG_PP_DBG"); p.dbg = e ? atoi(e) : 0; }
     constexpr int lds = 2 * NST * (BM + BN) * 128 + BM * 16;
-#define RGRG_KP_LAUNCH(F16_, LNF_) hipLaunchKernelGGL((gemm_bf16_kp_kernel<BM, BN, NST, F16_, LNF_>), dim3(mtiles * ntiles), dim3(512), lds, st, p, mtiles, ntiles)
-    if (p.Yb16) { if (p.f16) RGRG_KP_LAUNCH(true, 1); else RGRG_KP_LAUNCH(false, 1); }
+#define RGRG_KP_LAUNCH(...) hipLaunchKernelGGL((gemm_bf16_kp_kernel<BM, BN, NST, __VA_ARGS__>), dim3(mtiles * ntiles), dim3(512), lds, st, p, mtiles, ntiles)
+    bool wide = false;
+    if constexpr (BM == 64 && BN == 64) wide = kp_wide_enabled() && kp_wide_ok(p);
+    if (wide) {
+        kp_wide_launches.fetch_add(1, std::memory_order_relaxed);
+        if constexpr (BM == 64 && BN == 64) { if (p.f16) RGRG_KP_LAUNCH(true, 1, true); else RGRG_KP_LAUNCH(false, 1, true); }
+    }
+    else if (p.Yb16) { if (p.f16) RGRG_KP_LAUNCH(true, 1); else RGRG_KP_LAUNCH(false, 1); }
     else if (p.ln_colsum) { if (p.f16) RGRG_KP_LAUNCH(true, 2); else RGRG_KP_LAUNCH(false, 2); }
     else { if (p.f16) RGRG_KP_LAUNCH(true, 0); else RGRG_KP_LAUNCH(false, 0); }
 #undef RGRG_KP_LAUNCH
