@@ -224,6 +224,14 @@ int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feats, const in
 int rgrg_decoder_sample(rgrg_decoder* d, const float* feats, int S, int max_length, float temperature, int top_k, float top_p,
                         uint64_t seed, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph,
                         void* stream);
+/* LanguageModel.sample_from_prompt: rgrg_decoder_generate_prompted with every arg-max replaced by the draw of rgrg_decoder_sample -
+ * the same prompt pass, mask rules, max_length and refusals; the token behind the prompt is drawn from the logits of the S
+ * last-position rows.  The Philox counter of row r for the token in column c is (r, c - 1) - the device step word - so a [S,1] BOS
+ * prompt with a mask of ones uses the counters of rgrg_decoder_sample.  out_logprobs f32 [S,out_ld] or NULL: 0 in the prompt
+ * columns and for the PAD of finished rows.  A mask of ones replays the captured sampling step, a padded prompt its own. */
+int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S, int T,
+                                 int max_length, float temperature, int top_k, float top_p, uint64_t seed, int64_t* out_ids, int out_ld,
+                                 float* out_logprobs, int* out_len, int use_graph, void* stream);
 /* The same sampler on caller-provided logits [S][ld] (V <= 53248; 16-byte loads when ld % 4 == 0 and logits is 16-byte
  * aligned): row s is drawn with the counter (row0 + s, step).  out_tok int32 [S], out_logprob f32 [S] or NULL. */
 int rgrg_sample_logits_f32(const float* logits, int64_t ld, int S, int V, float temperature, int top_k, float top_p,
@@ -240,6 +248,19 @@ int rgrg_sample_logits_f32(const float* logits, int64_t ld, int S, int V, float 
 int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length,
                              int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
                              int out_ld, int* out_len, void* stream);
+/* LanguageModel.beam_search with a prompt (language_model.py:529-607): rgrg_decoder_beam_search that continues input_ids int64 [S,T],
+ * ONE prompt per item (the num_beams rows the reference expands an item into are equal).  attention_mask f32 [S,T] or NULL, with
+ * the rules and refusals of rgrg_decoder_generate_prompted.  The prompt runs as ONE teacher-forced pass over S x T token rows - not
+ * S x num_beams x T -: its keys / values live once, in cache row s * num_beams, and every beam row reaches them through the
+ * per-slot ancestor table.  The first ranking is the reference's first iteration on num_beams identical rows: the logits of the
+ * item's last prompt position with beam scores [0, -1e9, ...].  A mask of ones then replays the captured beam steps of
+ * rgrg_decoder_beam_search, a padded prompt steps of its own (per-item positions, padded slots left out of every later step).
+ * Hypothesis lengths and the is_done length count the prompt, padding included (hyp.shape[-1] and cur_len of the reference).
+ *   RGRG_EINVAL (with a message): max_length < T + 1 (finalize cannot hold a longer hypothesis) or > max_len of the decoder; the
+ *   mask refusals of rgrg_decoder_generate_prompted; the e4m3 K/V cache in use for S * num_beams rows. */
+int rgrg_decoder_beam_search_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
+                                      int T, int num_beams, int max_length, int early_stopping, float length_penalty,
+                                      int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream);
 /* Opt-in reduced precision for MANY sequences (BASELINE configs[2], batch 32): mode 1 (bfloat16) / 2 (float16) makes the
  * > 128-row paths run their projections on the 16-bit MFMA (16-bit weights and GEMM inputs, fp32 accumulate / LayerNorm /
  * softmax / residual) and keep the decode K/V cache in that type (what the reference's torch.autocast does to `present`);
@@ -466,6 +487,15 @@ int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void* kcache, c
 int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
                                  uint16_t* out16, int S, int H, int T_slots, const int* first, int fp16, int q_only,
                                  int max_workgroups, void* stream);
+/* rgrg_debug_attn_decode_beam_first: a beam step behind a left-padded prompt (rgrg_decoder_beam_search_prompted) - ancestor table
+ * src [S][T_slots] AND first int32 [S] together (first is constant inside a beam group in the product; any values in [0, t] here).
+ *   kv16 = 1: attn_decode_kv16_wave_kernel<true, fp16, false, true>, slots 1 .. first[s] left out of the softmax;
+ *   kv16 = 0: attn_decode_kernel<true, ni, true> on the additive mask the product builds from `first` (-1e4 on slots
+ *             1 .. first[s], 0 elsewhere), held in a buffer this call allocates and frees (it synchronises `stream`).
+ * Everything else as rgrg_debug_attn_decode (no frag_out).  RGRG_EINVAL: no src, no first, H % 4 with kv16, ni outside {0, 2, 9}. */
+int rgrg_debug_attn_decode_beam_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                                      uint16_t* out16, int S, int H, int T_slots, const int* src, const int* first, int kv16, int fp16,
+                                      int ni, int max_workgroups, void* stream);
 /* rgrg_debug_attn_decode_kv8: the same step on an e4m3 cache (rgrg_decoder_set_kv_format), attn_decode_kv8_wave_kernel<src, fp16>:
  * kcache / vcache [S][H][T_slots][64] BYTES; the new k / v are stored to slot t + 1 as clamp(+-448) + one rounding to nearest even;
  * the result goes to out16 (fp16 = 0 bf16 / 1 IEEE half) when given, else to out (fp32); max_workgroups > 0 caps the grid.

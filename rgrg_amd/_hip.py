@@ -60,6 +60,8 @@ SIGNATURES = {
     "rgrg_decoder_sample": (_i, [_p, _p, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_sample_logits_f32": (_i, [_p, C.c_int64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p]),
     "rgrg_decoder_beam_search": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
+    "rgrg_decoder_beam_search_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
+    "rgrg_decoder_sample_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_decoder_set_precision": (_i, [_p, _i]),
     "rgrg_decoder_set_kv_format": (_i, [_p, _i]),
     "rgrg_decoder_kv_format_in_use": (_i, [_p, _i]),
@@ -92,6 +94,7 @@ SIGNATURES = {
     "rgrg_debug_linear_bf16_ln_kv": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_qonly": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_first": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p]),
+    "rgrg_debug_attn_decode_beam_first": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_kv8": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "rgrg_debug_attn_prefill": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _i, _p]),
     "rgrg_debug_attn_backward_f32": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, C.c_uint32, _f,

@@ -650,14 +650,15 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
     m = m_new;
 }
 
-// HAS_FIRST (never with HAS_SRC): `src` is [S], the padded prompt slots of every sequence (kv16_wave_chunk) - the operand list, and
-// with it every other instantiation, is the one it was
+// HAS_FIRST without HAS_SRC: `src` is [S], the padded prompt slots of every sequence (kv16_wave_chunk).  HAS_FIRST with HAS_SRC
+// (beam search from a left-padded prompt, rgrg_decoder_beam_search_prompted): `src` is the ancestor table and the padded slots
+// come in `first` [S], an operand only that instantiation reads
 template <bool HAS_SRC, bool F16, bool QONLY = false, bool HAS_FIRST = false>
 __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                                     u16* __restrict__ kc, u16* __restrict__ vc,
                                                                     const int* __restrict__ step, float* __restrict__ out,
                                                                     int S, int H, int T, const int* __restrict__ src,
-                                                                    u16* __restrict__ out16) {
+                                                                    u16* __restrict__ out16, const int* __restrict__ first = nullptr) {
     const int lane = threadIdx.x & 63;
     const int t = *step, nkeys = t + 2, slot = t + 1;
     const int g = lane >> 3, d8 = lane & 7;
@@ -671,7 +672,7 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     const int s = item / H, hd = item - s * H;
     const float* row = qkv + (size_t)s * ld_qkv;
     const int* srow = HAS_SRC ? src + (size_t)s * T : nullptr;
-    const int npad = HAS_FIRST ? src[s] : 0;
+    const int npad = HAS_FIRST ? (HAS_SRC ? first[s] : src[s]) : 0;
     Kv16Row r;
     r.q0 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8);
     r.q1 = *reinterpret_cast<const f32x4*>(row + hd * 64 + d8 * 8 + 4);
@@ -1103,7 +1104,7 @@ struct AttnDecodeLaunch {
     float* out; unsigned short* out16;
     int S, H, T;
     const int* src;                        // beam search: [S][T] ancestor table, or NULL
-    const float* kmask;                    // [S][T] additive padding mask of the cache slots, or NULL (fp32 kernel without src only)
+    const float* kmask;                    // [S][T] additive padding mask of the cache slots, or NULL (fp32 kernel only)
     KvFormat fmt;                          // KV_F32, KV_BF16 / KV_F16 (one kernel; the type is f16), KV_E4M3
     int f16;                               // the 16-bit type of a 16-bit cache and of out16 (0 bf16, 1 fp16)
     int ni;                                // fp32 kernel: 9 / 2 keys per group and chunk; 0 = S * H <= 4096 ? 9 : 2
@@ -1112,17 +1113,16 @@ struct AttnDecodeLaunch {
     hipStream_t st;
     bool q_only = false;                   // 16-bit cache without src: slot t + 1 already holds the new k / v (c_attn's K/V-cache epilogue) -
                                            // the kernel reads q only and stores nothing to the cache
-    const int* first = nullptr;            // 16-bit cache without src: [S] padded prompt slots, cache slots 1 .. first[s] are left out
+    const int* first = nullptr;            // 16-bit cache: [S] padded prompt slots, cache slots 1 .. first[s] are left out (with src: not q_only)
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
-    if (a.kmask && (a.fmt != KV_F32 || a.src)) {
-        set_error("decode attention: the padding mask exists only in the fp32 kernel without an ancestor table (%s)",
-                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.fmt != KV_F32 ? "16-bit K/V cache" : "beam search");
+    if (a.kmask && a.fmt != KV_F32) {
+        set_error("decode attention: the padding mask exists only in the fp32 kernel (%s)", a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "16-bit K/V cache");
         return RGRG_EINVAL;
     }
-    if (a.first && ((a.fmt != KV_BF16 && a.fmt != KV_F16) || a.src)) {
-        set_error("decode attention: the padded-prompt variant exists for the 16-bit K/V cache without an ancestor table (%s)",
-                  a.src ? "beam search" : a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "fp32 K/V cache: pass the additive mask");
+    if (a.first && a.fmt != KV_BF16 && a.fmt != KV_F16) {
+        set_error("decode attention: the padded-prompt variant exists for the 16-bit K/V cache (%s)",
+                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "fp32 K/V cache: pass the additive mask");
         return RGRG_EINVAL;
     }
     if (a.fmt != KV_F32) {
@@ -1150,8 +1150,10 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
             return launch_attn_decode_kv8(a.qkv, a.ld_qkv, static_cast<uint8_t*>(a.kc), static_cast<uint8_t*>(a.vc), a.step, a.out, a.out16,
                                           a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
 #define KV16_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<__VA_ARGS__>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
-                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.first ? a.first : a.src, a.out16)
-        if (a.first) {
+                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, (a.first && !a.src) ? a.first : a.src, a.out16, a.first)
+        if (a.first && a.src) {   // beam search behind a left-padded prompt
+            if (a.f16) KV16_LAUNCH(true, true, false, true); else KV16_LAUNCH(true, false, false, true);
+        } else if (a.first) {
             if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true, true); else KV16_LAUNCH(false, false, true, true); }
             else { if (a.f16) KV16_LAUNCH(false, true, false, true); else KV16_LAUNCH(false, false, false, true); }
         } else if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true); else KV16_LAUNCH(false, false, true); }
@@ -1165,7 +1167,9 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
         if (ni != 9 && ni != 2) { set_error("decode attention: %d keys per group, the kernel is built for 9 and 2", ni); return RGRG_EINVAL; }
 #define ATT_LAUNCH(SRC_, NI_, MASK_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_, MASK_>), grid, blk, 0, a.st, a.qkv, a.ld_qkv, static_cast<float*>(a.kc), \
                                                        static_cast<float*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.frag_out, a.kmask)
-        if (a.kmask) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
+        if (a.kmask && a.src) {   // beam search behind a left-padded prompt (rgrg_decoder_beam_search_prompted)
+            if (ni == 9) ATT_LAUNCH(true, 9, true); else ATT_LAUNCH(true, 2, true);
+        } else if (a.kmask) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
             if (ni == 9) ATT_LAUNCH(false, 9, true); else ATT_LAUNCH(false, 2, true);
         } else if (ni == 9) { if (a.src) ATT_LAUNCH(true, 9, false); else ATT_LAUNCH(false, 9, false); }
         else { if (a.src) ATT_LAUNCH(true, 2, false); else ATT_LAUNCH(false, 2, false); }
@@ -1428,6 +1432,24 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool beam, unsigned 
 }
 int enqueue_head_argmax(rgrg_decoder* d, int S) {
     return enqueue_head(d, S, false, false, (kv_is_bf16(d, S) && d->xn16) ? d->xn16 : nullptr);
+}
+int enqueue_head_logits(rgrg_decoder* d, int S) {
+    return enqueue_head(d, S, false, true, (kv_is_bf16(d, S) && d->xn16) ? d->xn16 : nullptr);
+}
+
+// Beam search behind a left-padded prompt, fp32 cache: the additive mask of every cache slot of every beam row, -1e4 on slots
+// 1 .. first[r] (the padding of the row's item) and 0 elsewhere.  Padding belongs to the item and a parent lies inside the item, so
+// the rows never move with the ancestor table.
+__global__ __launch_bounds__(256) void beam_first_mask_kernel(const int* __restrict__ first, int R, int T, float* __restrict__ kmask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R * T) return;
+    const int r = i / T, j = i - r * T;
+    kmask[i] = (j >= 1 && j <= first[r]) ? -10000.0f : 0.f;
+}
+int launch_beam_first_mask(const int* first, int R, int T, float* kmask, hipStream_t st) {
+    hipLaunchKernelGGL(beam_first_mask_kernel, dim3((R * T + 255) / 256), dim3(256), 0, st, first, R, T, kmask);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
 }
 
 // One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
@@ -1920,6 +1942,10 @@ extern "C" int rgrg_debug_attn_decode(const float* qkv, int ld_qkv, void* kcache
     RGRG_CHECK_ARG(out || (kv16 && out16));
     RGRG_CHECK_ARG(kv16 || (!out16 && max_workgroups == 0));
     RGRG_CHECK_ARG(!kv16 || (ni == 0 && frag_out == 0));
+    if (kmask && (kv16 || src)) {   // (mask and table together: rgrg_debug_attn_decode_beam_first)
+        set_error("rgrg_debug_attn_decode: the padding mask goes with the fp32 cache and no ancestor table (%s)", kv16 ? "16-bit K/V cache" : "beam search");
+        return RGRG_EINVAL;
+    }
     AttnDecodeLaunch a{};
     a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
     a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.src = src; a.kmask = kmask;
@@ -1952,6 +1978,34 @@ extern "C" int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* 
     a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.first = first;
     a.fmt = fp16 ? KV_F16 : KV_BF16; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream); a.q_only = q_only != 0;
     return launch_attn_decode(a);
+}
+
+// Test hook: the two variants of a beam step behind a left-padded prompt (rgrg_decoder_beam_search_prompted) through the same launcher:
+// ancestor table src [S][T_slots] AND padded prompt slots first [S] (cache slots 1 .. first[s] are left out).  16-bit cache:
+// attn_decode_kv16_wave_kernel<true, fp16, false, true>.  fp32 cache: attn_decode_kernel<true, ni, true> on the additive mask the
+// product builds from `first` (launch_beam_first_mask), in a buffer of the call's own.
+extern "C" int rgrg_debug_attn_decode_beam_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
+                                                 uint16_t* out16, int S, int H, int T_slots, const int* src, const int* first, int kv16,
+                                                 int fp16, int ni, int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && step_dev && src && first && S > 0 && H > 0 && T_slots >= 2 && ld_qkv >= 3 * H * 64);
+    RGRG_CHECK_ARG(out || (kv16 && out16));
+    RGRG_CHECK_ARG(kv16 || (!out16 && max_workgroups == 0));
+    RGRG_CHECK_ARG(!kv16 || ni == 0);
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.src = src;
+    a.fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.max_wgs = max_workgroups;
+    a.st = as_stream(stream);
+    if (kv16) { a.first = first; return launch_attn_decode(a); }
+    float* kmask = nullptr;
+    RGRG_HIP(hipMalloc((void**)&kmask, (size_t)S * T_slots * sizeof(float)));
+    int rc = launch_beam_first_mask(first, S, T_slots, kmask, a.st);
+    a.kmask = kmask;
+    if (!rc) rc = launch_attn_decode(a);
+    const hipError_t e = hipStreamSynchronize(a.st);   // the mask is the call's own: it must outlive the launch
+    (void)hipFree(kmask);
+    if (!rc && e != hipSuccess) { set_error("rgrg_debug_attn_decode_beam_first: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return rc;
 }
 
 // Test hook: the same launcher on an e4m3 cache (attn_decode_kv8_wave_kernel): K / V planes of bytes, out (fp32) or out16 (bf16 / fp16 by

@@ -312,9 +312,12 @@ struct BeamHyps {
 };
 }  // namespace rgrg
 
-extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length,
-                                        int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
-                                        int out_ld, int* out_len, void* stream) {
+// prompt == NULL: the BOS start of rgrg_decoder_beam_search.  With a prompt (rgrg_decoder_beam_search_prompted, decoder_prompt.hip)
+// the first iteration ranks the logits of the prompt's last position instead of running a step - the reference's first iteration
+// on nb identical rows - and ids / cur_len start at the prompt.
+int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping,
+                          float length_penalty, int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream,
+                          const BeamPrompt* prompt) {
     RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && num_beams > 1 && num_beams <= (1 << 14));
     RGRG_CHECK_ARG(num_return_sequences >= 1 && num_return_sequences <= num_beams);
     const int nb = num_beams, K = 2 * nb, R = S * nb;
@@ -344,10 +347,18 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
     // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
     int rc = enqueue_prefill(d, feats, S, nb);
     if (rc) return rc;
-    hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d->src_a, d->T, nb, R, d->step);
-    RGRG_LAUNCH_CHECK();
+    bool padded = false;
+    std::vector<long long> prompt_ids;
+    if (prompt) {
+        if ((rc = enqueue_beam_prompt(d, *prompt, S, nb, &padded, &prompt_ids))) return rc;
+    } else {
+        hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d->src_a, d->T, nb, R, d->step);
+        RGRG_LAUNCH_CHECK();
+    }
 
     std::vector<std::vector<long long>> ids(R, std::vector<long long>(1, BOS_ID));
+    if (prompt)
+        for (int r = 0; r < R; ++r) ids[r].assign(prompt_ids.begin() + (size_t)(r / nb) * prompt->T, prompt_ids.begin() + (size_t)(r / nb + 1) * prompt->T);
     std::vector<float> beam_scores(R, 0.f), h_score((size_t)S * K);
     std::vector<int> beam_tok(R, BOS_ID), parent(R, 0), h_tok((size_t)S * K), h_beam((size_t)S * K);
     for (int r = 0; r < R; ++r) beam_scores[r] = (r % nb == 0) ? 0.f : -1e9f;
@@ -356,7 +367,24 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
     const double lp = (double)length_penalty;
     int* src_cur = d->src_a;
     int* src_nxt = d->src_b;
-    int cur_len = 1;
+    int cur_len = prompt ? prompt->T : 1;
+    bool first_ranking = prompt != nullptr;
+    // the ranking of d->logits behind a step (captured with it) or behind the prompt's last position
+    auto enqueue_ranking = [&]() {
+        if (!wide) {
+#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(R), dim3(THREADS_), 0, st, d->logits, d->ld_logits, d->V, K, \
+                                              d->row_max, d->row_logsum, d->top_val, d->top_tok)
+            if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
+#undef BEAM_TOPK
+            hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
+                               d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
+        } else {
+            hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
+                               d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
+            hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, d->row_max, d->row_logsum, d->wide_val, d->wide_tok,
+                               d->beam_scores, nb, K, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam);
+        }
+    };
     std::vector<float> nscore(R);
     std::vector<int> ntok(R), nidx(R);
     d->logits_stale_rows = 0;   // beam steps write d->logits
@@ -364,29 +392,22 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
     while (true) {
         RGRG_HIP(hipMemcpyAsync(d->beam_tok, beam_tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
         RGRG_HIP(hipMemcpyAsync(d->beam_scores, beam_scores.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
-        {
-            // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed
-            const int parity = (src_cur == d->src_a) ? 1 : 2;
+        if (first_ranking) {   // the prompt pass left the ln_f row of every item's last position in its nb rows: head, ranking, no step
+            if ((rc = enqueue_head_logits(d, R))) return rc;
+            enqueue_ranking();
+            RGRG_LAUNCH_CHECK();
+        } else {
+            // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed; behind a left-padded
+            // prompt the steps carry positions and padded slots and are captured under keys of their own (GraphEntry)
+            const int parity = ((src_cur == d->src_a) ? 1 : 2) + (padded ? 4 : 0);
             hipGraphExec_t exec = nullptr;
             for (auto& g : d->graphs)
                 if (g.S == R && g.key2 == parity && g.key3 == nb) exec = g.exec;
             if (!exec) {
                 hipGraph_t graph = nullptr;
                 RGRG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_step(d, R, false, d->beam_tok, src_cur, true);
-                if (!rc && !wide) {
-#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(R), dim3(THREADS_), 0, st, d->logits, d->ld_logits, d->V, K, \
-                                                      d->row_max, d->row_logsum, d->top_val, d->top_tok)
-                    if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
-#undef BEAM_TOPK
-                    hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
-                                       d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
-                } else if (!rc) {
-                    hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
-                                       d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
-                    hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, d->row_max, d->row_logsum, d->wide_val, d->wide_tok,
-                                       d->beam_scores, nb, K, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam);
-                }
+                rc = padded ? padded_beam_step(d, R, src_cur) : enqueue_step(d, R, false, d->beam_tok, src_cur, true);
+                if (!rc) enqueue_ranking();
                 hipError_t e = hipStreamEndCapture(st, &graph);
                 if (rc) return rc;
                 if (e != hipSuccess) { set_error("beam: hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
@@ -433,9 +454,15 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
         bool all_done = true;
         for (int b = 0; b < S; ++b) all_done = all_done && done[b];
         if (all_done || cur_len >= max_length) break;
-        RGRG_HIP(hipMemcpyAsync(d->beam_parent, parent.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_cur, src_nxt, d->beam_parent, d->step, d->T, R);
-        RGRG_LAUNCH_CHECK();
+        if (first_ranking) {
+            // no slot was written: slots 0 .. T of every beam live in row s * nb whatever its parent, and the prompt pass
+            // pointed BOTH tables there - the advance kernel would point slot T at the parent's row
+            first_ranking = false;
+        } else {
+            RGRG_HIP(hipMemcpyAsync(d->beam_parent, parent.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_cur, src_nxt, d->beam_parent, d->step, d->T, R);
+            RGRG_LAUNCH_CHECK();
+        }
         hipLaunchKernelGGL(beam_step_inc_kernel, dim3(1), dim3(64), 0, st, d->step);
         RGRG_LAUNCH_CHECK();
         int* tmp = src_cur; src_cur = src_nxt; src_nxt = tmp;
@@ -476,4 +503,11 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
     *out_len = L;
     d->logits_valid = true;
     return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length,
+                                        int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
+                                        int out_ld, int* out_len, void* stream) {
+    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld,
+                           out_len, stream, nullptr);
 }

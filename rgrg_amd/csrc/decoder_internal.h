@@ -82,7 +82,8 @@ struct LayerW {
 
 struct GraphEntry {
     int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3),
-            // 3 = sampling step, 4 = greedy step behind a left-padded prompt (decoder_prompt.hip)
+            // 3 = sampling step, 4 = greedy step behind a left-padded prompt (decoder_prompt.hip), 5/6 = beam step reading table A/B
+            // behind a left-padded prompt (num_beams in key3), 7 = sampling step behind a left-padded prompt
     hipGraphExec_t exec;
     int key2 = 0, key3 = 0;
 };
@@ -208,6 +209,7 @@ struct rgrg_decoder {
     int* prompt_pad = nullptr;               // [rows]
     long long* prompt_pos = nullptr;         // [rows][max_len]
     const int* kv_first_cur = nullptr;
+    int* beam_pad = nullptr;                 // [rows] rgrg_decoder_beam_search_prompted: prompt_pad of every beam row's item
     // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
     // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
     int logits_stale_rows = 0;
@@ -251,10 +253,28 @@ bool lm_head_cand_path(const rgrg_decoder* d, int S);   // greedy many-sequence 
 // the end of a greedy step on its own: lm_head over the ln_f rows in d->xn (and d->xn16 where the step plan of S rows reads 16-bit
 // activations), arg-max, record_step_token at *d->step
 int enqueue_head_argmax(rgrg_decoder* d, int S);
+// ... and in its logits-leaving form (the form beam search and sampling rank): d->logits rows [0, S), nothing else
+int enqueue_head_logits(rgrg_decoder* d, int S);
+// additive slot mask [R][T] of beam rows behind a left-padded prompt: -1e4 on slots 1 .. first[r], 0 elsewhere
+int launch_beam_first_mask(const int* first, int R, int T, float* kmask, hipStream_t st);
 
 // decoder_lm.hip: embedding .. ln_f of the teacher-forced pass over S x T token rows; leaves the ln_f rows in d->tf.xn (the image
 // key / value of every layer must be in d->ukv_out, the work space reserved with tf_reserve).  after_qkv (or NULL) runs behind
 // every layer's c_attn with that layer's q | k | v rows [S*T][3D] (fp32).
+// decoder_prompt.hip: the prompt of rgrg_decoder_beam_search_prompted, one per ITEM.  enqueue_beam_prompt runs between the prefill
+// and the first ranking: mask scan and refusals (one read-back), the teacher-forced pass over the S x T prompt rows with keys /
+// values into slots 1 .. T of cache row s * nb, both ancestor tables pointing slots 0 .. T of every beam row there, *step = T - 1,
+// and the ln_f row of every item's last prompt position in the lm_head input of its nb rows.  -> *padded, host_ids [S][T].
+struct BeamPrompt { const long long* ids; const float* am; int T; };
+int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, bool* padded, std::vector<long long>* host_ids);
+// a beam step behind a left-padded prompt: per-row positions, the slot mask (fp32 cache) / padded slots (16-bit cache), enqueue_step
+int padded_beam_step(rgrg_decoder* d, int R, const int* src);
+// decoder_beam.hip: rgrg_decoder_beam_search, from a prompt when one is given
+int beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping, float length_penalty,
+                    int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream, const BeamPrompt* prompt);
+// decoder_sample.hip: the sampling step (graph key 3) and the start of every sampling entry
+int sample_step(rgrg_decoder* d, int S, bool count);
+int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
 int tf_reserve(rgrg_decoder* d, size_t rows);
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
                    int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr);

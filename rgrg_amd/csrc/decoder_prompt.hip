@@ -3,6 +3,9 @@
 // decoder_lm.hip) whose keys / values go to slots 1 .. T of the decode cache, lm_head + arg-max over the S last-position rows, and
 // the decode loop of rgrg_decoder_generate from step T on.  A left-padded prompt keeps its padded slots out of every later step and
 // embeds every row's tokens at the row's own position (prepare_inputs_for_generation, :498-520).
+// rgrg_decoder_sample_prompted is the same entry with the sampler behind the prompt's last position and behind every step.
+// rgrg_decoder_beam_search_prompted (beam_search, :529-607) runs the prompt pass once per ITEM: the nb beams of an item share its
+// prompt, whose keys / values live once, in cache row s * nb, and reach every beam row through the ancestor table.
 #include <algorithm>
 
 #include "decoder_internal.h"
@@ -59,9 +62,10 @@ __global__ __launch_bounds__(256) void prompt_setup_kernel(const long long* __re
 // q | k | v rows [S*T][3D] (fp32) of one layer -> slots 1 .. T of the decode cache planes [rows][H][slots][64] of that layer.  A
 // (sequence, head) owns T consecutive slots = T * 64 consecutive elements of a plane; a lane moves 16 bytes of the DESTINATION:
 // consecutive lanes write consecutive 16-byte pieces (a wave 1 KiB in one piece) and read whole 256-byte head rows of the source.
+// row_mul: sequence s owns cache row s * row_mul (beam search: the first beam row of the item).
 template <typename KV>   // float, or u16 in the 16-bit type f16
 __global__ __launch_bounds__(256) void prompt_kv_store_kernel(const float* __restrict__ qkv, KV* __restrict__ kplane, KV* __restrict__ vplane,
-                                                              int S, int H, int T, int slots, int f16) {
+                                                              int S, int H, int T, int slots, int f16, int row_mul) {
     constexpr int PER = 16 / sizeof(KV);      // elements per lane
     constexpr int LANES = 64 / PER;           // lanes per head row
     const int D = H * 64;
@@ -73,7 +77,7 @@ __global__ __launch_bounds__(256) void prompt_kv_store_kernel(const float* __res
         const int kv = (int)(r & 1); r >>= 1;
         const int hd = (int)(r % H), s = (int)(r / H);
         const float* src = qkv + ((size_t)s * T + t) * 3 * D + (size_t)(1 + kv) * D + hd * 64 + e;
-        KV* dst = (kv ? vplane : kplane) + (((size_t)s * H + hd) * slots + 1 + t) * 64 + e;
+        KV* dst = (kv ? vplane : kplane) + (((size_t)s * row_mul * H + hd) * slots + 1 + t) * 64 + e;
         const f32x4 a = *reinterpret_cast<const f32x4*>(src);
         if constexpr (sizeof(KV) == 4) {
             *reinterpret_cast<f32x4*>(dst) = a;
@@ -89,14 +93,34 @@ __global__ __launch_bounds__(256) void prompt_kv_store_kernel(const float* __res
     }
 }
 
-// ln_f row of every sequence's last prompt position -> row s of the decode step's lm_head input (fp32, and 16 bit where that step
-// reads 16-bit activations): the lm_head runs on S rows, not S x T
+// ln_f row of every sequence's last prompt position -> the decode step's lm_head input (fp32, and 16 bit where that step reads
+// 16-bit activations): the lm_head runs on S rows, not S x T.  Block r writes row r from sequence r / row_div (beam search: the nb
+// rows of an item start from the same row).
 __global__ __launch_bounds__(256) void prompt_last_rows_kernel(const float* __restrict__ xn_all, int T, int D, float* __restrict__ xn,
-                                                               u16* __restrict__ xn16, int f16) {
-    const int s = blockIdx.x, tid = threadIdx.x;   // D == 1024
+                                                               u16* __restrict__ xn16, int f16, int row_div) {
+    const int r = blockIdx.x, s = r / row_div, tid = threadIdx.x;   // D == 1024
     const f32x4 v = reinterpret_cast<const f32x4*>(xn_all + ((size_t)s * T + T - 1) * D)[tid];
-    reinterpret_cast<f32x4*>(xn + (size_t)s * D)[tid] = v;
-    if (xn16) store_16x4(xn16 + (size_t)s * D + 4 * tid, v, f16);
+    reinterpret_cast<f32x4*>(xn + (size_t)r * D)[tid] = v;
+    if (xn16) store_16x4(xn16 + (size_t)r * D + 4 * tid, v, f16);
+}
+
+// Beam search from a prompt: slots 0 .. T of all R = S * nb rows of BOTH ancestor tables -> row (r / nb) * nb, where the image slot
+// and the prompt pass put them; beam_pad[r] = the padded prompt slots of the row's item (0 without padding)
+__global__ __launch_bounds__(256) void beam_prompt_init_kernel(int* __restrict__ src_a, int* __restrict__ src_b, int slots, int nb, int R,
+                                                               int T, const int* __restrict__ pad, int* __restrict__ beam_pad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R * (T + 1)) return;
+    const int r = i / (T + 1), j = i - r * (T + 1);
+    src_a[(size_t)r * slots + j] = (r / nb) * nb;
+    src_b[(size_t)r * slots + j] = (r / nb) * nb;
+    if (j == 0) beam_pad[r] = pad ? pad[r / nb] : 0;
+}
+
+// Before every beam step behind a padded prompt: beam row r embeds its token at position step - pad of its item
+__global__ __launch_bounds__(256) void beam_row_pos_kernel(const int* __restrict__ step, const int* __restrict__ beam_pad,
+                                                           int* __restrict__ row_pos, int R) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r < R) row_pos[r] = *step - beam_pad[r];
 }
 
 // Before every step behind a padded prompt: row s embeds its token at position step - pad[s] (the cache slot stays step + 1); the
@@ -114,19 +138,21 @@ struct PromptCall {
     const long long* ids;
     const float* am;     // NULL unless the prompt is padded
     int S, T;
+    int row_mul = 1;     // beam search: num_beams - sequence s owns cache row s * row_mul, the cache format is that of S * row_mul rows
+    bool sample = false; // the token behind the prompt is drawn (launch_sample_step), not the arg-max
 };
 
 int store_prompt_kv(rgrg_decoder* d, int l, const float* qkv, const void* arg) {
     const PromptCall& c = *static_cast<const PromptCall*>(arg);
-    const int S = c.S, fmt = rgrg_decoder_kv_format_in_use(d, S);
+    const int S = c.S, fmt = rgrg_decoder_kv_format_in_use(d, S * c.row_mul);
     const size_t total = (size_t)S * d->H * 2 * c.T * (fmt == KV_F32 ? 16 : 8);
     const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096)), blk(256);
     if (fmt == KV_F32) {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
-        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, 0);
+        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, 0, c.row_mul);
     } else {   // the 16-bit cache lives in the same allocation with the same element strides (enqueue_prefill)
         u16* kc = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride;
-        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, d->f16());
+        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, d->f16(), c.row_mul);
     }
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
@@ -145,14 +171,19 @@ int enqueue_prompt(rgrg_decoder* d, int S, const void* arg) {
     RGRG_LAUNCH_CHECK();
     if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, arg))) return rc;
     u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
-    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(S), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16());
+    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(S), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), 1);
     RGRG_LAUNCH_CHECK();
-    return enqueue_head_argmax(d, S);
+    if (!c.sample) return enqueue_head_argmax(d, S);
+    // the device step word is T - 1: the Philox counter of row r for the token in column T is (r, T - 1), as a step would have it
+    if ((rc = enqueue_head_logits(d, S))) return rc;
+    return launch_sample_step(d->logits, d->ld_logits, S, d->V, d->sample_prm, d->ids, d->max_len, d->finished, d->step, d->done_len,
+                              d->sync, d->sample_lp, d->max_len, st);
 }
 
 int greedy_step(rgrg_decoder* d, int S, bool count) { return enqueue_step(d, S, count); }
 
-int padded_step(rgrg_decoder* d, int S, bool count) {
+// beam: the step leaves logits (sampling), the caller ranks them
+int padded_step_any(rgrg_decoder* d, int S, bool count, bool beam) {
     hipLaunchKernelGGL(prompt_step_rows_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, d->ids, d->max_len, d->step, d->prompt_pad,
                        d->beam_tok, d->row_pos, S);
     RGRG_LAUNCH_CHECK();
@@ -160,14 +191,96 @@ int padded_step(rgrg_decoder* d, int S, bool count) {
     d->pos_override_cur = d->row_pos;
     if (kv16) d->kv_first_cur = d->prompt_pad;
     else d->key_mask_cur = d->key_mask;
-    const int rc = enqueue_step(d, S, count, S <= rgrg_decoder_row_limit(d) ? d->beam_tok : nullptr);
+    const int rc = enqueue_step(d, S, count, S <= rgrg_decoder_row_limit(d) ? d->beam_tok : nullptr, nullptr, beam);
+    d->pos_override_cur = nullptr;
+    d->kv_first_cur = nullptr;
+    d->key_mask_cur = nullptr;
+    return rc;
+}
+int padded_step(rgrg_decoder* d, int S, bool count) { return padded_step_any(d, S, count, false); }
+int padded_sample_step(rgrg_decoder* d, int S, bool count) {
+    const int rc = padded_step_any(d, S, count, true);
+    if (rc) return rc;
+    return launch_sample_step(d->logits, d->ld_logits, S, d->V, d->sample_prm, d->ids, d->max_len, d->finished, d->step, d->done_len,
+                              d->sync, d->sample_lp, d->max_len, d->stream);
+}
+
+// The mask scan of every prompted entry on d->stream, with ONE read-back: a mask the kernels cannot honour is refused before any
+// work.  -> *padded; d->prompt_pad[s] = the zeros in front of row s.  extra_dst / extra_src: a copy that rides on the same wait.
+int prompt_mask_check(rgrg_decoder* d, const char* who, const float* attention_mask, int S, int T, bool* padded, void* extra_dst = nullptr,
+                      const void* extra_src = nullptr, size_t extra_bytes = 0) {
+    int rc;
+    *padded = false;
+    if (!d->prompt_pad && (rc = dmalloc(d, (void**)&d->prompt_pad, (size_t)d->rows * sizeof(int), true))) return rc;
+    if (extra_dst) RGRG_HIP(hipMemcpyAsync(extra_dst, extra_src, extra_bytes, hipMemcpyDeviceToHost, d->stream));
+    if (attention_mask) {
+        int* flags = d->next;   // a scratch word of the decoder
+        RGRG_HIP(hipMemsetAsync(flags, 0, sizeof(int), d->stream));
+        hipLaunchKernelGGL(prompt_mask_scan_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, attention_mask, S, T, d->prompt_pad, flags);
+        RGRG_LAUNCH_CHECK();
+        RGRG_HIP(hipMemcpyAsync(d->h_done, flags, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (attention_mask || extra_dst) RGRG_HIP(hipStreamSynchronize(d->stream));
+    if (attention_mask) {
+        const int f = *d->h_done;
+        if (f & (MASK_ROW_EMPTY | MASK_NOT_LEFT | MASK_NOT_BINARY)) {
+            set_error("%s: attention_mask %s", who, (f & MASK_ROW_EMPTY) ? "has a row of zeros only (no token to continue from)"
+                      : (f & MASK_NOT_LEFT) ? "is not left padding (a zero behind a one): only padding in front of the prompt is supported"
+                      : "holds values other than 0 and 1");
+            return RGRG_EINVAL;
+        }
+        *padded = (f & MASK_HAS_PAD) != 0;
+    }
+    if (*padded) {
+        if (!d->prompt_pos && (rc = dmalloc(d, (void**)&d->prompt_pos, (size_t)d->rows * d->max_len * sizeof(long long), true))) return rc;
+        if (!d->key_mask && (rc = dmalloc(d, (void**)&d->key_mask, (size_t)d->rows * d->T * sizeof(float), true))) return rc;
+    }
+    return RGRG_OK;
+}
+
+}  // namespace
+
+int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, bool* padded, std::vector<long long>* host_ids) {
+    const int T = p.T, R = S * nb, fmt = rgrg_decoder_kv_format_in_use(d, R);
+    hipStream_t st = d->stream;
+    int rc;
+    host_ids->resize((size_t)S * T);
+    if ((rc = prompt_mask_check(d, "rgrg_decoder_beam_search_prompted", p.am, S, T, padded, host_ids->data(), p.ids,
+                                (size_t)S * T * sizeof(long long))))
+        return rc;
+    if (!d->beam_pad && (rc = dmalloc(d, (void**)&d->beam_pad, (size_t)d->rows * sizeof(int), true))) return rc;
+    if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
+    PromptCall c{p.ids, *padded ? p.am : nullptr, S, T};
+    c.row_mul = nb;
+    // (the id buffer rows written here are not read: beam search keeps its histories on the host)
+    hipLaunchKernelGGL(prompt_setup_kernel, dim3((S * T + 255) / 256), dim3(256), 0, st, c.ids, S, T, d->V, d->ids, d->max_len, d->step,
+                       c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, (float*)nullptr, d->T);
+    RGRG_LAUNCH_CHECK();
+    if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, &c))) return rc;
+    hipLaunchKernelGGL(beam_prompt_init_kernel, dim3((R * (T + 1) + 255) / 256), dim3(256), 0, st, d->src_a, d->src_b, d->T, nb, R, T,
+                       c.am ? d->prompt_pad : (const int*)nullptr, d->beam_pad);
+    RGRG_LAUNCH_CHECK();
+    if (*padded && fmt == KV_F32 && (rc = launch_beam_first_mask(d->beam_pad, R, d->T, d->key_mask, st))) return rc;
+    u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
+    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), nb);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+int padded_beam_step(rgrg_decoder* d, int R, const int* src) {
+    hipLaunchKernelGGL(beam_row_pos_kernel, dim3((R + 255) / 256), dim3(256), 0, d->stream, d->step, d->beam_pad, d->row_pos, R);
+    RGRG_LAUNCH_CHECK();
+    const bool kv16 = rgrg_decoder_kv_format_in_use(d, R) != KV_F32;
+    d->pos_override_cur = d->row_pos;
+    if (kv16) d->kv_first_cur = d->beam_pad;
+    else d->key_mask_cur = d->key_mask;
+    const int rc = enqueue_step(d, R, false, d->beam_tok, src, true);
     d->pos_override_cur = nullptr;
     d->kv_first_cur = nullptr;
     d->key_mask_cur = nullptr;
     return rc;
 }
 
-}  // namespace
 }  // namespace rgrg
 
 extern "C" int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask,
@@ -188,36 +301,68 @@ extern "C" int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feat
         return RGRG_EINVAL;
     }
     int rc;
-    if (!d->prompt_pad && (rc = dmalloc(d, (void**)&d->prompt_pad, (size_t)d->rows * sizeof(int), true))) return rc;
     if ((rc = decode_begin(d, stream))) return rc;
     bool padded = false;
-    if (attention_mask) {   // one read-back per call: a mask the kernels cannot honour is refused before any work
-        int* flags = d->next;   // a scratch word of the decoder
-        RGRG_HIP(hipMemsetAsync(flags, 0, sizeof(int), d->stream));
-        hipLaunchKernelGGL(prompt_mask_scan_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, attention_mask, S, T, d->prompt_pad, flags);
-        RGRG_LAUNCH_CHECK();
-        RGRG_HIP(hipMemcpyAsync(d->h_done, flags, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-        RGRG_HIP(hipStreamSynchronize(d->stream));
-        const int f = *d->h_done;
-        if (f & (MASK_ROW_EMPTY | MASK_NOT_LEFT | MASK_NOT_BINARY)) {
-            set_error("rgrg_decoder_generate_prompted: attention_mask %s", (f & MASK_ROW_EMPTY) ? "has a row of zeros only (no token to continue from)"
-                      : (f & MASK_NOT_LEFT) ? "is not left padding (a zero behind a one): only padding in front of the prompt is supported"
-                      : "holds values other than 0 and 1");
-            return RGRG_EINVAL;
-        }
-        padded = (f & MASK_HAS_PAD) != 0;
-    }
-    if (padded) {
-        if (!d->prompt_pos && (rc = dmalloc(d, (void**)&d->prompt_pos, (size_t)d->rows * d->max_len * sizeof(long long), true))) return rc;
-        if (!d->key_mask && (rc = dmalloc(d, (void**)&d->key_mask, (size_t)d->rows * d->T * sizeof(float), true))) return rc;
-    }
+    if ((rc = prompt_mask_check(d, "rgrg_decoder_generate_prompted", attention_mask, S, T, &padded))) return rc;
     if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
-    const PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
+    PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
     const DecodePrologue pro{enqueue_prompt, &call, T};
     // a mask of ones leaves the steps of rgrg_decoder_generate (and their captured graph); a padded prompt has its own (key 4)
     if ((rc = run_decode_loop(d, feats, S, limit, padded ? 4 : 0, padded ? padded_step : greedy_step, use_graph, out_ids, out_ld, nullptr,
                               out_len, &pro)))
         return rc;
     d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_beam_search_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask,
+                                                 int S, int T, int num_beams, int max_length, int early_stopping, float length_penalty,
+                                                 int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream) {
+    RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && T >= 1 && num_beams > 1 && num_beams <= (1 << 14));
+    RGRG_CHECK_ARG((long long)S * num_beams <= d->max_seqs);
+    // beam_search (:541, :597-605): the first iteration always runs, and finalize cannot hold a hypothesis longer than max_length
+    if (max_length < T + 1 || max_length > d->max_len) {
+        set_error("rgrg_decoder_beam_search_prompted: max_length %d with a prompt of %d tokens: %d .. %d (the cache) are possible", max_length,
+                  T, T + 1, d->max_len);
+        return RGRG_EINVAL;
+    }
+    if (rgrg_decoder_kv_format_in_use(d, S * num_beams) == KV_E4M3) {
+        set_error("rgrg_decoder_beam_search_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
+        return RGRG_EINVAL;
+    }
+    const BeamPrompt p{reinterpret_cast<const long long*>(input_ids), attention_mask, T};
+    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
+                           stream, &p);
+}
+
+extern "C" int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
+                                            int T, int max_length, float temperature, int top_k, float top_p, uint64_t seed,
+                                            int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && S <= d->max_seqs && T >= 1);
+    if (T + 1 > d->max_len) {
+        set_error("rgrg_decoder_sample_prompted: a prompt of %d tokens and one generated token need %d token slots, the cache has %d",
+                  T, T + 1, d->max_len);
+        return RGRG_EINVAL;
+    }
+    int limit = (max_length > 0) ? max_length : d->max_len;   // as rgrg_decoder_generate_prompted: one token is always produced
+    if (limit < T + 1) limit = T + 1;
+    RGRG_CHECK_ARG(limit <= d->max_len && out_ld >= limit);
+    if (rgrg_decoder_kv_format_in_use(d, S) == KV_E4M3) {
+        set_error("rgrg_decoder_sample_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
+        return RGRG_EINVAL;
+    }
+    int rc;
+    if ((rc = sample_begin(d, S, temperature, top_k, top_p, seed, stream))) return rc;
+    bool padded = false;
+    if ((rc = prompt_mask_check(d, "rgrg_decoder_sample_prompted", attention_mask, S, T, &padded))) return rc;
+    if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
+    PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
+    call.sample = true;
+    const DecodePrologue pro{enqueue_prompt, &call, T};
+    // a mask of ones leaves the steps of rgrg_decoder_sample (and their captured graph, key 3); a padded prompt has its own (key 7)
+    if ((rc = run_decode_loop(d, feats, S, limit, padded ? 7 : 3, padded ? padded_sample_step : sample_step, use_graph, out_ids, out_ld,
+                              out_logprobs, out_len, &pro)))
+        return rc;
+    d->logits_stale_rows = 0;   // the head behind the prompt and every step wrote d->logits
     return RGRG_OK;
 }

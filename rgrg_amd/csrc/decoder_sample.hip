@@ -5,7 +5,7 @@
 
 using namespace rgrg;
 
-static int sample_step(rgrg_decoder* d, int S, bool count) {
+int rgrg::sample_step(rgrg_decoder* d, int S, bool count) {
     int rc = enqueue_step(d, S, count, nullptr, nullptr, true);
     if (rc) return rc;
     return launch_sample_step(d->logits, d->ld_logits, S, d->V, d->sample_prm, d->ids, d->max_len, d->finished, d->step, d->done_len,
@@ -19,13 +19,20 @@ extern "C" int rgrg_decoder_sample(rgrg_decoder* d, const float* feats, int S, i
     const int limit = (max_length > 0) ? max_length : d->max_len;
     RGRG_CHECK_ARG(limit >= 2 && limit <= d->max_len && out_ld >= limit);
     int rc;
+    if ((rc = sample_begin(d, S, temperature, top_k, top_p, seed, stream))) return rc;
+    if ((rc = run_decode_loop(d, feats, S, limit, 3, sample_step, use_graph, out_ids, out_ld, out_logprobs, out_len))) return rc;
+    d->logits_stale_rows = 0;   // every step wrote d->logits: the logits the last draw was made from
+    return RGRG_OK;
+}
+
+// what every sampling entry does before its decode loop: buffers, d->stream behind the caller's, the parameter block, zero log-probs
+int rgrg::sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream) {
+    int rc;
     if (!d->sample_prm && (rc = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return rc;
     if (!d->sample_lp && (rc = dmalloc(d, (void**)&d->sample_lp, (size_t)d->rows * d->max_len * sizeof(float), true))) return rc;
     if ((rc = decode_begin(d, stream))) return rc;
     // the parameter block lives in device memory: the captured step (graph key 3) serves every seed and parameter set
     if ((rc = enqueue_sample_params(d->sample_prm, temperature, top_k, top_p, seed, d->stream))) return rc;
-    RGRG_HIP(hipMemsetAsync(d->sample_lp, 0, (size_t)S * d->max_len * sizeof(float), d->stream));   // BOS column, steps not run
-    if ((rc = run_decode_loop(d, feats, S, limit, 3, sample_step, use_graph, out_ids, out_ld, out_logprobs, out_len))) return rc;
-    d->logits_stale_rows = 0;   // every step wrote d->logits: the logits the last draw was made from
+    RGRG_HIP(hipMemsetAsync(d->sample_lp, 0, (size_t)S * d->max_len * sizeof(float), d->stream));   // BOS / prompt columns, steps not run
     return RGRG_OK;
 }

@@ -748,6 +748,25 @@ class HipEngine:
         pass over the S x T prompt rows fills the decode cache, the decode loop of ``greedy_decode`` continues from there.
         Token ids are validated like ``forward_cached`` does (IndexError, one read-back); shapes raise ValueError; an all-zero
         mask row, a mask that is not left padding and the e4m3 cache in use raise RgrgHipError."""
+        ids, am = self._check_prompt(feats, input_ids, attention_mask)
+        S, T = ids.shape
+        limit = int(max_length) if max_length else 1024
+        limit = max(limit, T + 1)   # the reference's loop always produces one token (language_model.py:624-650)
+        if limit > 1024:
+            raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
+        dec = self._get_decoder(S, limit)
+        self._cached = None   # as in greedy_decode
+        self._set_modes(dec, bf16, kv_fp8)
+        feats = feats.to(torch.float32).contiguous()
+        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
+        out_len = C.c_int(0)
+        _hip.check(self.lib.rgrg_decoder_generate_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, _hip.ptr(out),
+                                                           limit, C.byref(out_len), 1 if use_graph else 0, self._s()),
+                   "rgrg_decoder_generate_prompted")
+        return out[:, :out_len.value].contiguous()
+
+    def _check_prompt(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor]):
+        """Shapes, dtypes and ids of a prompted decode call, as ``greedy_decode_prompted`` validates them -> (ids, mask or None)."""
         _require_gpu(feats.device)
         _require_gpu(input_ids.device)
         if input_ids.dim() != 2 or input_ids.shape[1] < 1:
@@ -766,20 +785,66 @@ class HipEngine:
             if tuple(attention_mask.shape) != (S, T):
                 raise ValueError(f"attention_mask has shape {tuple(attention_mask.shape)}, input_ids {(S, T)}")
             am = attention_mask.to(device=self.device, dtype=torch.float32).contiguous()
+        return ids, am
+
+    def beam_search_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: int, num_beams: int,
+                             early_stopping: bool = False, length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
+                             kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.beam_search with a prompt (rgrg_decoder_beam_search_prompted): feats [S,1024], input_ids int64 [S,T] and
+        attention_mask [S,T] (or None = ones) hold ONE prompt per item -> int64 [S * num_return_sequences, L], the prompt in
+        front.  Validation as ``greedy_decode_prompted``; ``max_length < T + 1`` raises ValueError."""
+        ids, am = self._check_prompt(feats, input_ids, attention_mask)
+        S, T = ids.shape
+        limit = int(max_length)
+        if limit < T + 1:
+            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens (one iteration always runs and the "
+                             f"scorer cannot hold a hypothesis longer than max_length), but is {limit}")
+        if limit > 1024:
+            raise ValueError(f"max_length {limit} exceeds the 1024 positions of the model")
+        dec = self._get_decoder(S * int(num_beams), limit)
+        self._cached = None   # as in greedy_decode
+        self._set_modes(dec, bf16, kv_fp8)
+        feats = feats.to(torch.float32).contiguous()
+        out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
+        out_len = C.c_int(0)
+        _hip.check(self.lib.rgrg_decoder_beam_search_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), limit,
+                                                              1 if early_stopping else 0, float(length_penalty),
+                                                              int(num_return_sequences), _hip.ptr(out), limit, C.byref(out_len), self._s()),
+                   "rgrg_decoder_beam_search_prompted")
+        return out[:, :out_len.value].contiguous()
+
+    def sample_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
+                               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                               num_return_sequences: int = 1, bf16=False, use_graph: bool = True,
+                               kv_fp8: bool = False) -> Tuple[Tensor, Tensor]:
+        """LanguageModel.sample_from_prompt (rgrg_decoder_sample_prompted): ``sample_decode`` that continues input_ids [S,T] ->
+        (ids int64 [S*n, L'], log-probs f32 [S*n, L'], 0 in the prompt columns).  n = num_return_sequences hypotheses per row are
+        decoded as S*n rows with prompt, mask and features repeated row-wise (output row s*n + j).  Row r draws the token of column
+        c from the Philox counter (r, c - 1).  Validation as ``greedy_decode_prompted``."""
+        ids, am = self._check_prompt(feats, input_ids, attention_mask)
+        n = int(num_return_sequences)
+        feats = feats.to(torch.float32)
+        if n > 1:
+            feats = feats.repeat_interleave(n, dim=0)
+            ids = ids.repeat_interleave(n, dim=0).contiguous()
+            am = None if am is None else am.repeat_interleave(n, dim=0).contiguous()
+        feats = feats.contiguous()
+        S, T = ids.shape
         limit = int(max_length) if max_length else 1024
-        limit = max(limit, T + 1)   # the reference's loop always produces one token (language_model.py:624-650)
+        limit = max(limit, T + 1)   # one token is always produced, as in greedy_decode_prompted
         if limit > 1024:
             raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
         dec = self._get_decoder(S, limit)
         self._cached = None   # as in greedy_decode
         self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
         out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
+        lp = torch.empty((S, limit), dtype=torch.float32, device=feats.device)
         out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_generate_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, _hip.ptr(out),
-                                                           limit, C.byref(out_len), 1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_generate_prompted")
-        return out[:, :out_len.value].contiguous()
+        _hip.check(self.lib.rgrg_decoder_sample_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, float(temperature),
+                                                         int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(out), limit,
+                                                         _hip.ptr(lp), C.byref(out_len), 1 if use_graph else 0, self._s()),
+                   "rgrg_decoder_sample_prompted")
+        return out[:, :out_len.value].contiguous(), lp[:, :out_len.value].contiguous()
 
     def sample_decode(self, feats: Tensor, max_length: Optional[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                       seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True,

@@ -302,21 +302,101 @@ class LanguageModel(EngineOwner):
         AttributeError raised here.  The prompt is run as ONE batched pass into the decode cache (DESIGN.md 7.9);
         torch.autocast opts into the 16-bit plans exactly as for ``generate``.  A BOS column with a mask of ones IS
         ``generate()``."""
-        unknown = set(model_kwargs) - {"attention_mask", "use_cache"}
-        if unknown:
-            raise TypeError(f"greedy_search() got an unexpected keyword argument {sorted(unknown)[0]!r}")
-        if model_kwargs.get("use_cache", True) is not True:
-            raise ValueError("greedy_search needs use_cache=True: its loop feeds one token per step on top of the cached keys / values")
-        attention_mask = model_kwargs.get("attention_mask")
-        if attention_mask is None:
-            raise AttributeError("'NoneType' object has no attribute 'to' (greedy_search needs model_kwargs['attention_mask'], like the "
-                                 "reference's forward, language_model.py:281)")
+        attention_mask = self._prompt_kwargs("greedy_search", model_kwargs)
         from .engine import _require_gpu
         _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
         self.sync_trainable_if_stale()
         low = _hip.autocast_mode()
         return self.engine().greedy_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, bf16=low,
                                                     kv_fp8=self._kv_fp8())
+
+    @staticmethod
+    def _prompt_kwargs(name: str, model_kwargs: dict):
+        """The ``model_kwargs`` rules of ``greedy_search``, for ``name``: -> attention_mask."""
+        unknown = set(model_kwargs) - {"attention_mask", "use_cache"}
+        if unknown:
+            raise TypeError(f"{name}() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+        if model_kwargs.get("use_cache", True) is not True:
+            raise ValueError(f"{name} needs use_cache=True: its loop feeds one token per step on top of the cached keys / values")
+        attention_mask = model_kwargs.get("attention_mask")
+        if attention_mask is None:
+            raise AttributeError(f"'NoneType' object has no attribute 'to' ({name} needs model_kwargs['attention_mask'], like the "
+                                 "reference's forward, language_model.py:281)")
+        return attention_mask
+
+    @torch.no_grad()
+    def beam_search(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: int, beam_scorer,
+                    **model_kwargs) -> torch.LongTensor:
+        """language_model.py:529-607 with a prompt: ``input_ids`` and ``model_kwargs['attention_mask']`` are [S*num_beams, T],
+        expanded as ``_expand_inputs_for_generation`` (:481-490) leaves them (the num_beams rows of an item equal; zeros = LEFT
+        padding), ``image_hidden_states`` is [S,1024].  Returns int64 [S * num_beam_hyps_to_keep, L], the prompt in front.
+        ``beam_scorer`` (a transformers-4.19.2 ``BeamSearchScorer`` or anything with its attributes) is READ, not called:
+        ``num_beams``, ``len(_beam_hyps)``, ``length_penalty``, ``do_early_stopping`` and ``num_beam_hyps_to_keep`` are taken
+        from it and the search runs on the decoder's own restatement of the scorer - ITS STATE IS NOT UPDATED (no hypotheses are
+        added to it, ``is_done`` stays what it was); ``num_beam_groups > 1`` raises ValueError.  Hypothesis lengths count the
+        prompt, padding included, as the reference's do.  ``max_length >= T + 1`` is required (ValueError: the scorer's
+        ``finalize`` cannot hold a longer hypothesis).  Rows of a group that differ in ids or in mask raise ValueError: the prompt
+        runs ONCE per item, as S x T token rows whose keys / values every beam reaches through the ancestor table (DESIGN.md
+        7.10).  ``model_kwargs`` follow ``greedy_search``: the mask is required (AttributeError), ``use_cache`` must be True, any
+        other keyword raises TypeError.  torch.autocast opts into the 16-bit plans as for ``generate``."""
+        attention_mask = self._prompt_kwargs("beam_search", model_kwargs)
+        if getattr(beam_scorer, "num_beam_groups", 1) > 1:
+            raise ValueError("beam_search takes a scorer with num_beam_groups = 1: diverse beam search is not implemented")
+        batch_size = len(beam_scorer._beam_hyps)
+        num_beams = int(beam_scorer.num_beams)
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [S * num_beams, T], got {tuple(input_ids.shape)}")
+        batch_beam_size, T = input_ids.shape
+        if num_beams * batch_size != batch_beam_size:
+            raise ValueError(f"Batch dimension of 'input_ids' should be {num_beams * batch_size}, but is {batch_beam_size}.")
+        if tuple(attention_mask.shape) != (batch_beam_size, T):
+            raise ValueError(f"attention_mask has shape {tuple(attention_mask.shape)}, input_ids {(batch_beam_size, T)}")
+        if int(max_length) < T + 1:
+            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens, but is {max_length}")
+        from .engine import _require_gpu
+        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
+        _require_gpu(input_ids.device)
+        _require_gpu(attention_mask.device)
+        ids3 = input_ids.reshape(batch_size, num_beams, T)
+        am3 = attention_mask.reshape(batch_size, num_beams, T)
+        # one device comparison per call: the shared prompt pass needs the rows of a group equal
+        if bool(((ids3 != ids3[:, :1]).any() | (am3 != am3[:, :1]).any())):
+            raise ValueError("the num_beams rows of a beam group differ in input_ids or attention_mask: beam_search runs one prompt "
+                             "per item (expand the prompts with _expand_inputs_for_generation)")
+        return self._beam_search_prompts(ids3[:, 0], am3[:, 0], image_hidden_states, int(max_length), num_beams,
+                                         bool(beam_scorer.do_early_stopping), float(beam_scorer.length_penalty),
+                                         int(beam_scorer.num_beam_hyps_to_keep))
+
+    def _beam_search_prompts(self, prompts, mask, image_hidden_states, max_length, num_beams, early_stopping, length_penalty, keep):
+        """``beam_search`` on unexpanded prompts [S,T] (one per item)."""
+        self.sync_trainable_if_stale()
+        low = _hip.autocast_mode()
+        return self.engine().beam_search_prompted(image_hidden_states, prompts, mask, max_length, num_beams, early_stopping,
+                                                  length_penalty, bf16=low, num_return_sequences=keep, kv_fp8=self._kv_fp8())
+
+    @torch.no_grad()
+    def sample_from_prompt(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None,
+                           *, attention_mask: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                           num_return_sequences: int = 1, seed: Optional[int] = None, return_logprobs: bool = False):
+        """``sample`` that continues ``input_ids`` [S,T] (``attention_mask`` [S,T], zeros = LEFT padding, with the rules of
+        ``greedy_search``): int64 ids [S*n, L'] with the prompt in front, rows s*n + j for the n = num_return_sequences hypotheses
+        of row s; with ``return_logprobs`` also fp32 [S*n, L'], 0 in the prompt columns and for the PAD of finished rows.  One
+        token is always produced; ``max_length`` is ``greedy_search``'s.  Row r draws the token of column c from the Philox
+        counter (r, c - 1) under ``seed``, so a BOS column with a mask of ones IS ``sample()``."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        if attention_mask is None:
+            raise AttributeError("'NoneType' object has no attribute 'to' (sample_from_prompt needs attention_mask, like the "
+                                 "reference's forward, language_model.py:281)")
+        from .engine import _require_gpu
+        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
+        self.sync_trainable_if_stale()
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        low = _hip.autocast_mode()
+        ids, logprobs = self.engine().sample_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, temperature,
+                                                             int(top_k), top_p, int(seed), int(num_return_sequences), bf16=low,
+                                                             kv_fp8=self._kv_fp8())
+        return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
     def generate(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, num_beams: int = 1,

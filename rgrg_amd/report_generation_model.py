@@ -196,23 +196,68 @@ class ReportGenerationModel(EngineOwner):
         [B,29,T] (zeros = left padding) hold one prompt per region; the prompts of the SELECTED regions are continued by
         ``LanguageModel.greedy_search``.  Returns the 4-tuple of ``generate`` (output_ids [S,L'] with the prompts in front) or
         ``-1`` when no region is selected."""
+        sel = self._selected_prompts(images, region_prompts, region_prompt_mask)
+        if sel is None:
+            return -1
+        prompts, mask, feats, selected_regions, detections, class_detected = sel
+        output_ids = self.language_model.greedy_search(prompts, feats, max_length, attention_mask=mask, use_cache=True)
+        return output_ids, selected_regions, detections, class_detected
+
+    def _selected_prompts(self, images, region_prompts, region_prompt_mask):
+        """Detector and region selection of ``generate`` plus the prompts of the selected regions -> None when nothing is selected,
+        else (prompts [S,T], mask [S,T], features [S,1024], selected_regions, detections, class_detected)."""
         B = images.shape[0]
         if region_prompts.dim() != 3 or tuple(region_prompts.shape[:2]) != (B, 29):
             raise ValueError(f"region_prompts must be [B, 29, T] with B = {B}, got {tuple(region_prompts.shape)}")
         if tuple(region_prompt_mask.shape) != tuple(region_prompts.shape):
             raise ValueError(f"region_prompt_mask has shape {tuple(region_prompt_mask.shape)}, region_prompts {tuple(region_prompts.shape)}")
         _, detections, top_region_features, class_detected = self.object_detector(images)
-        del images
         selected_regions, selected_region_features = self.binary_classifier_region_selection(
             top_region_features, class_detected, return_loss=False)
-        del top_region_features
         if selected_region_features.shape[0] == 0:
-            return -1
+            return None
         prompts, mask = self.get_valid_decoder_input_for_evaluation(selected_regions, region_prompts.reshape(B * 29, -1),
                                                                     region_prompt_mask.reshape(B * 29, -1))
-        output_ids = self.language_model.greedy_search(prompts, selected_region_features, max_length, attention_mask=mask, use_cache=True)
-        del selected_region_features
+        return prompts, mask, selected_region_features, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def beam_search_from_prompts(self, images: torch.FloatTensor, region_prompts: torch.LongTensor, region_prompt_mask: torch.Tensor,
+                                 max_length: int, num_beams: int, early_stopping: bool = False, num_return_sequences: int = 1):
+        """``generate_from_prompts`` with beam search: the prompts of the SELECTED regions (one per region, unexpanded) are continued
+        by ``LanguageModel.beam_search`` with ``num_beams`` beams and length penalty 1.0, each prompt run once for all its beams.
+        Returns the 4-tuple of ``generate`` (output_ids [S * num_return_sequences, L]) or ``-1`` when no region is selected."""
+        if int(num_beams) != num_beams or num_beams < 2:
+            raise ValueError(f"num_beams has to be an integer > 1 for beam search, but is {num_beams}")
+        if not 1 <= num_return_sequences <= num_beams:
+            raise ValueError("'num_return_sequences' has to be between 1 and 'num_beams'.")
+        if max_length is None:
+            raise ValueError("max_length has to be set for beam generation.")
+        T = region_prompts.shape[-1]
+        if int(max_length) < T + 1:
+            raise ValueError(f"max_length has to be at least {T + 1} for prompts of {T} tokens, but is {max_length}")
+        sel = self._selected_prompts(images, region_prompts, region_prompt_mask)
+        if sel is None:
+            return -1
+        prompts, mask, feats, selected_regions, detections, class_detected = sel
+        output_ids = self.language_model._beam_search_prompts(prompts, mask, feats, int(max_length), int(num_beams), bool(early_stopping),
+                                                              1.0, int(num_return_sequences))
         return output_ids, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def sample_from_prompts(self, images: torch.FloatTensor, region_prompts: torch.LongTensor, region_prompt_mask: torch.Tensor,
+                            max_length: int = None, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                            num_return_sequences: int = 1, seed: Optional[int] = None, return_logprobs: bool = False):
+        """``generate_from_prompts`` with the continuations drawn by ``LanguageModel.sample_from_prompt``: the same 4-tuple
+        (``output_ids`` replaced by the sampler's return: ids, or (ids, logprobs) with ``return_logprobs``) or ``-1``."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        sel = self._selected_prompts(images, region_prompts, region_prompt_mask)
+        if sel is None:
+            return -1
+        prompts, mask, feats, selected_regions, detections, class_detected = sel
+        output = self.language_model.sample_from_prompt(prompts, feats, max_length, attention_mask=mask, temperature=temperature,
+                                                        top_k=top_k, top_p=top_p, num_return_sequences=num_return_sequences, seed=seed,
+                                                        return_logprobs=return_logprobs)
+        return output, selected_regions, detections, class_detected
 
     def set_kv_cache_dtype(self, name: Optional[str]) -> None:
         """``LanguageModel.set_kv_cache_dtype``: None, or "fp8_e4m3" for an e4m3 decode K/V cache under torch.autocast with more than
