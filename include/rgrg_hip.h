@@ -557,6 +557,68 @@ int rgrg_debug_ce_backward(float* logits, int64_t ld, int V, int row0, int rows,
 int rgrg_debug_gelu(const float* pre, float* out, float* d, int64_t n, void* stream);
 int rgrg_debug_dropout_add(const float* src, const float* resid, float* out, int64_t n, uint64_t seed, uint32_t stream_id, float p,
                            void* stream);
+/* ---- test hooks of the weight-streaming ("skinny") GEMMs of <= 128 token rows: the fused decode plan (skinny_direct.inc) and the
+ * prefill GEMMs (decoder.hip).  No decoder object: device pointers of the caller, launched on `stream`, through the shape rules,
+ * packing steps and kernel dispatch of the product path.  Every argument is validated first: RGRG_EINVAL with rgrg_last_error() set
+ * for M < 1 or M > 128, an unsupported K, N % 16 != 0 with a fragment-major output / residual / accumulator, a mode / lnf pair the
+ * plan does not have, a missing operand, or w16 != 0 on one row tile.
+ *
+ * Layouts.  Fragment-major [rows][L] (L % 16 == 0): element (row, k) at
+ *   ((((row / 32) * 2 + (row % 32) / 16) * (L / 16) + k / 16) * 64 + ((k % 16) / 4) * 16 + row % 16) * 4 + k % 4.
+ * Accumulators of a split-K GEMM with N columns: [row tile][2 accumulators][2 row halves][N / 16][64][4] - accumulator p of tile t is
+ * the fragment-major block of 32 rows at ((t * 2 + p) * 32 * N) floats.  Packed weights [NT = ceil(N / 16)][K / 16][64 lanes][4]:
+ * lane l of (tile, chunk) holds W[tile * 16 + l % 16][chunk * 16 + (l / 16) * 4 .. + 3], zero for rows >= N; 16-bit: same order.
+ * Buffer contract: every fragment-major buffer covers ceil(M / 32) * 32 rows; ids (rows of ld_ids) / tok_override / pos_override
+ * cover that many entries too and EVERY entry, pad rows included, is a valid row of wte (the kernels read them); the row-major X of
+ * rgrg_debug_skinny_linear covers ceil(M / 32) * 32 rows of K floats.  Values in pad rows never reach a stored row < M.
+ *
+ * rgrg_debug_direct_pack: the one-time packing of make_lin's fused branch and of set_precision's 16-bit copies.  W [N][K]; ln_g / ln_b
+ *   (both or neither): the LayerNorm folded into the GEMM; bias [N] or NULL; w16: 0 fp32, 1 bf16, 2 fp16.  K = 1024, or K = 4096 with
+ *   N = 1024 and no LayerNorm.  packed (always): fp32 fragments of W o ln_g.  ln_g given: c1 [N] = sum_k fl32(g W), c2 [N] = sum_k
+ *   beta W + bias.  w16: packed16 = packed rounded to the type (nearest even); with ln_g also c1_16 [NT * 16] = column sums of the
+ *   ROUNDED values.
+ * rgrg_debug_direct_linear: ONE launch of the plan's kernel choice (lm_head wave kernel / row-half kernel / generic kernel) on the
+ *   operands of rgrg_direct_args; NT and KS follow from N and K as in make_lin.  mode: 0 plain (Xf), 1 combine (Xf + the two
+ *   accumulators `part` of a 1024-column producer, (x + acc01) + acc23), 2 / 3 / 4 embedding (wte[ids[row][*step]] + wte[*step];
+ *   wte[tok_override[row]] + wte[*step]; wte[tok_override[row]] + wte[pos_override[row]]); modes 1-4 need lnf.  lnf: P holds the
+ *   gain-scaled weights, bias = c2 and c1 are required.  w16 != 0: P = packed16 and, with lnf, c1 = c1_16; more than 32 rows only.
+ *   K = 4096: the four K slices add into part_out (slices 2p, 2p + 1 into accumulator p, slice 0 with the bias), which the caller
+ *   zeroes beforehand; no other output.  Otherwise Y (row-major, ldy >= N) and / or Yf (fragment-major; rows >= M are written as 0)
+ *   = act(X W^T + bias + Rf); zero_acc: accumulators (N columns) the epilogue resets; xout (modes 1-4): the rebuilt rows, written
+ *   by workgroup (0, 0); cand_val / cand_idx [M][NT]: per 16-column tile the row maximum and its lowest column.  The lm_head wave
+ *   kernel (lnf, mode 1, NT > 512, <= 32 rows) writes Y and the candidates only.  *kernel_ran (optional): 0 generic, 1 row half,
+ *   2 lm_head wave.
+ * rgrg_debug_skinny_linear: Y[:M] = act(X W^T + bias + R) through pack_weights_kernel, launch_skinny_any and (K split over
+ *   workgroups) skinny_reduce_kernel with KS / chunks per wave as make_lin derives them; R and Y have row stride ldy >= N.  The
+ *   packed weights and partial sums are temporaries of the call, freed after a stream synchronise. */
+typedef struct rgrg_direct_args {
+    const float* Xf;
+    const float* part;
+    float* xout;
+    const float* wte;
+    const int64_t* ids;
+    int ld_ids;
+    const int* step;
+    const int* tok_override;
+    const int* pos_override;
+    const void* P;
+    const float* bias;
+    const float* c1;
+    const float* Rf;
+    float* Y;
+    int ldy;
+    float* Yf;
+    float* part_out;
+    float* zero_acc;
+    int K, N, act;
+    float* cand_val;
+    int* cand_idx;
+} rgrg_direct_args;
+int rgrg_debug_direct_pack(const float* W, const float* ln_g, const float* ln_b, const float* bias, int N, int K, int w16,
+                           float* packed, uint16_t* packed16, float* c1, float* c2, float* c1_16, void* stream);
+int rgrg_debug_direct_linear(const rgrg_direct_args* args, int mode, int lnf, int w16, int M, int* kernel_ran, void* stream);
+int rgrg_debug_skinny_linear(const float* X, const float* W, const float* bias, const float* R, float* Y, int M, int N, int K,
+                             int ldy, int act, void* stream);
 /* ---- detector targets and losses: ObjectDetector.forward(images, targets), the detector half of
  * ReportGenerationModel.forward(images, image_targets, ...) (src/full_model/report_generation_model.py:55,91 ->
  * src/object_detector/object_detector.py:216-224 -> custom_rpn.py:74-83, custom_roi_heads.py:225-242, and underneath

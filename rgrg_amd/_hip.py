@@ -16,7 +16,7 @@ c_float_p = C.c_void_p  # device pointers travel as void*
 _i, _f, _p = C.c_int, C.c_float, C.c_void_p
 
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
-ABI_VERSION = 27  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
+ABI_VERSION = 28  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
 
 
 class RgrgHipError(RuntimeError):
@@ -26,6 +26,13 @@ class RgrgHipError(RuntimeError):
 class DecoderLayerWeights(C.Structure):
     _fields_ = [(n, _p) for n in ("ln1_g", "ln1_b", "ln2_g", "ln2_b", "c_attn_w", "c_attn_b", "attn_proj_w",
                                   "attn_proj_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b")]
+
+
+class DirectArgs(C.Structure):
+    """rgrg_direct_args: the operands of one GEMM of the fused decode plan (rgrg_debug_direct_linear)."""
+    _fields_ = [("Xf", _p), ("part", _p), ("xout", _p), ("wte", _p), ("ids", _p), ("ld_ids", _i), ("step", _p), ("tok_override", _p),
+                ("pos_override", _p), ("P", _p), ("bias", _p), ("c1", _p), ("Rf", _p), ("Y", _p), ("ldy", _i), ("Yf", _p),
+                ("part_out", _p), ("zero_acc", _p), ("K", _i), ("N", _i), ("act", _i), ("cand_val", _p), ("cand_idx", _p)]
 
 
 class DecoderWeights(C.Structure):
@@ -87,6 +94,9 @@ SIGNATURES = {
     "rgrg_debug_linear_bf16_train": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_argmax": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _i, _p]),
     "rgrg_debug_ln_fold16": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "rgrg_debug_direct_pack": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "rgrg_debug_direct_linear": (_i, [C.POINTER(DirectArgs), _i, _i, _i, _i, C.POINTER(_i), _p]),
+    "rgrg_debug_skinny_linear": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln_kp": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_wide_epilogue_launches": (_i, []),

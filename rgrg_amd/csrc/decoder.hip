@@ -925,35 +925,70 @@ static int pick_ks(int NT, int chunks) {
     return ks;
 }
 
+// Shapes and one-time packing of the two weight-streaming families.  make_lin / rgrg_decoder_set_precision run them on the decoder's
+// buffers, the test hooks rgrg_debug_direct_pack / rgrg_debug_direct_linear / rgrg_debug_skinny_linear on the caller's - the rules
+// exist once, here.
+// fused plan: 16-column tiles, one 1024-wide K slice per workgroup (mlp_proj: 4 slices -> 256 workgroups, the fp32 MFMA work needs
+// every CU; the 4 partial sums are added by the consumer while it loads its fragments)
+static bool direct_shape(int N, int K, bool lnf, int* KS, int* NT) {
+    if (N < 1 || !(K == DK_SLICE || (K == 4 * DK_SLICE && !lnf && N == DK_SLICE))) return false;
+    *KS = K / DK_SLICE; *NT = (N + 15) / 16;
+    return true;
+}
+// packed [NT][K / 16][64][4] = (W o ln_g) in fragment order; c1 / c2 (ln_g given): the folded LayerNorm vectors
+static int direct_pack(const float* w, const float* b, const float* ln_g, const float* ln_b, int N, int K, int NT, float* packed,
+                       float* c1, float* c2, hipStream_t st) {
+    hipLaunchKernelGGL(pack_weights16_scaled_kernel, dim3(2048), dim3(256), 0, st, w, ln_g, packed, N, K, NT);
+    RGRG_LAUNCH_CHECK();
+    if (ln_g) {
+        hipLaunchKernelGGL(ln_fold_vectors_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, ln_g, ln_b, b, c1, c2, N, K);
+        RGRG_LAUNCH_CHECK();
+    }
+    return RGRG_OK;
+}
+// the 16-bit-weight copy: the fp32 fragments rounded to the type, and (c1_16 given: GEMMs behind a LayerNorm) the column sums of the
+// ROUNDED values [NT * 16]
+static int direct_pack16(const float* packed, void* packed16, float* c1_16, int NT, int K, int f16, hipStream_t st) {
+    int r = convert_f32_to_bf16(packed, packed16, (size_t)NT * 16 * K, st, f16);
+    if (r) return r;
+    if (c1_16) {
+        hipLaunchKernelGGL(packed16_colsum_kernel, dim3(NT), dim3(64), 0, st, (const unsigned short*)packed16, c1_16, NT * 16, K, f16);
+        RGRG_LAUNCH_CHECK();
+    }
+    return RGRG_OK;
+}
+// prefill GEMMs (fst-nn, uk/uv): LDS-staged weight-streaming kernel, 32-column tiles; *pw = one-KiB chunks per wave
+static bool skinny_shape(int N, int K, int* KS, int* NT, int* pw) {
+    const int kc = 8;
+    *NT = (N + 31) / 32;
+    *KS = pick_ks(*NT, K / 8);
+    *pw = K / (kc * *KS * SK_WAVES);
+    return N >= 1 && K >= 1 && (K % (kc * *KS * SK_WAVES) == 0) && (*pw == 4 || *pw == 8 || *pw == 16);
+}
+static int skinny_pack(const float* w, float* packed, int N, int K, int NT, hipStream_t st) {
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(2048), dim3(256), 0, st, w, packed, N, K, NT);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
 static int make_lin(rgrg_decoder* d, Lin& l, const float* w, const float* b, int N, int K, bool pack,
                     bool direct = false, const float* ln_g = nullptr, const float* ln_b = nullptr) {
     l.w = w; l.b = b; l.N = N; l.K = K;
     if (direct) {
-        // fused plan: 16-column tiles, one 1024-wide K slice per workgroup (mlp_proj: 4 slices -> 256 workgroups, the
-        // fp32 MFMA work needs every CU; the 4 partial sums are added by the consumer while it loads its fragments)
-        if (!(K == DK_SLICE || (K == 4 * DK_SLICE && !ln_g && N == DK_SLICE))) { set_error("decoder: N=%d K=%d unsupported by the fused plan", N, K); return RGRG_EINVAL; }
-        l.direct = true; l.ntile = 16; l.KS = K / DK_SLICE; l.NT = (N + 15) / 16; l.lnf = ln_g != nullptr;
+        if (!direct_shape(N, K, ln_g != nullptr, &l.KS, &l.NT)) { set_error("decoder: N=%d K=%d unsupported by the fused plan", N, K); return RGRG_EINVAL; }
+        l.direct = true; l.ntile = 16; l.lnf = ln_g != nullptr;
         int rc = dmalloc(d, (void**)&l.packed, (size_t)l.NT * 16 * K * sizeof(float), false);
         if (rc) return rc;
-        hipLaunchKernelGGL(pack_weights16_scaled_kernel, dim3(2048), dim3(256), 0, d->stream, w, ln_g, l.packed, N, K, l.NT);
-        RGRG_LAUNCH_CHECK();
         if (l.lnf) {
             if ((rc = dmalloc(d, (void**)&l.c1, (size_t)N * sizeof(float), false)) ||
                 (rc = dmalloc(d, (void**)&l.c2, (size_t)N * sizeof(float), false)))
                 return rc;
-            hipLaunchKernelGGL(ln_fold_vectors_kernel, dim3((N + 3) / 4), dim3(256), 0, d->stream, w, ln_g, ln_b, b, l.c1, l.c2, N, K);
-            RGRG_LAUNCH_CHECK();
         }
-        return RGRG_OK;
+        return direct_pack(w, b, ln_g, ln_b, N, K, l.NT, l.packed, l.c1, l.c2, d->stream);
     }
-    // prefill GEMMs (fst-nn, uk/uv): LDS-staged weight-streaming kernel, 32-column tiles
     l.ntile = 32;
-    l.KS = pick_ks((N + 31) / 32, K / 8);
-    l.NT = (N + l.ntile - 1) / l.ntile;
-    const int kc = 8;
-    const int pw = K / (kc * l.KS * SK_WAVES);
-    const bool ok = (K % (kc * l.KS * SK_WAVES) == 0) && (pw == 4 || pw == 8 || pw == 16);
-    if (!ok) {
+    int pw;
+    if (!skinny_shape(N, K, &l.KS, &l.NT, &pw)) {
         set_error("decoder: no skinny GEMM instance for N=%d K=%d (ntile %d, KS %d, %d chunks per wave)", N, K, l.ntile, l.KS, pw);
         return RGRG_EINVAL;
     }
@@ -961,8 +996,7 @@ static int make_lin(rgrg_decoder* d, Lin& l, const float* w, const float* b, int
         const size_t bytes = (size_t)l.NT * l.ntile * K * sizeof(float);
         int rc = dmalloc(d, (void**)&l.packed, bytes, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(pack_weights_kernel, dim3(2048), dim3(256), 0, d->stream, w, l.packed, N, K, l.NT);
-        RGRG_LAUNCH_CHECK();
+        return skinny_pack(w, l.packed, N, K, l.NT, d->stream);
     }
     return RGRG_OK;
 }
@@ -1208,6 +1242,53 @@ static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsig
     return launch_attn_decode(a);
 }
 
+// The kernel choice of the fused plan for one GEMM whose DirectArgs are complete: lm_head' on one row tile -> a wave per column tile;
+// attn_proj' on 17-32 rows -> one row half per workgroup; everything else the generic kernel <row tiles, MODE, LNF, W16>.
+// direct_linear calls it with the decoder's buffers, the test hook rgrg_debug_direct_linear with the caller's.  *ran (optional)
+// receives the DX_RAN_* code of the kernel that was launched.
+constexpr int DX_RAN_GENERIC = 0, DX_RAN_HALF = 1, DX_RAN_LM_WAVE = 2;
+static int direct_dispatch(const DirectArgs& a, bool lnf, int mode, int w16, hipStream_t st, int* ran = nullptr) {
+    const int mt = (a.M + PAD_ROWS - 1) / PAD_ROWS;
+    const dim3 grid(a.NT, a.KS), blk(64 * SK_WAVES);
+    if (lnf && mode == DX_COMBINE4 && a.NT > 512 && mt == 1 && a.K == DK_SLICE) {  // lm_head, one row tile: a wave per column tile
+        hipLaunchKernelGGL((rgrg_lm_head_wave_f32<DX_COMBINE4>), dim3(256), blk, LMH_LDS, st, a);
+        if (ran) *ran = DX_RAN_LM_WAVE;
+    } else if (!lnf && mode == DX_PLAIN && a.KS == 1 && mt == 1 && a.NT <= 64 && a.M > 16 && !a.cand_val) {
+        // attn_proj': few column tiles, MFMA bound -> one row half per workgroup (2 x NT workgroups)
+        hipLaunchKernelGGL(rgrg_skinny_direct_half_f32, dim3(a.NT, 2), blk, 0, st, a);
+        if (ran) *ran = DX_RAN_HALF;
+    } else {
+#define DX_LAUNCH(MT_, MODE_, LNF_)                                                                                          \
+    do {                                                                                                                      \
+        if constexpr (MT_ > 1) {                                                                                              \
+            if (w16 == 1) { hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_, 1>), grid, blk, 0, st, a); break; }  \
+            if (w16 == 2) { hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_, 2>), grid, blk, 0, st, a); break; }  \
+        }                                                                                                                     \
+        hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_>), grid, blk, 0, st, a);                                  \
+    } while (0)
+#define DX_MODES(MT_)                                                                        \
+    do {                                                                                     \
+        if (!lnf && mode == DX_PLAIN) DX_LAUNCH(MT_, DX_PLAIN, false);                       \
+        else if (lnf && mode == DX_PLAIN) DX_LAUNCH(MT_, DX_PLAIN, true);                    \
+        else if (lnf && mode == DX_COMBINE4) DX_LAUNCH(MT_, DX_COMBINE4, true);              \
+        else if (lnf && mode == DX_EMBED) DX_LAUNCH(MT_, DX_EMBED, true);                    \
+        else if (lnf && mode == DX_EMBED_TOK) DX_LAUNCH(MT_, DX_EMBED_TOK, true);            \
+        else if (lnf && mode == DX_EMBED_TOKPOS) DX_LAUNCH(MT_, DX_EMBED_TOKPOS, true);      \
+        else { set_error("direct_linear: unsupported mode %d (lnf %d)", mode, (int)lnf); return RGRG_EINVAL; } \
+    } while (0)
+        if (mt == 1) DX_MODES(1);
+        else if (mt == 2) DX_MODES(2);
+        else if (mt == 3) DX_MODES(3);
+        else if (mt == 4) DX_MODES(4);
+        else { set_error("direct_linear: %d rows exceed 4 row tiles", a.M); return RGRG_EINVAL; }
+#undef DX_MODES
+#undef DX_LAUNCH
+        if (ran) *ran = DX_RAN_GENERIC;
+    }
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
 // One GEMM of the fused plan.  `a` arrives with the operand / output pointers and `act` set; the layer fills the rest.
 static int direct_linear(rgrg_decoder* d, const Lin& l, DirectArgs a, int mode, int M, bool count, bool cand = false) {
     if (!l.direct) { set_error("direct_linear: layer was not packed for the fused plan"); return RGRG_EINVAL; }
@@ -1220,41 +1301,8 @@ static int direct_linear(rgrg_decoder* d, const Lin& l, DirectArgs a, int mode, 
     // under autocast, more than one row tile: the 16-bit-weight kernels (one row tile - batch-1 greedy decoding - stays bit-exact fp32)
     const int w16 = (d->bf16_gemms && d->w16_fused && mt > 1 && l.packed16 && l.packed16_f16 == d->f16() && (!l.lnf || l.c1_16)) ? (d->f16() ? 2 : 1) : 0;
     if (w16) { a.P = reinterpret_cast<const float*>(l.packed16); if (l.lnf) a.c1 = l.c1_16; }
-    const dim3 grid(l.NT, l.KS), blk(64 * SK_WAVES);
-    hipStream_t st = d->stream;
-    if (l.lnf && mode == DX_COMBINE4 && l.NT > 512 && mt == 1 && l.K == DK_SLICE) {  // lm_head, one row tile: a wave per column tile
-        hipLaunchKernelGGL((rgrg_lm_head_wave_f32<DX_COMBINE4>), dim3(256), blk, LMH_LDS, st, a);
-    } else if (!l.lnf && mode == DX_PLAIN && l.KS == 1 && mt == 1 && l.NT <= 64 && M > 16 && !cand) {
-        // attn_proj': few column tiles, MFMA bound -> one row half per workgroup (2 x NT workgroups)
-        hipLaunchKernelGGL(rgrg_skinny_direct_half_f32, dim3(l.NT, 2), blk, 0, st, a);
-    } else {
-#define DX_LAUNCH(MT_, MODE_, LNF_)                                                                                          \
-    do {                                                                                                                      \
-        if constexpr (MT_ > 1) {                                                                                              \
-            if (w16 == 1) { hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_, 1>), grid, blk, 0, st, a); break; }  \
-            if (w16 == 2) { hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_, 2>), grid, blk, 0, st, a); break; }  \
-        }                                                                                                                     \
-        hipLaunchKernelGGL((rgrg_skinny_direct_f32<MT_, MODE_, LNF_>), grid, blk, 0, st, a);                                  \
-    } while (0)
-#define DX_MODES(MT_)                                                                        \
-    do {                                                                                     \
-        if (!l.lnf && mode == DX_PLAIN) DX_LAUNCH(MT_, DX_PLAIN, false);                     \
-        else if (l.lnf && mode == DX_PLAIN) DX_LAUNCH(MT_, DX_PLAIN, true);                  \
-        else if (l.lnf && mode == DX_COMBINE4) DX_LAUNCH(MT_, DX_COMBINE4, true);            \
-        else if (l.lnf && mode == DX_EMBED) DX_LAUNCH(MT_, DX_EMBED, true);                  \
-        else if (l.lnf && mode == DX_EMBED_TOK) DX_LAUNCH(MT_, DX_EMBED_TOK, true);          \
-        else if (l.lnf && mode == DX_EMBED_TOKPOS) DX_LAUNCH(MT_, DX_EMBED_TOKPOS, true);    \
-        else { set_error("direct_linear: unsupported mode %d (lnf %d)", mode, (int)l.lnf); return RGRG_EINVAL; } \
-    } while (0)
-        if (mt == 1) DX_MODES(1);
-        else if (mt == 2) DX_MODES(2);
-        else if (mt == 3) DX_MODES(3);
-        else if (mt == 4) DX_MODES(4);
-        else { set_error("direct_linear: %d rows exceed 4 row tiles", M); return RGRG_EINVAL; }
-#undef DX_MODES
-#undef DX_LAUNCH
-    }
-    RGRG_LAUNCH_CHECK();
+    const int rc = direct_dispatch(a, l.lnf, mode, w16, d->stream);
+    if (rc) return rc;
     if (count) {
         d->gemm_bytes_per_step += (size_t)l.N * l.K * (w16 ? 2 : sizeof(float));
         d->gemm_flops_per_step += 2.0 * M * l.N * l.K;
@@ -1921,8 +1969,8 @@ extern "C" int rgrg_decoder_refresh_trainable(rgrg_decoder* d, void* stream) {
     Lin* ls[] = {&d->fst0, &d->fst2, &d->ukv};
     for (Lin* l : ls) {
         if (l->packed) {
-            hipLaunchKernelGGL(pack_weights_kernel, dim3(2048), dim3(256), 0, st, l->w, l->packed, l->N, l->K, l->NT);
-            RGRG_LAUNCH_CHECK();
+            int rc = skinny_pack(l->w, l->packed, l->N, l->K, l->NT, st);
+            if (rc) return rc;
         }
         if (l->wT) {
             int rc = launch_transpose_pad(l->w, l->wT, l->N, l->K, pad256(l->N), st);
@@ -2031,6 +2079,106 @@ extern "C" int rgrg_debug_ln_fold16(const float* w, const float* gain, const flo
     return RGRG_OK;
 }
 
+// Test hooks of the two weight-streaming families (tests/test_gpu_skinny_gemms.py).  No decoder: the caller's device buffers, the
+// given stream, and the shape rules / packing steps / kernel dispatch of the product path (direct_shape, direct_pack, direct_pack16,
+// direct_dispatch, skinny_shape, skinny_pack, launch_skinny_any).  Every argument is validated before anything is launched.
+#define DBG_REJECT(cond, ...)                                     \
+    do {                                                          \
+        if (cond) { set_error(__VA_ARGS__); return RGRG_EINVAL; } \
+    } while (0)
+
+extern "C" int rgrg_debug_direct_pack(const float* W, const float* ln_g, const float* ln_b, const float* bias, int N, int K, int w16,
+                                      float* packed, uint16_t* packed16, float* c1, float* c2, float* c1_16, void* stream) {
+    const bool lnf = ln_g != nullptr;
+    int KS, NT;
+    DBG_REJECT(!W || !packed, "rgrg_debug_direct_pack: missing operand (W / packed)");
+    DBG_REJECT((ln_g != nullptr) != (ln_b != nullptr), "rgrg_debug_direct_pack: LayerNorm gain and beta go together");
+    DBG_REJECT(w16 < 0 || w16 > 2, "rgrg_debug_direct_pack: w16 = %d (0 fp32, 1 bf16, 2 fp16)", w16);
+    DBG_REJECT(!direct_shape(N, K, lnf, &KS, &NT), "rgrg_debug_direct_pack: N=%d K=%d unsupported by the fused plan", N, K);
+    DBG_REJECT(lnf && (!c1 || !c2), "rgrg_debug_direct_pack: missing operand (c1 / c2 of a folded LayerNorm)");
+    DBG_REJECT(w16 && !packed16, "rgrg_debug_direct_pack: missing operand (packed16)");
+    DBG_REJECT(w16 && lnf && !c1_16, "rgrg_debug_direct_pack: missing operand (c1_16)");
+    hipStream_t st = as_stream(stream);
+    int rc = direct_pack(W, bias, ln_g, ln_b, N, K, NT, packed, c1, c2, st);
+    if (rc || !w16) return rc;
+    return direct_pack16(packed, packed16, lnf ? c1_16 : nullptr, NT, K, w16 == 2 ? 1 : 0, st);
+}
+
+extern "C" int rgrg_debug_direct_linear(const rgrg_direct_args* u, int mode, int lnf, int w16, int M, int* kernel_ran, void* stream) {
+    DBG_REJECT(!u, "rgrg_debug_direct_linear: missing operand (args)");
+    DBG_REJECT(M < 1 || M > SKINNY_MAX_ROWS, "rgrg_debug_direct_linear: %d rows (1 .. %d)", M, SKINNY_MAX_ROWS);
+    DBG_REJECT(lnf != 0 && lnf != 1, "rgrg_debug_direct_linear: lnf = %d", lnf);
+    DBG_REJECT(!((!lnf && mode == DX_PLAIN) || (lnf && mode >= DX_PLAIN && mode <= DX_EMBED_TOKPOS)),
+               "rgrg_debug_direct_linear: unsupported mode %d (lnf %d)", mode, lnf);
+    DBG_REJECT(w16 < 0 || w16 > 2, "rgrg_debug_direct_linear: w16 = %d (0 fp32, 1 bf16, 2 fp16)", w16);
+    DBG_REJECT(w16 && M <= PAD_ROWS, "rgrg_debug_direct_linear: the 16-bit-weight kernels need more than one row tile (%d rows)", M);
+    DBG_REJECT(u->act < RGRG_ACT_NONE || u->act > RGRG_ACT_GELU_NEW, "rgrg_debug_direct_linear: act = %d", u->act);
+    DirectArgs a{};
+    DBG_REJECT(!direct_shape(u->N, u->K, lnf != 0, &a.KS, &a.NT), "rgrg_debug_direct_linear: N=%d K=%d unsupported by the fused plan", u->N, u->K);
+    DBG_REJECT(!u->P || (lnf && (!u->bias || !u->c1)), "rgrg_debug_direct_linear: missing operand (P; c2 as bias and c1 when lnf)");
+    DBG_REJECT((mode == DX_PLAIN || mode == DX_COMBINE4) && !u->Xf, "rgrg_debug_direct_linear: missing operand (Xf)");
+    DBG_REJECT(mode == DX_COMBINE4 && !u->part, "rgrg_debug_direct_linear: missing operand (part)");
+    DBG_REJECT(mode >= DX_EMBED && !u->wte, "rgrg_debug_direct_linear: missing operand (wte)");
+    DBG_REJECT(mode == DX_EMBED && (!u->ids || !u->step || u->ld_ids < 1), "rgrg_debug_direct_linear: missing operand (ids / ld_ids / step)");
+    DBG_REJECT(mode == DX_EMBED_TOK && (!u->tok_override || !u->step), "rgrg_debug_direct_linear: missing operand (tok_override / step)");
+    DBG_REJECT(mode == DX_EMBED_TOKPOS && (!u->tok_override || !u->pos_override), "rgrg_debug_direct_linear: missing operand (tok_override / pos_override)");
+    DBG_REJECT(mode == DX_PLAIN && u->xout, "rgrg_debug_direct_linear: xout goes with a mode that rebuilds the residual stream");
+    DBG_REJECT((u->cand_val != nullptr) != (u->cand_idx != nullptr), "rgrg_debug_direct_linear: missing operand (cand_val and cand_idx go together)");
+    if (a.KS > 1) {
+        DBG_REJECT(!u->part_out, "rgrg_debug_direct_linear: missing operand (part_out of a split-K GEMM)");
+        DBG_REJECT(u->Y || u->Yf || u->Rf || u->zero_acc || u->cand_val, "rgrg_debug_direct_linear: a split-K GEMM writes part_out only");
+    } else {
+        DBG_REJECT(u->part_out, "rgrg_debug_direct_linear: part_out goes with K = %d", 4 * DK_SLICE);
+        DBG_REJECT(!u->Y && !u->Yf, "rgrg_debug_direct_linear: missing operand (Y or Yf)");
+        DBG_REJECT(u->Y && u->ldy < u->N, "rgrg_debug_direct_linear: ldy %d < N %d", u->ldy, u->N);
+    }
+    DBG_REJECT((u->Yf || u->Rf || u->zero_acc || u->part_out) && u->N % 16 != 0,
+               "rgrg_debug_direct_linear: N = %d with a fragment-major output, residual or accumulator (N %% 16 == 0)", u->N);
+    a.Xf = u->Xf; a.part = u->part; a.xout = u->xout; a.wte = u->wte; a.ids = reinterpret_cast<const long long*>(u->ids); a.ld_ids = u->ld_ids;
+    a.step = u->step; a.tok_override = u->tok_override; a.pos_override = u->pos_override;
+    a.P = reinterpret_cast<const float*>(u->P); a.bias = u->bias; a.c1 = u->c1; a.Rf = u->Rf; a.Y = u->Y; a.ldy = u->ldy; a.Yf = u->Yf;
+    a.part_out = u->part_out; a.zero_acc = u->zero_acc; a.M = M; a.K = u->K; a.N = u->N; a.act = u->act;
+    a.cand_val = u->cand_val; a.cand_idx = u->cand_idx;
+    int rc = init_skinny_attrs();
+    if (rc) return rc;
+    return direct_dispatch(a, lnf != 0, mode, w16, as_stream(stream), kernel_ran);
+}
+
+extern "C" int rgrg_debug_skinny_linear(const float* X, const float* W, const float* bias, const float* R, float* Y, int M, int N, int K,
+                                        int ldy, int act, void* stream) {
+    DBG_REJECT(!X || !W || !Y, "rgrg_debug_skinny_linear: missing operand (X / W / Y)");
+    DBG_REJECT(M < 1 || M > SKINNY_MAX_ROWS, "rgrg_debug_skinny_linear: %d rows (1 .. %d)", M, SKINNY_MAX_ROWS);
+    DBG_REJECT(act < RGRG_ACT_NONE || act > RGRG_ACT_GELU_NEW, "rgrg_debug_skinny_linear: act = %d", act);
+    int KS, NT, pw;
+    DBG_REJECT(N < 1 || K < 64 || !skinny_shape(N, K, &KS, &NT, &pw), "rgrg_debug_skinny_linear: no skinny GEMM instance for N=%d K=%d", N, K);
+    DBG_REJECT(ldy < N, "rgrg_debug_skinny_linear: ldy %d < N %d", ldy, N);
+    hipStream_t st = as_stream(stream);
+    int rc = init_skinny_attrs();
+    if (rc) return rc;
+    const int mt = (M + PAD_ROWS - 1) / PAD_ROWS;
+    float *packed = nullptr, *part = nullptr;
+    RGRG_HIP(hipMalloc((void**)&packed, (size_t)NT * 32 * K * sizeof(float)));
+    if (KS > 1 && hipMalloc((void**)&part, (size_t)mt * KS * PAD_ROWS * NT * 32 * sizeof(float)) != hipSuccess) {
+        (void)hipFree(packed);
+        set_error("rgrg_debug_skinny_linear: out of device memory");
+        return RGRG_EHIP;
+    }
+    rc = skinny_pack(W, packed, N, K, NT, st);
+    SkinnyArgs a{X, packed, bias, R, Y, part, M, K, N, NT, KS, ldy, act};
+    if (!rc) rc = launch_skinny_any(a, st);
+    if (!rc && KS > 1) {
+        const int total = M * N;
+        hipLaunchKernelGGL(skinny_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a);
+        if (hipGetLastError() != hipSuccess) { set_error("rgrg_debug_skinny_linear: skinny_reduce_kernel launch failed"); rc = RGRG_EHIP; }
+    }
+    const hipError_t e = hipStreamSynchronize(st);   // the temporaries are the call's own: they must outlive the launches
+    (void)hipFree(packed);
+    (void)hipFree(part);
+    if (!rc && e != hipSuccess) { set_error("rgrg_debug_skinny_linear: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return rc;
+}
+#undef DBG_REJECT
+
 static int set_precision_impl(rgrg_decoder* d, int mode);
 extern "C" int rgrg_decoder_set_precision(rgrg_decoder* d, int mode) {
     RGRG_CHECK_ARG(d && mode >= 0 && mode <= 2);
@@ -2088,10 +2236,7 @@ static int set_precision_impl(rgrg_decoder* d, int mode) {
                 int r;
                 if (!l.packed16 && (r = dmalloc(d, &l.packed16, n * 2, false))) return r;
                 if (l.lnf && !l.c1_16 && (r = dmalloc(d, (void**)&l.c1_16, (size_t)l.NT * 16 * sizeof(float), false))) return r;
-                if ((r = convert_f32_to_bf16(l.packed, l.packed16, n, d->stream, d->f16()))) return r;
-                if (l.lnf)
-                    hipLaunchKernelGGL(packed16_colsum_kernel, dim3(l.NT), dim3(64), 0, d->stream, (const unsigned short*)l.packed16, l.c1_16, l.NT * 16, l.K,
-                                       d->f16());
+                if ((r = direct_pack16(l.packed, l.packed16, l.lnf ? l.c1_16 : nullptr, l.NT, l.K, d->f16(), d->stream))) return r;
                 l.packed16_f16 = d->f16();
                 return RGRG_OK;
             };

@@ -85,4 +85,4 @@ def test_header_declares_the_new_entries_like_the_binding():
         assert len(m.group(1).split(",")) == len(_hip.SIGNATURES[name][1]), name
     declared = set(re.findall(r"\b(rgrg_[a-z0-9_]+)\s*\(", header))
     assert set(_hip.SIGNATURES) <= declared
-    assert _hip.ABI_VERSION == 27   # 26 brought the prompted entries, 27 the hooks of the training pass's row kernels
+    assert _hip.ABI_VERSION == 28   # 26 brought the prompted entries, 27 the hooks of the training pass's row kernels, 28 those of the skinny GEMMs
