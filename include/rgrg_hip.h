@@ -261,6 +261,43 @@ int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int S, int num
 int rgrg_decoder_beam_search_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
                                       int T, int num_beams, int max_length, int early_stopping, float length_penalty,
                                       int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream);
+/* Diverse beam search (transformers 4.19.2 group_beam_search with its HammingDiversityLogitsProcessor; the reference's generate()
+ * refuses num_beam_groups > 1, LanguageModel.group_beam_search is this build's own entry).  G = num_beam_groups groups of
+ * gs = num_beams / G beam rows per item: group g of item s owns rows s * num_beams + g * gs .. + gs - 1 and starts with beam score
+ * 0 in its first row, -1e9 in the others.  Every step runs ONE decode step over the S * num_beams rows, beam_row_topk_kernel with
+ * K = 2 * num_beams candidates per row, and ONE launch of beam_group_merge_kernel (one workgroup per item) that ranks the groups
+ * in order: group g's candidates are penalised by the tokens that groups 0 .. g-1 of the item took IN THIS STEP - the first gs
+ * non-EOS candidates of each in rank order - a token taken by two beams counting twice.
+ *   Arithmetic contract (fp32, every operation rounded once, the multiply never contracted into the subtract):
+ *     score = ((v - row_max) - row_logsum) - round(diversity_penalty * (float)freq) + beam_score
+ *   ranked per group over its gs * 2 num_beams row candidates: score descending, ties to the lower flat index
+ *   beam_in_group * V + token; the top 2 gs of group g go to candidate slots g * 2 gs .. of the item's 2 num_beams slots.
+ * The penalty is read from a device word written before the loop: the captured step (keyed on num_beams AND num_beam_groups, never
+ * shared with a plain beam step) serves every penalty.  Host side: BeamSearchScorer.process per item and group with group_size gs.
+ * HF's quirks are kept: the hypothesis heap (capacity num_beams) and the `done` flag belong to the ITEM and are shared by its
+ * groups, is_done takes the group's best candidate score, so `done` can flip between two groups of a step - the later groups of
+ * that item then take PAD with score 0 and finalize skips the item; cur_len is the same for all groups of a step; finalize returns
+ * the num_return_sequences best hypotheses of the item's heap overall, not one per group.  num_beam_groups = 1 applies no penalty
+ * and IS rgrg_decoder_beam_search (same ids).
+ *   RGRG_EINVAL (with a message): num_beams % num_beam_groups != 0; num_beam_groups > num_beams; num_beam_groups > 1 with a
+ *   diversity_penalty that is not a finite float > 0; num_beams > 16 (the K-round ranking kernels of wider beams have no group
+ *   form); num_return_sequences outside 1 .. num_beams. */
+int rgrg_decoder_group_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int num_beam_groups,
+                                   float diversity_penalty, int max_length, int early_stopping, float length_penalty,
+                                   int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream);
+/* ... from a prompt: the prompt arguments, mask rules and refusals of rgrg_decoder_beam_search_prompted (max_length < T + 1, the
+ * mask refusals, the e4m3 K/V cache in use for S * num_beams rows) on top of the refusals above.  The first ranking is the group
+ * ranking of the item's last prompt position on num_beams identical rows. */
+int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask,
+                                            int S, int T, int num_beams, int num_beam_groups, float diversity_penalty, int max_length,
+                                            int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
+                                            int out_ld, int* out_len, void* stream);
+/* Test hook: beam_group_merge_kernel alone on caller buffers.  row_max / row_logsum / beam_scores f32 [S * nb], top_val f32 /
+ * top_tok i32 [S * nb][32] (rows as wide as in the decoder, the first 2 nb entries used) -> out_score f32 / out_tok i32 /
+ * out_beam i32 [S][2 nb] (out_beam: the row within the item).  nb <= 16, G divides nb.  Synchronizes the stream. */
+int rgrg_debug_beam_group_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+                                const float* beam_scores, int S, int nb, int G, float penalty, int V, float* out_score, int* out_tok,
+                                int* out_beam, void* stream);
 /* Opt-in reduced precision for MANY sequences (BASELINE configs[2], batch 32): mode 1 (bfloat16) / 2 (float16) makes the
  * > 128-row paths run their projections on the 16-bit MFMA (16-bit weights and GEMM inputs, fp32 accumulate / LayerNorm /
  * softmax / residual) and keep the decode K/V cache in that type (what the reference's torch.autocast does to `present`);

@@ -167,6 +167,77 @@ __global__ __launch_bounds__(BEAM_MERGE_THREADS) void beam_merge_kernel(const fl
     }
 }
 
+// Diverse (grouped) beam search, transformers 4.19.2 group_beam_search with its HammingDiversityLogitsProcessor: one workgroup per
+// item runs the G groups of num_beams / G rows IN ORDER - group g's candidates are penalised by the tokens groups 0 .. g-1 took in
+// this very step - behind the same beam_row_topk_kernel (K = 2 nb candidates per row).  Per group: one thread per candidate of the
+// gs * K row candidates, score by the contract of include/rgrg_hip.h ("Diverse beam search": every operation rounded once, the
+// multiply NOT contracted into the subtract), ranked against all others through LDS (score desc; ties: lower flat index
+// beam_in_group * V + token), top 2 gs -> columns g * 2 gs .. of the item's K = G * 2 gs candidate slots (`beam` = the row within
+// the item), and the first gs non-EOS tokens in rank order - what BeamSearchScorer.process hands back as the group's next tokens -
+// join the LDS list the later groups count their penalty from.  The row lists are enough: at most nb - gs tokens are penalised and
+// a penalty only lowers a value, so a row's list keeps >= nb + gs >= 2 gs unpenalised entries, each of which beats every unlisted
+// token of the row.  A finished item needs no special case: the host ignores its candidates.  *penalty is read from device memory,
+// so one captured step serves every penalty.
+__global__ __launch_bounds__(BEAM_MERGE_THREADS) void beam_group_merge_kernel(const float* __restrict__ row_max, const float* __restrict__ row_logsum,
+                                                               const float* __restrict__ top_val, const int* __restrict__ top_tok,
+                                                               const float* __restrict__ beam_scores, int nb, int G,
+                                                               const float* __restrict__ penalty, int V, float* __restrict__ out_score,
+                                                               int* __restrict__ out_tok, int* __restrict__ out_beam) {
+#pragma clang fp contract(off)
+    __shared__ float ssc[BEAM_MERGE_THREADS];
+    __shared__ long long sflat[BEAM_MERGE_THREADS];
+    __shared__ int chosen[BEAM_K / 2];   // tokens taken by the groups so far: <= nb - gs when the last group reads it
+    __shared__ int rtok[BEAM_K];         // the current group's ranked tokens
+    __shared__ int nchosen;
+    const int item = blockIdx.x, tid = threadIdx.x;
+    const int gs = nb / G, K = 2 * nb, n = gs * K, top = 2 * gs;   // n <= 512 for nb <= 16
+    const float lam = *penalty;
+    if (tid == 0) nchosen = 0;
+    for (int g = 0; g < G; ++g) {
+        __syncthreads();   // the list of the groups before this one is complete; ssc / sflat / rtok are free again
+        float sc = -INFINITY;
+        long long flat = 0x7fffffffffffLL;
+        int tok = 0, b = 0;
+        if (tid < n) {
+            const int bi = tid / K;
+            b = g * gs + bi;
+            const int row = item * nb + b;
+            const float v = top_val[(size_t)row * BEAM_K + (tid - bi * K)];
+            tok = top_tok[(size_t)row * BEAM_K + (tid - bi * K)];
+            int freq = 0;
+            for (int j = 0; j < nchosen; ++j) freq += (chosen[j] == tok) ? 1 : 0;
+            const float logp = __fsub_rn(__fsub_rn(v, row_max[row]), row_logsum[row]);
+            float pen = __fmul_rn(lam, (float)freq);
+            asm volatile("" : "+v"(pen));   // the product stays a rounded value of its own: __fmul_rn is a plain multiply in this
+                                            // toolchain and hipcc contracts it into the subtract once inlined, the pragma notwithstanding
+            sc = __fadd_rn(__fsub_rn(logp, pen), beam_scores[row]);
+            flat = (long long)bi * V + tok;
+        }
+        ssc[tid] = sc;
+        sflat[tid] = flat;
+        __syncthreads();
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const float oj = ssc[j];
+            const long long fj = sflat[j];
+            if (oj > sc || (oj == sc && fj < flat)) ++rank;
+        }
+        if (tid < n && rank < top) {
+            out_score[item * K + g * top + rank] = sc;
+            out_tok[item * K + g * top + rank] = tok;
+            out_beam[item * K + g * top + rank] = b;
+            rtok[rank] = tok;   // n = gs * 2 nb >= 2 gs candidates with distinct (score, flat): every rank below top is written
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int c = nchosen;
+            for (int r = 0, picked = 0; r < top && picked < gs; ++r)
+                if (rtok[r] != EOS_ID) { chosen[c++] = rtok[r]; ++picked; }
+            nchosen = c;
+        }
+    }
+}
+
 // ---- more than 16 beams (round 6: the reference's loop has no bound, language_model.py:450-475).  The per-thread sorted lists of the
 // kernels above hold 32 candidates in registers; wider beams take K = 2 num_beams rounds of a block-wide arg-max over the elements
 // that come AFTER the previous winner in the same total order (value desc, index asc) - K scans of the row from L2 instead of one,
@@ -315,12 +386,16 @@ struct BeamHyps {
 // prompt == NULL: the BOS start of rgrg_decoder_beam_search.  With a prompt (rgrg_decoder_beam_search_prompted, decoder_prompt.hip)
 // the first iteration ranks the logits of the prompt's last position instead of running a step - the reference's first iteration
 // on nb identical rows - and ids / cur_len start at the prompt.
+// groups != NULL: diverse beam search (rgrg_decoder_group_beam_search[_prompted]; the caller has checked G and the penalty) - G
+// groups of gs = nb / G rows per item, ranked by beam_group_merge_kernel; BeamSearchScorer.process runs per item and group with
+// group_size gs on the item's shared heap and `done` flag.  groups == NULL is G = 1 on beam_merge_kernel: plain beam search.
 int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping,
                           float length_penalty, int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream,
-                          const BeamPrompt* prompt) {
+                          const BeamPrompt* prompt, const BeamGroups* groups) {
     RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && num_beams > 1 && num_beams <= (1 << 14));
     RGRG_CHECK_ARG(num_return_sequences >= 1 && num_return_sequences <= num_beams);
     const int nb = num_beams, K = 2 * nb, R = S * nb;
+    const int G = groups ? groups->G : 1, gs = nb / G;   // K = G * 2 gs candidate slots per item either way
     RGRG_CHECK_ARG(R <= d->max_seqs && max_length >= 2 && max_length <= d->max_len && out_ld >= max_length);
     hipStream_t st = d->stream;
     const bool wide = K > BEAM_K;   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
@@ -342,8 +417,14 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
             return r;
         d->wide_cap = (size_t)R * K;
     }
+    if (groups && !d->group_penalty) {
+        int r = dmalloc(d, (void**)&d->group_penalty, sizeof(float), true);
+        if (r) return r;
+    }
     RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
+    // the captured group step reads the penalty from this word: one graph per (rows, table, nb, G) serves every penalty
+    if (groups) RGRG_HIP(hipMemcpyAsync(d->group_penalty, &groups->penalty, sizeof(float), hipMemcpyHostToDevice, st));
     // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
     int rc = enqueue_prefill(d, feats, S, nb);
     if (rc) return rc;
@@ -361,7 +442,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         for (int r = 0; r < R; ++r) ids[r].assign(prompt_ids.begin() + (size_t)(r / nb) * prompt->T, prompt_ids.begin() + (size_t)(r / nb + 1) * prompt->T);
     std::vector<float> beam_scores(R, 0.f), h_score((size_t)S * K);
     std::vector<int> beam_tok(R, BOS_ID), parent(R, 0), h_tok((size_t)S * K), h_beam((size_t)S * K);
-    for (int r = 0; r < R; ++r) beam_scores[r] = (r % nb == 0) ? 0.f : -1e9f;
+    for (int r = 0; r < R; ++r) beam_scores[r] = (r % nb % gs == 0) ? 0.f : -1e9f;   // beam_scores[:, ::gs] = 0
     std::vector<BeamHyps> hyps(S);
     std::vector<char> done(S, 0);
     const double lp = (double)length_penalty;
@@ -376,8 +457,12 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
                                               d->row_max, d->row_logsum, d->top_val, d->top_tok)
             if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
 #undef BEAM_TOPK
-            hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
-                               d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
+            if (groups)
+                hipLaunchKernelGGL(beam_group_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
+                                   d->top_tok, d->beam_scores, nb, G, d->group_penalty, d->V, d->cand_score, d->cand_tok, d->cand_beam);
+            else
+                hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
+                                   d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
         } else {
             hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
                                d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
@@ -400,9 +485,10 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
             // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed; behind a left-padded
             // prompt the steps carry positions and padded slots and are captured under keys of their own (GraphEntry)
             const int parity = ((src_cur == d->src_a) ? 1 : 2) + (padded ? 4 : 0);
+            const int key3 = nb | (groups ? G << 16 : 0);   // a group step (G >= 1 in the high half) is never a plain beam step (0 there)
             hipGraphExec_t exec = nullptr;
             for (auto& g : d->graphs)
-                if (g.S == R && g.key2 == parity && g.key3 == nb) exec = g.exec;
+                if (g.S == R && g.key2 == parity && g.key3 == key3) exec = g.exec;
             if (!exec) {
                 hipGraph_t graph = nullptr;
                 RGRG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -413,7 +499,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
                 if (e != hipSuccess) { set_error("beam: hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
                 RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                 (void)hipGraphDestroy(graph);
-                d->graphs.push_back({R, exec, parity, nb});
+                d->graphs.push_back({R, exec, parity, key3});
             }
             RGRG_HIP(hipGraphLaunch(exec, st));
         }
@@ -421,28 +507,34 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         RGRG_HIP(hipMemcpyAsync(h_tok.data(), d->cand_tok, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
         RGRG_HIP(hipMemcpyAsync(h_beam.data(), d->cand_beam, (size_t)S * K * sizeof(int), hipMemcpyDeviceToHost, st));
         RGRG_HIP(hipStreamSynchronize(st));
-        // BeamSearchScorer.process
+        // BeamSearchScorer.process, per item and - in group order - per group of gs rows (plain beam search: one group of nb): the
+        // heap (capacity nb) and `done` belong to the ITEM, so `done` may flip between two groups of a step, and the later groups
+        // of that item then take PAD like a finished item (HF's behaviour, kept); items are independent, so item-major order is HF's
         for (int b = 0; b < S; ++b) {
-            if (done[b]) {
-                for (int j = 0; j < nb; ++j) { nscore[b * nb + j] = 0.f; ntok[b * nb + j] = PAD_ID; nidx[b * nb + j] = 0; }
-                continue;
-            }
-            int beam_idx = 0;
-            for (int rank = 0; rank < K; ++rank) {
-                const int tok = h_tok[(size_t)b * K + rank];
-                const float sc = h_score[(size_t)b * K + rank];
-                const int row = b * nb + h_beam[(size_t)b * K + rank];
-                if (tok == EOS_ID) {
-                    if (rank >= nb) continue;
-                    hyps[b].add(ids[row], (double)sc, nb, lp);
-                } else {
-                    nscore[b * nb + beam_idx] = sc; ntok[b * nb + beam_idx] = tok; nidx[b * nb + beam_idx] = row;
-                    ++beam_idx;
+            for (int g = 0; g < G; ++g) {
+                const int r0 = b * nb + g * gs;            // the group's first row
+                const size_t c0 = (size_t)b * K + (size_t)g * 2 * gs;   // ... and first candidate slot
+                if (done[b]) {
+                    for (int j = 0; j < gs; ++j) { nscore[r0 + j] = 0.f; ntok[r0 + j] = PAD_ID; nidx[r0 + j] = 0; }
+                    continue;
                 }
-                if (beam_idx == nb) break;
+                int beam_idx = 0;
+                for (int rank = 0; rank < 2 * gs; ++rank) {
+                    const int tok = h_tok[c0 + rank];
+                    const float sc = h_score[c0 + rank];
+                    const int row = b * nb + h_beam[c0 + rank];
+                    if (tok == EOS_ID) {
+                        if (rank >= gs) continue;
+                        hyps[b].add(ids[row], (double)sc, nb, lp);
+                    } else {
+                        nscore[r0 + beam_idx] = sc; ntok[r0 + beam_idx] = tok; nidx[r0 + beam_idx] = row;
+                        ++beam_idx;
+                    }
+                    if (beam_idx == gs) break;
+                }
+                if (beam_idx < gs) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
+                done[b] = done[b] || hyps[b].is_done((double)h_score[c0], cur_len, early_stopping != 0, nb, lp);
             }
-            if (beam_idx < nb) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
-            done[b] = done[b] || hyps[b].is_done((double)h_score[(size_t)b * K], cur_len, early_stopping != 0, nb, lp);
         }
         // input_ids = cat(input_ids[beam_idx], tokens); cache "re-order" = new ancestor table
         std::vector<std::vector<long long>> nids(R);
@@ -510,4 +602,57 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
                                         int out_ld, int* out_len, void* stream) {
     return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld,
                            out_len, stream, nullptr);
+}
+
+// the refusals the two diverse entries share, each with a message
+int rgrg::check_beam_groups(const char* who, int num_beams, int num_beam_groups, float diversity_penalty, int num_return_sequences) {
+    const int nb = num_beams, G = num_beam_groups;
+    if (nb < 2 || G < 1) { set_error("%s: num_beams %d (> 1) and num_beam_groups %d (>= 1) are required", who, nb, G); return RGRG_EINVAL; }
+    if (nb > BEAM_K / 2) {
+        set_error("%s: num_beams %d: diverse beam search ranks at most %d beams (the wide ranking kernels have no group form)", who, nb, BEAM_K / 2);
+        return RGRG_EINVAL;
+    }
+    if (G > nb) { set_error("%s: num_beam_groups %d has to be smaller or equal to num_beams %d", who, G, nb); return RGRG_EINVAL; }
+    if (nb % G != 0) { set_error("%s: num_beams %d has to be divisible by num_beam_groups %d", who, nb, G); return RGRG_EINVAL; }
+    if (G > 1 && !(diversity_penalty > 0.f && std::isfinite(diversity_penalty))) {
+        set_error("%s: diversity_penalty has to be a float > 0 with num_beam_groups %d > 1, but is %g", who, G, (double)diversity_penalty);
+        return RGRG_EINVAL;
+    }
+    if (num_return_sequences < 1 || num_return_sequences > nb) {
+        set_error("%s: num_return_sequences %d outside 1 .. num_beams %d", who, num_return_sequences, nb);
+        return RGRG_EINVAL;
+    }
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_group_beam_search(rgrg_decoder* d, const float* feats, int S, int num_beams, int num_beam_groups,
+                                              float diversity_penalty, int max_length, int early_stopping, float length_penalty,
+                                              int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream) {
+    int rc;
+    if ((rc = check_beam_groups("rgrg_decoder_group_beam_search", num_beams, num_beam_groups, diversity_penalty, num_return_sequences))) return rc;
+    const BeamGroups grp{num_beam_groups, num_beam_groups > 1 ? diversity_penalty : 0.f};
+    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld,
+                           out_len, stream, nullptr, &grp);
+}
+
+// Test hook: beam_group_merge_kernel alone on caller buffers (top_val / top_tok rows BEAM_K wide, as in the decoder)
+extern "C" int rgrg_debug_beam_group_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+                                           const float* beam_scores, int S, int nb, int G, float penalty, int V, float* out_score,
+                                           int* out_tok, int* out_beam, void* stream) {
+    RGRG_CHECK_ARG(row_max && row_logsum && top_val && top_tok && beam_scores && out_score && out_tok && out_beam);
+    RGRG_CHECK_ARG(S > 0 && V > 0 && nb >= 1 && nb <= BEAM_K / 2 && G >= 1 && G <= nb && nb % G == 0);
+    float* pen = nullptr;
+    RGRG_HIP(hipMalloc((void**)&pen, sizeof(float)));
+    hipStream_t st = as_stream(stream);
+    hipError_t e = hipMemcpyAsync(pen, &penalty, sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(beam_group_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, row_max, row_logsum, top_val, top_tok, beam_scores,
+                           nb, G, pen, V, out_score, out_tok, out_beam);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);   // the penalty word is the call's own: it must outlive the launch
+    (void)hipFree(pen);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { set_error("rgrg_debug_beam_group_merge: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return RGRG_OK;
 }

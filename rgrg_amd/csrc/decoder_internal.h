@@ -81,7 +81,8 @@ struct LayerW {
 };
 
 struct GraphEntry {
-    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (num_beams in key3),
+    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (key3 = num_beams, plus
+            // num_beam_groups << 16 for a step of diverse beam search, which ranks with another kernel),
             // 3 = sampling step, 4 = greedy step behind a left-padded prompt (decoder_prompt.hip), 5/6 = beam step reading table A/B
             // behind a left-padded prompt (num_beams in key3), 7 = sampling step behind a left-padded prompt
     hipGraphExec_t exec;
@@ -110,6 +111,7 @@ struct rgrg_decoder {
     float *wide_val = nullptr, *wide_score = nullptr;   // more than 16 beams: [rows][K] row candidates, [items][num_beams * K] scores
     int* wide_tok = nullptr;
     size_t wide_cap = 0;                                 // rows * K the wide buffers were sized for
+    float* group_penalty = nullptr;                      // diverse beam search: the device word the captured group step reads its penalty from
     // sampling (decoder_sample.hip): device-side parameter block the captured step reads, log-probs [rows][max_len]
     void* sample_prm = nullptr;
     float* sample_lp = nullptr;
@@ -270,8 +272,12 @@ int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, boo
 // a beam step behind a left-padded prompt: per-row positions, the slot mask (fp32 cache) / padded slots (16-bit cache), enqueue_step
 int padded_beam_step(rgrg_decoder* d, int R, const int* src);
 // decoder_beam.hip: rgrg_decoder_beam_search, from a prompt when one is given
+// groups (or NULL = plain beam search): num_beam_groups and the Hamming diversity penalty of rgrg_decoder_group_beam_search
+struct BeamGroups { int G; float penalty; };
 int beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping, float length_penalty,
-                    int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream, const BeamPrompt* prompt);
+                    int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream, const BeamPrompt* prompt,
+                    const BeamGroups* groups = nullptr);
+int check_beam_groups(const char* who, int num_beams, int num_beam_groups, float diversity_penalty, int num_return_sequences);
 // decoder_sample.hip: the sampling step (graph key 3) and the start of every sampling entry
 int sample_step(rgrg_decoder* d, int S, bool count);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);

@@ -335,6 +335,30 @@ extern "C" int rgrg_decoder_beam_search_prompted(rgrg_decoder* d, const float* f
                            stream, &p);
 }
 
+extern "C" int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask,
+                                                       int S, int T, int num_beams, int num_beam_groups, float diversity_penalty, int max_length,
+                                                       int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
+                                                       int out_ld, int* out_len, void* stream) {
+    RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && T >= 1);
+    int rc;
+    if ((rc = check_beam_groups("rgrg_decoder_group_beam_search_prompted", num_beams, num_beam_groups, diversity_penalty, num_return_sequences)))
+        return rc;
+    RGRG_CHECK_ARG((long long)S * num_beams <= d->max_seqs);
+    if (max_length < T + 1 || max_length > d->max_len) {
+        set_error("rgrg_decoder_group_beam_search_prompted: max_length %d with a prompt of %d tokens: %d .. %d (the cache) are possible",
+                  max_length, T, T + 1, d->max_len);
+        return RGRG_EINVAL;
+    }
+    if (rgrg_decoder_kv_format_in_use(d, S * num_beams) == KV_E4M3) {
+        set_error("rgrg_decoder_group_beam_search_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
+        return RGRG_EINVAL;
+    }
+    const BeamPrompt p{reinterpret_cast<const long long*>(input_ids), attention_mask, T};
+    const BeamGroups grp{num_beam_groups, num_beam_groups > 1 ? diversity_penalty : 0.f};
+    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
+                           stream, &p, &grp);
+}
+
 extern "C" int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
                                             int T, int max_length, float temperature, int top_k, float top_p, uint64_t seed,
                                             int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph, void* stream) {

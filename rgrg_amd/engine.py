@@ -906,6 +906,54 @@ class HipEngine:
                    "rgrg_decoder_beam_search")
         return out[:, :out_len.value].contiguous()
 
+    def _group_beam_call(self, feats: Tensor, limit: int, num_beams: int, num_return_sequences: int, bf16, kv_fp8: bool, name: str,
+                         call) -> Tensor:
+        """What the two diverse entries share: decoder, modes, output buffer; ``call(dec, feats_ptr, out_ptr, out_len_ref)`` is the
+        C call -> int64 [S * num_return_sequences, L]."""
+        S = feats.shape[0]
+        dec = self._get_decoder(S * int(num_beams), limit)
+        self._cached = None   # as in greedy_decode
+        self._set_modes(dec, bf16, kv_fp8)
+        feats = feats.to(torch.float32).contiguous()
+        out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
+        out_len = C.c_int(0)
+        _hip.check(call(dec, _hip.ptr(feats), _hip.ptr(out), C.byref(out_len)), name)
+        return out[:, :out_len.value].contiguous()
+
+    def group_beam_search(self, feats: Tensor, max_length: int, num_beams: int, num_beam_groups: int, diversity_penalty: float,
+                          early_stopping: bool = False, length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
+                          kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.group_beam_search without a prompt (rgrg_decoder_group_beam_search): feats [S,1024] ->
+        int64 [S * num_return_sequences, L].  The library refuses what diverse beam search cannot take (RgrgHipError)."""
+        _require_gpu(feats.device)
+        S, limit = feats.shape[0], int(max_length)
+        return self._group_beam_call(feats, limit, num_beams, num_return_sequences, bf16, kv_fp8, "rgrg_decoder_group_beam_search",
+                                     lambda dec, f, out, n: self.lib.rgrg_decoder_group_beam_search(
+                                         dec, f, S, int(num_beams), int(num_beam_groups), float(diversity_penalty), limit,
+                                         1 if early_stopping else 0, float(length_penalty), int(num_return_sequences), out, limit, n,
+                                         self._s()))
+
+    def group_beam_search_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: int,
+                                   num_beams: int, num_beam_groups: int, diversity_penalty: float, early_stopping: bool = False,
+                                   length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
+                                   kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.group_beam_search with a prompt (rgrg_decoder_group_beam_search_prompted): input_ids int64 [S,T] and
+        attention_mask [S,T] (or None = ones) hold ONE prompt per item -> int64 [S * num_return_sequences, L], the prompt in
+        front.  Validation as ``beam_search_prompted``."""
+        ids, am = self._check_prompt(feats, input_ids, attention_mask)
+        S, T = ids.shape
+        limit = int(max_length)
+        if limit < T + 1:
+            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens (one iteration always runs and the "
+                             f"scorer cannot hold a hypothesis longer than max_length), but is {limit}")
+        if limit > 1024:
+            raise ValueError(f"max_length {limit} exceeds the 1024 positions of the model")
+        return self._group_beam_call(feats, limit, num_beams, num_return_sequences, bf16, kv_fp8, "rgrg_decoder_group_beam_search_prompted",
+                                     lambda dec, f, out, n: self.lib.rgrg_decoder_group_beam_search_prompted(
+                                         dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), int(num_beam_groups),
+                                         float(diversity_penalty), limit, 1 if early_stopping else 0, float(length_penalty),
+                                         int(num_return_sequences), out, limit, n, self._s()))
+
     def _raise_pending_id_error(self) -> None:
         """An unreported token-id error of a decoder that has been re-created since (close())."""
         if getattr(self, "_pending_id_error", False):

@@ -113,6 +113,27 @@ def check_sample_args(temperature, top_k, top_p, num_return_sequences) -> None:
         raise ValueError(f"num_return_sequences has to be a positive integer, but is {num_return_sequences}")
 
 
+def check_group_beam_args(max_length, num_beams, num_beam_groups, diversity_penalty, num_return_sequences) -> None:
+    """Argument errors of ``group_beam_search`` (LanguageModel) / ``generate_diverse`` (ReportGenerationModel): raised before any
+    GPU work."""
+    if max_length is None:
+        raise ValueError("max_length has to be set for beam generation.")
+    if int(num_beams) != num_beams or num_beams < 2:
+        raise ValueError(f"num_beams has to be an integer > 1 for beam search, but is {num_beams}")
+    if int(num_beam_groups) != num_beam_groups or num_beam_groups < 1:
+        raise ValueError(f"num_beam_groups has to be a positive integer, but is {num_beam_groups}")
+    if num_beam_groups > num_beams:
+        raise ValueError("'num_beam_groups' has to be smaller or equal to 'num_beams'")
+    if num_beams % num_beam_groups != 0:
+        raise ValueError("'num_beams' has to be divisible by 'num_beam_groups'")
+    if num_beam_groups > 1 and (not isinstance(diversity_penalty, float) or not diversity_penalty > 0.0):
+        raise ValueError("'diversity_penalty' has to be a float strictly larger than 0 when 'num_beam_groups' > 1")
+    if num_beams > 16:
+        raise ValueError(f"diverse beam search ranks at most 16 beams, but num_beams is {num_beams}")
+    if int(num_return_sequences) != num_return_sequences or not 1 <= num_return_sequences <= num_beams:
+        raise ValueError("'num_return_sequences' has to be between 1 and 'num_beams'.")
+
+
 class LanguageModel(EngineOwner):
     _engine_prefix = "language_model."
 
@@ -373,6 +394,42 @@ class LanguageModel(EngineOwner):
         low = _hip.autocast_mode()
         return self.engine().beam_search_prompted(image_hidden_states, prompts, mask, max_length, num_beams, early_stopping,
                                                   length_penalty, bf16=low, num_return_sequences=keep, kv_fp8=self._kv_fp8())
+
+    @torch.no_grad()
+    def group_beam_search(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, num_beam_groups: int,
+                          diversity_penalty: float, *, early_stopping: bool = False, num_return_sequences: int = 1,
+                          length_penalty: float = 1.0, input_ids: Optional[torch.LongTensor] = None,
+                          attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
+        """Diverse beam search (transformers 4.19.2 ``group_beam_search`` with ``HammingDiversityLogitsProcessor``; ``generate`` keeps
+        raising for ``num_beam_groups > 1``, as the reference does): the ``num_beams`` beams of an item form ``num_beam_groups``
+        groups that are ranked in order within every step, each group's candidates lowered by ``diversity_penalty`` times the number
+        of beams of the earlier groups that took the same token in that step (arithmetic contract in
+        include/rgrg_hip.h).  Returns int64 [S * num_return_sequences, L]: the best hypotheses of the item's heap overall (best
+        first), NOT one per group.  ``input_ids`` / ``attention_mask`` [S,T] hold ONE prompt per item, unexpanded (zeros = LEFT
+        padding, the rules of ``greedy_search``); both or neither; without them the search starts from BOS.  The prompt runs once
+        per item, as in ``beam_search``.  ``num_beam_groups = 1`` applies no penalty and IS plain beam search.  ValueError:
+        ``num_beams`` not divisible by ``num_beam_groups`` or smaller than it; ``num_beam_groups > 1`` with a ``diversity_penalty``
+        that is not a float > 0 (HF's rule); ``num_beams > 16`` (the K-round "wide" ranking kernels of more than 16 beams are not
+        extended to groups); ``num_return_sequences`` outside 1 .. ``num_beams``; ``max_length`` None.  torch.autocast opts into
+        the 16-bit plans as for ``generate``."""
+        check_group_beam_args(max_length, num_beams, num_beam_groups, diversity_penalty, num_return_sequences)
+        if (input_ids is None) != (attention_mask is None):
+            raise ValueError("input_ids and attention_mask have to be given together (one prompt per item), or neither")
+        if input_ids is not None and int(max_length) < input_ids.shape[-1] + 1:
+            raise ValueError(f"max_length has to be at least {input_ids.shape[-1] + 1} for a prompt of {input_ids.shape[-1]} tokens, "
+                             f"but is {max_length}")
+        from .engine import _require_gpu
+        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
+        self.sync_trainable_if_stale()
+        low = _hip.autocast_mode()
+        if input_ids is None:
+            return self.engine().group_beam_search(image_hidden_states, int(max_length), int(num_beams), int(num_beam_groups),
+                                                   float(diversity_penalty), bool(early_stopping), float(length_penalty), bf16=low,
+                                                   num_return_sequences=int(num_return_sequences), kv_fp8=self._kv_fp8())
+        return self.engine().group_beam_search_prompted(image_hidden_states, input_ids, attention_mask, int(max_length), int(num_beams),
+                                                        int(num_beam_groups), float(diversity_penalty), bool(early_stopping),
+                                                        float(length_penalty), bf16=low, num_return_sequences=int(num_return_sequences),
+                                                        kv_fp8=self._kv_fp8())
 
     @torch.no_grad()
     def sample_from_prompt(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None,
