@@ -1213,15 +1213,16 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
     return RGRG_OK;
 }
 
-// r0: first sequence of the launch (the many-sequence step may run as two row ranges on two streams, enqueue_step); src / att16
-// are the caller's pointers for that first sequence already
+// The attention of layer l for the S sequences from r0 on of step `s` (the many-sequence step may run as several row ranges on
+// several streams, enqueue_step); att16 is the caller's pointer for sequence r0 already
 // q_only: c_attn ran with the K/V-cache epilogue (step_qkv_cache / cons_kv_cache below)
-static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsigned short* att16, int frag_out = 0, int r0 = 0,
+static int launch_attention(rgrg_decoder* d, int l, const StepSpec& s, int r0, int S, unsigned short* att16, int frag_out = 0,
                             bool q_only = false) {
     const int D = d->D;
     AttnDecodeLaunch a{};
     a.q_only = q_only;
-    a.ld_qkv = 3 * D; a.step = d->step; a.S = S; a.H = d->H; a.T = d->T; a.src = src; a.kmask = d->key_mask_cur;
+    a.ld_qkv = 3 * D; a.step = d->step; a.S = S; a.H = d->H; a.T = d->T; a.kmask = s.key_mask;
+    a.src = s.src ? s.src + (size_t)r0 * d->T : nullptr;
     a.frag_out = frag_out; a.st = d->stream; a.plane_elems = d->kv_kv_stride;
     a.fmt = kv_format(d, S);
     if (a.fmt != KV_F32) {
@@ -1234,7 +1235,7 @@ static int launch_attention(rgrg_decoder* d, int l, int S, const int* src, unsig
         a.f16 = d->f16(); a.max_wgs = cap > 0 ? cap * 256 : 0;
         a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kcr; a.vc = kcr + d->kv_kv_stride * esz;
         a.out = d->att + (size_t)r0 * D; a.out16 = att16;
-        a.first = d->kv_first_cur ? d->kv_first_cur + r0 : nullptr;
+        a.first = s.kv_first ? s.kv_first + r0 : nullptr;
     } else {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
         a.qkv = d->qkv; a.kc = kc; a.vc = kc + d->kv_kv_stride; a.out = d->att;
@@ -1313,19 +1314,19 @@ static int direct_linear(rgrg_decoder* d, const Lin& l, DirectArgs a, int mode, 
 
 // The GEMMs of layer l of the fused plan (everything but the attention); `cur` holds x_mid of the previous layer in
 // fragment-major order with its mlp_proj partial sums pending in d->part, `nxt` receives this layer's residual stream.
-static int enqueue_layer_gemms(rgrg_decoder* d, int l, int S, bool count, const int* tok_override, const float* cur, float* nxt,
+static int enqueue_layer_gemms(rgrg_decoder* d, int l, const StepSpec& s, bool count, const float* cur, float* nxt,
                                int part) {  // part: 0 = c_attn', 1 = attn_proj' .. mlp_proj
     const LayerW& w = d->layers[l];
-    const int D = d->D;
+    const int D = d->D, S = s.rows;
     int rc;
     if (part == 0) {
         DirectArgs a{};
         a.xout = nxt; a.Y = d->qkv; a.ldy = 3 * D; a.act = RGRG_ACT_NONE;
         int mode;
         if (l == 0) {
-            a.wte = d->wte; a.ids = d->ids; a.ld_ids = d->max_len; a.step = d->step; a.tok_override = tok_override;
-            a.pos_override = d->pos_override_cur;
-            mode = tok_override ? (d->pos_override_cur ? DX_EMBED_TOKPOS : DX_EMBED_TOK) : DX_EMBED;
+            a.wte = d->wte; a.ids = d->ids; a.ld_ids = d->max_len; a.step = d->step; a.tok_override = s.tok;
+            a.pos_override = s.row_pos;
+            mode = s.tok ? (s.row_pos ? DX_EMBED_TOKPOS : DX_EMBED_TOK) : DX_EMBED;
         } else {
             a.Xf = cur; a.part = d->part;
             mode = DX_COMBINE4;
@@ -1349,22 +1350,24 @@ static int enqueue_layer_gemms(rgrg_decoder* d, int l, int S, bool count, const 
 //   residual, in place] -> c_fc' [ln_2 folded, gelu] -> mlp_proj (4 partial sums)
 //   lm_head' [combine; ln_f folded; arg-max candidates] -> argmax + bookkeeping.
 // The residual stream ping-pongs between d->x and d->x2; x, att, ff and the partial sums are fragment-major.
-static int enqueue_step_fused(rgrg_decoder* d, int S, bool count, const int* tok_override, const int* src, bool beam) {
+static int enqueue_step_fused(rgrg_decoder* d, const StepSpec& s, bool count) {
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     hipStream_t st = d->stream;
+    const int S = s.rows;
+    const bool logits = s.end != STEP_ARGMAX;
     int rc;
     float* cur = d->x;
     float* nxt = d->x2;
     for (int l = 0; l < d->n_layer; ++l) {
-        if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 0))) return rc;
-        if ((rc = launch_attention(d, l, S, src, nullptr, 1))) return rc;
-        if ((rc = enqueue_layer_gemms(d, l, S, count, tok_override, cur, nxt, 1))) return rc;
+        if ((rc = enqueue_layer_gemms(d, l, s, count, cur, nxt, 0))) return rc;
+        if ((rc = launch_attention(d, l, s, 0, S, nullptr, 1))) return rc;
+        if ((rc = enqueue_layer_gemms(d, l, s, count, cur, nxt, 1))) return rc;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     DirectArgs h{};
     h.Xf = cur; h.part = d->part; h.Y = d->logits; h.ldy = d->ld_logits; h.act = RGRG_ACT_NONE;
-    if ((rc = direct_linear(d, d->lm_head, h, DX_COMBINE4, S, count, !beam))) return rc;
-    if (beam) return RGRG_OK;
+    if ((rc = direct_linear(d, d->lm_head, h, DX_COMBINE4, S, count, !logits))) return rc;
+    if (logits) return RGRG_OK;
     hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, d->lm_head.NT, d->ids,
                        d->max_len, d->finished, d->step, d->done_len, d->sync, S);
     RGRG_LAUNCH_CHECK();
@@ -1436,12 +1439,14 @@ static bool step_ln_fold(const rgrg_decoder* d, int S) {
     return kv_is_bf16(d, S) && d->xn16 && d->ln_fold && d->ln_stat && d->layers[0].c_attn.wb_ln && d->D == 1024;
 }
 // ... whose c_attn writes the new token's k / v straight into slot t + 1 of the 16-bit cache and whose attention reads q only:
-// `plain` steps (the step's own token and cache rows: greedy and sampling; not beam search, not forward(use_cache=True)) on the
-// bf16 / fp16 cache (not e4m3), c_attn on the LDS-DMA kernel - the row-split kernel of RGRG_GEMM_KP=1/3 has no such epilogue and
-// keeps the fp32 q | k | v row.  RGRG_QKV_CACHE=0: the fp32 row everywhere (A/B, tests/test_gpu_qkv_cache.py).
-static bool step_qkv_cache(const rgrg_decoder* d, int S, bool plain) {
+// plain steps (the step's own token and cache rows: greedy and sampling; not beam search, not forward(use_cache=True)) without a
+// slot mask on the bf16 / fp16 cache (not e4m3), c_attn on the LDS-DMA kernel - the row-split kernel of RGRG_GEMM_KP=1/3 has no such
+// epilogue and keeps the fp32 q | k | v row.  RGRG_QKV_CACHE=0: the fp32 row everywhere (A/B, tests/test_gpu_qkv_cache.py).
+static bool step_qkv_cache(const rgrg_decoder* d, const StepSpec& s) {
+    const int S = s.rows;
     const KvFormat f = kv_format(d, S);
-    return d->qkv_cache && plain && step_ln_fold(d, S) && (f == KV_BF16 || f == KV_F16) && d->kp_gemms != 1 && d->kp_gemms != 3 && !d->key_mask_cur;
+    const bool plain = !s.tok && !s.src;
+    return d->qkv_cache && plain && step_ln_fold(d, S) && (f == KV_BF16 || f == KV_F16) && d->kp_gemms != 1 && d->kp_gemms != 3 && !s.key_mask;
 }
 // the consumer fold of layer l's c_attn for the sequences from r0 on, with the cache planes launch_attention passes for them
 static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, int l, int r0) {
@@ -1451,12 +1456,12 @@ static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, i
     return f;
 }
 
-// The end of a step: lm_head over the ln_f rows (d->xn, or xn16 where the step's GEMMs read 16-bit activations).  Beam search and
-// sampling rank the logits themselves; greedy: per-tile arg-max candidates, arg-max and the bookkeeping.
-static int enqueue_head(rgrg_decoder* d, int S, bool count, bool beam, unsigned short* xn16) {
+// The end of a step: lm_head over the ln_f rows (d->xn, or xn16 where the step's GEMMs read 16-bit activations).  logits: d->logits
+// and nothing else (the sampler or a ranking follows); otherwise per-tile arg-max candidates, arg-max and the bookkeeping.
+static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigned short* xn16) {
     hipStream_t st = d->stream;
     int rc;
-    if (!beam && xn16 && lm_head_cand_path(d, S)) {
+    if (!logits && xn16 && lm_head_cand_path(d, S)) {
         // greedy: the 256 x 256 lm_head leaves one (maximum, column) pair per row and column tile; no logits, no candidates pass
         GemmLnFold ce{};
         ce.cand_val = d->cand_val; ce.cand_idx = d->cand_idx;
@@ -1468,7 +1473,7 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool beam, unsigned 
         return trace_mark(d, 0, 1003);
     }
     if ((rc = linear(d, d->lm_head, d->xn, nullptr, d->logits, S, d->ld_logits, RGRG_ACT_NONE, count, xn16))) return rc;
-    if (beam) return RGRG_OK;  // the caller ranks the logits (beam_row_topk / beam_merge)
+    if (logits) return RGRG_OK;
     const int cand_nt = (d->V + 31) / 32;  // ld_logits >= 32 * cand_nt, and the candidate buffers hold lm_head.NT >= cand_nt per row
     hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, S), dim3(256), 0, st, d->logits, d->ld_logits, d->V,
                        cand_nt, d->cand_val, d->cand_idx);
@@ -1500,11 +1505,11 @@ int launch_beam_first_mask(const int* first, int R, int T, float* kmask, hipStre
     return RGRG_OK;
 }
 
-// One decode step.  <= 128 token rows: the fused plan above.  More rows (many images, beam rows): tiled MFMA GEMMs
+// The decode step of more token rows than the fused plan takes (many images, beam rows): tiled MFMA GEMMs
 //   embed+ln1 | per layer: c_attn, attention, attn_proj (+ residual), ln2, c_fc+gelu, mlp_proj (+ residual),
 //   ln1 of the next layer / ln_f | lm_head, per-32-column arg-max candidates, argmax + bookkeeping
-int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, const int* src, bool beam) {
-    if (S <= decode_row_limit(d)) return enqueue_step_fused(d, S, count, tok_override, src, beam);
+static int enqueue_step_tiled(rgrg_decoder* d, const StepSpec& s, bool count) {
+    const int S = s.rows;
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     d->step_rows = S;
     const int D = d->D;
@@ -1522,7 +1527,7 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
     // the lm_head stays a launch: the slot reads cost its 3144 workgroups more than the one ln_rows per step
     const bool fold = step_ln_fold(d, S);
     // ... and c_attn's k / v columns go straight to cache slot t + 1 as 16 bit; the attention then reads q only (step_qkv_cache)
-    const bool qc = step_qkv_cache(d, S, !tok_override && !src);
+    const bool qc = step_qkv_cache(d, s);
     static const float cons_tag = 0.f;   // any non-null pointer: linear() substitutes the GEMM's own column sums
     GemmLnFold prod{}, cons{};
     prod.Yb16 = xn16; prod.stats_out = d->ln_stat;
@@ -1544,8 +1549,8 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
         const GemmLnFold* pfr = fold ? &prod_r : nullptr;
         const GemmLnFold* cfr = fold ? &cons_r : nullptr;
         hipLaunchKernelGGL(embed_ln_kernel, dim3(rows), dim3(256), 0, rs, d->wte, d->ids + (size_t)r0 * d->max_len, d->max_len, d->step,
-                           d->layers[0].ln1_g, d->layers[0].ln1_b, x, xn, D, tok_override ? tok_override + r0 : nullptr, xn16r, d->f16(),
-                           d->pos_override_cur ? d->pos_override_cur + r0 : nullptr, fold ? statr : (float*)nullptr);
+                           d->layers[0].ln1_g, d->layers[0].ln1_b, x, xn, D, s.tok ? s.tok + r0 : nullptr, xn16r, d->f16(),
+                           s.row_pos ? s.row_pos + r0 : nullptr, fold ? statr : (float*)nullptr);
         RGRG_LAUNCH_CHECK();
         int rc2;
         if ((rc2 = trace_mark(d, r0, 1000))) return rc2;
@@ -1556,7 +1561,7 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
             const GemmLnFold cons_kv = qc ? cons_kv_cache(d, cons_r, l, r0) : cons_r;
             if ((rc2 = linear(d, w.c_attn, xn, nullptr, d->qkv + 3 * o, rows, 3 * D, RGRG_ACT_NONE, count, xn16r, nullptr, qc ? &cons_kv : cfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 0))) return rc2;
-            if ((rc2 = launch_attention(d, l, rows, src ? src + (size_t)r0 * d->T : nullptr, att16r, 0, r0, qc))) return rc2;
+            if ((rc2 = launch_attention(d, l, s, r0, rows, att16r, 0, qc))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 1))) return rc2;
             if ((rc2 = linear(d, w.attn_proj, d->att + o, x, x, rows, D, RGRG_ACT_NONE, count, att16r, nullptr, pfr))) return rc2;
             if ((rc2 = trace_mark(d, r0, l * 8 + 2))) return rc2;
@@ -1574,8 +1579,20 @@ int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override, co
         }
         return RGRG_OK;
     };
-    if ((rc = run_row_ranges(d, S, step_chains(d, S, !beam && !tok_override && !src, fold), run_rows))) return rc;
-    return enqueue_head(d, S, count, beam, xn16);
+    if ((rc = run_row_ranges(d, S, step_chains(d, S, s.end == STEP_ARGMAX && !s.tok && !s.src, fold), run_rows))) return rc;
+    return enqueue_head(d, S, count, s.end != STEP_ARGMAX, xn16);
+}
+// One decode step: the fused plan up to its row limit (128 token rows; 64 under autocast), the tiled plan above
+int enqueue_step(rgrg_decoder* d, const StepSpec& s, bool count) {
+    const int rc = s.rows <= decode_row_limit(d) ? enqueue_step_fused(d, s, count) : enqueue_step_tiled(d, s, count);
+    return (rc || s.end != STEP_SAMPLE) ? rc : enqueue_sampler(d, s.rows);
+}
+
+StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad) {
+    s.row_pos = d->row_pos;
+    if (kv_format(d, s.rows) != KV_F32) s.kv_first = pad;
+    else s.key_mask = d->key_mask;
+    return s;
 }
 
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
@@ -1767,8 +1784,8 @@ extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
 
 namespace rgrg {
 // The decode loop that greedy search and sampling share.  decode_begin: d->stream waits for the caller's stream.
-// run_decode_loop: prefill, then `step` (one decode step ending in a kernel that calls record_step_token) limit - 1 times -
-// captured once per S under `graph_key` when use_graph -, the polling below, and the copies of ids [S, limit] (and of the
+// run_decode_loop: prefill, then `step` (a decode step ending in a kernel that calls record_step_token, `prepare` in front of it)
+// limit - 1 times - replayed from its graph when use_graph -, the polling below, and the copies of ids [S, limit] (and of the
 // sampler's log-probs, d->sample_lp, when out_logprobs is given) before the one synchronise; *out_len as rgrg_decoder_generate
 // documents it.
 int decode_begin(rgrg_decoder* d, void* stream) {
@@ -1777,28 +1794,33 @@ int decode_begin(rgrg_decoder* d, void* stream) {
     d->logits_valid = false;   // until the call has completed (an early error return leaves no logits to copy)
     return RGRG_OK;
 }
-int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
+int step_graph(rgrg_decoder* d, const StepSpec& s, const std::function<int()>& body, hipGraphExec_t* exec) {
+    for (auto& g : d->graphs)
+        if (g.spec == s) { *exec = g.exec; return RGRG_OK; }
+    hipGraph_t graph = nullptr;
+    RGRG_HIP(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = body();
+    hipError_t e = hipStreamEndCapture(d->stream, &graph);   // also behind a failed step: the stream must not stay in capture mode
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("%shipStreamEndCapture: %s", s.end == STEP_BEAM ? "beam: " : "", hipGetErrorString(e)); return RGRG_EHIP; }
+    RGRG_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(graph);
+    d->graphs.push_back({s, *exec});
+    return RGRG_OK;
+}
+int run_decode_loop(rgrg_decoder* d, const float* feats, const StepSpec& step, int (*prepare)(rgrg_decoder*, int S), int limit,
                     int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, const DecodePrologue* prologue) {
+    const int S = step.rows;
     int rc = enqueue_prefill(d, feats, S);
     if (rc) return rc;
     if (prologue && (rc = prologue->fn(d, S, prologue->arg))) return rc;
 
+    auto enqueue = [&](bool count) -> int {
+        const int r = prepare ? prepare(d, S) : RGRG_OK;
+        return r ? r : enqueue_step(d, step, count);
+    };
     hipGraphExec_t exec = nullptr;
-    if (use_graph) {
-        for (auto& g : d->graphs)
-            if (g.S == S && g.key2 == graph_key) exec = g.exec;
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            RGRG_HIP(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
-            rc = step(d, S, true);
-            hipError_t e = hipStreamEndCapture(d->stream, &graph);
-            if (rc) return rc;
-            if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
-            RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            d->graphs.push_back({S, exec, graph_key, 0});
-        }
-    }
+    if (use_graph && (rc = step_graph(d, step, [&] { return enqueue(true); }, &exec))) return rc;
     const int steps = limit - 1 - (prologue ? prologue->steps_done : 0);
     int done = 0;
     // "every row has emitted EOS" is polled WITHOUT draining the pipeline: every 16 steps the device-side length word is
@@ -1812,7 +1834,7 @@ int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int g
         if (exec) {
             RGRG_HIP(hipGraphLaunch(exec, d->stream));
         } else {
-            rc = step(d, S, t == 0);
+            rc = enqueue(t == 0);
             if (rc) return rc;
         }
         if ((t & 15) == 15 && t + 1 < steps) {
@@ -1841,8 +1863,6 @@ int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int g
 }
 }  // namespace rgrg
 
-static int greedy_step(rgrg_decoder* d, int S, bool count) { return enqueue_step(d, S, count); }
-
 extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_length, int64_t* out_ids,
                                      int out_ld, int* out_len, int use_graph, void* stream) {
     RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && S <= d->max_seqs);
@@ -1850,7 +1870,8 @@ extern "C" int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S,
     RGRG_CHECK_ARG(limit >= 2 && limit <= d->max_len && out_ld >= limit);
     int rc = decode_begin(d, stream);
     if (rc) return rc;
-    if ((rc = run_decode_loop(d, feats, S, limit, 0, greedy_step, use_graph, out_ids, out_ld, nullptr, out_len))) return rc;
+    const StepSpec step{S};
+    if ((rc = run_decode_loop(d, feats, step, nullptr, limit, use_graph, out_ids, out_ld, nullptr, out_len))) return rc;
     d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
     return RGRG_OK;
 }
@@ -1916,17 +1937,16 @@ extern "C" int rgrg_decoder_forward_cached(rgrg_decoder* d, const float* feats, 
         hipLaunchKernelGGL(key_mask_kernel, dim3((S * d->T + 255) / 256), dim3(256), 0, st, attention_mask, past_len + T, S, d->T, d->key_mask);
         RGRG_LAUNCH_CHECK();
     }
+    StepSpec step;   // ... lm_head: logits, nothing else
+    step.rows = S; step.tok = d->beam_tok; step.end = STEP_LOGITS;
+    step.row_pos = position_ids ? d->row_pos : nullptr;   // embedding rows wte[position_ids[s][j]]; the cache slot stays past_len + j + 1
+    step.key_mask = attention_mask ? d->key_mask : nullptr;
     for (int j = 0; j < T; ++j) {
         hipLaunchKernelGGL(forward_cached_tokens_kernel, dim3((S + 255) / 256), dim3(256), 0, st,
                            reinterpret_cast<const long long*>(input_ids), reinterpret_cast<const long long*>(position_ids), T, j, S, d->V,
                            d->beam_tok, d->row_pos, d->step, past_len + j);
         RGRG_LAUNCH_CHECK();
-        d->pos_override_cur = position_ids ? d->row_pos : nullptr;   // embedding rows wte[position_ids[s][j]]; the cache slot stays past_len + j + 1
-        d->key_mask_cur = attention_mask ? d->key_mask : nullptr;
-        rc = enqueue_step(d, S, false, d->beam_tok, nullptr, true);   // ... lm_head: logits, nothing else
-        d->pos_override_cur = nullptr;
-        d->key_mask_cur = nullptr;
-        if (rc) return rc;
+        if ((rc = enqueue_step(d, step, false))) return rc;
         RGRG_HIP(hipMemcpy2DAsync(logits_out + (size_t)j * d->V, (size_t)T * d->V * sizeof(float), d->logits,
                                   (size_t)d->ld_logits * sizeof(float), (size_t)d->V * sizeof(float), S, hipMemcpyDeviceToDevice, st));
     }
@@ -2348,9 +2368,10 @@ extern "C" int rgrg_decoder_attention_only(rgrg_decoder* d, int S, int nkeys, in
     hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, nkeys - 2);
     int rc = RGRG_OK;
     unsigned short* att16 = (kv_is_bf16(d, S) && d->xn16) ? d->att16 : nullptr;
-    const bool qc = step_qkv_cache(d, S, true);   // the variant the greedy step launches
+    const StepSpec step{S};   // the variant the greedy step launches
+    const bool qc = step_qkv_cache(d, step);
     for (int it = 0; it < iters && !rc; ++it)
-        for (int l = 0; l < d->n_layer && !rc; ++l) rc = launch_attention(d, l, S, nullptr, att16, 0, 0, qc);
+        for (int l = 0; l < d->n_layer && !rc; ++l) rc = launch_attention(d, l, step, 0, S, att16, 0, qc);
     hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, 0);
     d->stream = keep;
     return rc;
@@ -2367,10 +2388,11 @@ extern "C" int rgrg_decoder_trace_step(rgrg_decoder* d, int S, int nkeys, int it
     hipEvent_t base;
     RGRG_HIP(hipEventCreate(&base));
     int rc = RGRG_OK;
+    const StepSpec step{S};
     for (int it = 0; it <= iters && !rc; ++it) {
         hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, d->stream, d->step, nkeys - 2);
         if (it == iters) { d->trace = &marks; RGRG_HIP(hipEventRecord(base, d->stream)); }
-        rc = enqueue_step(d, S, false);
+        rc = enqueue_step(d, step, false);
     }
     d->trace = nullptr;
     (void)hipStreamSynchronize(d->stream);
@@ -2412,7 +2434,8 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     unsigned short* ff16 = xn16 ? d->ff16 : nullptr;
     // the folded-LayerNorm variants the step launches in the 16-bit mode
     const bool fold = step_ln_fold(d, S);
-    const bool qc = step_qkv_cache(d, S, true);   // c_attn with the K/V-cache epilogue, q-only attention: as the greedy step
+    const StepSpec step{S};   // c_attn with the K/V-cache epilogue, q-only attention: as the greedy step
+    const bool qc = step_qkv_cache(d, step);
     static const float cons_tag = 0.f;
     GemmLnFold prod{}, cons{};
     prod.Yb16 = xn16; prod.stats_out = d->ln_stat;
@@ -2445,8 +2468,8 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
             for (int l = 0; l < d->n_layer && !rc2; ++l) {
                 const LayerW& w = d->layers[l];
                 if (fused) {
-                    if ((rc2 = enqueue_layer_gemms(d, l ? l : 1, S, c, nullptr, d->x, d->x2, 0))) break;
-                    if ((rc2 = enqueue_layer_gemms(d, l, S, c, nullptr, d->x, d->x2, 1))) break;
+                    if ((rc2 = enqueue_layer_gemms(d, l ? l : 1, step, c, d->x, d->x2, 0))) break;
+                    if ((rc2 = enqueue_layer_gemms(d, l, step, c, d->x, d->x2, 1))) break;
                     continue;
                 }
                 const GemmLnFold cons_kv = qc ? cons_kv_cache(d, cons_r, l, r0) : cons_r;
@@ -2481,7 +2504,7 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
             rc = run_row_ranges(d, S, fused ? 1 : step_chains(d, S, true, fold), [&](int r0, int rows) -> int {
                 int rc2 = RGRG_OK;
                 for (int l = 0; l < d->n_layer && !rc2; ++l)
-                    rc2 = launch_attention(d, l, rows, nullptr, att16 ? att16 + (size_t)r0 * D : nullptr, fused ? 1 : 0, r0, qc);
+                    rc2 = launch_attention(d, l, step, r0, rows, att16 ? att16 + (size_t)r0 * D : nullptr, fused ? 1 : 0, qc);
                 return rc2;
             });
         }

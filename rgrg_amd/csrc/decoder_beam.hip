@@ -1,6 +1,7 @@
 // Beam search of the RGRG decoder (LanguageModel.generate with num_beams > 1 -> beam_search of ttanida/rgrg):
 // the ranking / merge / ancestor-table kernels and the host-side restatement of transformers' BeamSearchScorer.
-// A beam step is the decode step of decoder.hip (enqueue_step) with the beam tokens and the ancestor table as inputs.
+// A beam step is the decode step of decoder.hip (enqueue_step) whose StepSpec names the beam tokens, the ancestor table and
+// STEP_BEAM; the ranking behind it is captured into the step's graph (step_graph).
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -423,7 +424,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     }
     RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
-    // the captured group step reads the penalty from this word: one graph per (rows, table, nb, G) serves every penalty
+    // the captured group step reads the penalty from this word: the graph of a spec serves every penalty
     if (groups) RGRG_HIP(hipMemcpyAsync(d->group_penalty, &groups->penalty, sizeof(float), hipMemcpyHostToDevice, st));
     // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
     int rc = enqueue_prefill(d, feats, S, nb);
@@ -482,25 +483,18 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
             enqueue_ranking();
             RGRG_LAUNCH_CHECK();
         } else {
-            // the step body (embed .. lm_head .. ranking) is captured once per (rows, table parity) and replayed; behind a left-padded
-            // prompt the steps carry positions and padded slots and are captured under keys of their own (GraphEntry)
-            const int parity = ((src_cur == d->src_a) ? 1 : 2) + (padded ? 4 : 0);
-            const int key3 = nb | (groups ? G << 16 : 0);   // a group step (G >= 1 in the high half) is never a plain beam step (0 there)
+            // the step (embed .. lm_head .. ranking) is captured once per spec - the ancestor table it reads is part of it - and
+            // replayed; behind a left-padded prompt it carries per-row positions and the padded slots of every row
+            StepSpec step;
+            step.rows = R; step.tok = d->beam_tok; step.src = src_cur; step.end = STEP_BEAM; step.nb = nb; step.G = groups ? G : 0;
+            if (padded) step = padded_step_spec(d, step, d->beam_pad);
             hipGraphExec_t exec = nullptr;
-            for (auto& g : d->graphs)
-                if (g.S == R && g.key2 == parity && g.key3 == key3) exec = g.exec;
-            if (!exec) {
-                hipGraph_t graph = nullptr;
-                RGRG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = padded ? padded_beam_step(d, R, src_cur) : enqueue_step(d, R, false, d->beam_tok, src_cur, true);
-                if (!rc) enqueue_ranking();
-                hipError_t e = hipStreamEndCapture(st, &graph);
-                if (rc) return rc;
-                if (e != hipSuccess) { set_error("beam: hipStreamEndCapture: %s", hipGetErrorString(e)); return RGRG_EHIP; }
-                RGRG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(graph);
-                d->graphs.push_back({R, exec, parity, key3});
-            }
+            rc = step_graph(d, step, [&]() -> int {
+                int r = padded ? enqueue_beam_row_pos(d, R) : RGRG_OK;
+                if (!r && !(r = enqueue_step(d, step, false))) enqueue_ranking();
+                return r;
+            }, &exec);
+            if (rc) return rc;
             RGRG_HIP(hipGraphLaunch(exec, st));
         }
         RGRG_HIP(hipMemcpyAsync(h_score.data(), d->cand_score, (size_t)S * K * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -2,6 +2,7 @@
 // decoder_lm.hip: the teacher-forced and training passes) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
+#include <functional>
 #include <vector>
 
 #include "internal.h"
@@ -80,13 +81,32 @@ struct LayerW {
     Lin c_attn, attn_proj, c_fc, mlp_proj;
 };
 
+// Everything that shapes the launches of one decode step (enqueue_step).  The pointers are buffers of the decoder; a captured step
+// bakes them in, so two steps may share a graph exactly when their specs are equal (step_graph).
+enum StepEnd {
+    STEP_ARGMAX,   // arg-max and the bookkeeping of record_step_token
+    STEP_LOGITS,   // d->logits, nothing else (forward(use_cache=True))
+    STEP_SAMPLE,   // d->logits, then the sampler and its bookkeeping (enqueue_sampler)
+    STEP_BEAM      // d->logits, then the ranking of nb beams per item in G groups, which the caller enqueues behind the step (G = 0: plain)
+};
+struct StepSpec {
+    int rows = 0;                      // sequences, or beam rows
+    const int* tok = nullptr;          // [rows] the tokens to embed; NULL: the id buffer at *d->step
+    const int* src = nullptr;          // [rows][T] ancestor table: the cache row that holds each slot of a beam row; NULL: the row itself
+    const int* row_pos = nullptr;      // [rows] embedding positions; NULL: *d->step
+    const int* kv_first = nullptr;     // [rows] 16-bit cache: the attention skips slots 1 .. kv_first[r] (padding in front of a prompt)
+    const float* key_mask = nullptr;   // [rows][T] fp32 cache: added to the scores of the slots
+    StepEnd end = STEP_ARGMAX;
+    int nb = 0, G = 0;                 // STEP_BEAM
+    bool operator==(const StepSpec& o) const {
+        return rows == o.rows && tok == o.tok && src == o.src && row_pos == o.row_pos && kv_first == o.kv_first && key_mask == o.key_mask &&
+               end == o.end && nb == o.nb && G == o.G;
+    }
+};
+
 struct GraphEntry {
-    int S;  // sequences (greedy) or beam rows; key2 = 0 greedy, 1/2 = beam step reading ancestor table A/B (key3 = num_beams, plus
-            // num_beam_groups << 16 for a step of diverse beam search, which ranks with another kernel),
-            // 3 = sampling step, 4 = greedy step behind a left-padded prompt (decoder_prompt.hip), 5/6 = beam step reading table A/B
-            // behind a left-padded prompt (num_beams in key3), 7 = sampling step behind a left-padded prompt
+    StepSpec spec;   // the step the graph was captured for
     hipGraphExec_t exec;
-    int key2 = 0, key3 = 0;
 };
 
 }  // namespace rgrg
@@ -190,8 +210,7 @@ struct rgrg_decoder {
     int step_rows = 0;           // token rows of the many-sequence step being enqueued (all row ranges together)
     float* ln_stat = nullptr;   // [rows][16][2]: per-row (sum, sum of squares) slots (one per 64 columns) of the residual stream (folded LayerNorm)
     bool ln_fold = true;        // 16-bit path: LayerNorms folded into the GEMMs around them; RGRG_LN_FOLD=0: ln_rows launches (A/B)
-    float* key_mask = nullptr;             // [rows][T] additive padding mask of the cache slots (forward(use_cache=True) with padding)
-    const float* key_mask_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached when a mask was given
+    float* key_mask = nullptr;             // [rows][T] additive padding mask of the cache slots (forward(use_cache=True) with padding, padded prompts)
     // rgrg_decoder_trace_step: one hipEvent after every launch of an eagerly enqueued step, on the stream it was launched on
     struct TraceMark { hipEvent_t ev; int r0; int tag; };
     std::vector<TraceMark>* trace = nullptr;
@@ -203,14 +222,11 @@ struct rgrg_decoder {
                                 // 2 (default) the producers only (attn_proj / mlp_proj, N = 1024), 3 the consumers only (c_attn / c_fc, 128 x 128 row-split kernel).
                                 // Measured per mode: profiles/r06_step_trace_v3.log
     int gemm_launches_per_step = 0;
-    const int* pos_override_cur = nullptr;   // set around the steps of rgrg_decoder_forward_cached: per-row embedding positions
-    int* row_pos = nullptr;                  // [rows] buffer behind it
-    // rgrg_decoder_generate_prompted with a left-padded prompt (decoder_prompt.hip): padded prompt slots of every row, the
-    // prompt's position ids, and - set around the steps on the 16-bit cache, whose kernel skips cache slots 1 .. prompt_pad[s]
-    // instead of adding a mask - the pointer launch_attention hands to attn_decode_kv16_wave_kernel<.., HAS_FIRST>
+    int* row_pos = nullptr;                  // [rows] per-row embedding positions (StepSpec::row_pos of forward(use_cache=True) and padded prompts)
+    // a left-padded prompt (decoder_prompt.hip): padded prompt slots of every row - on the 16-bit cache also StepSpec::kv_first of the
+    // steps behind it, whose kernel skips cache slots 1 .. prompt_pad[s] instead of adding a mask - and the prompt's position ids
     int* prompt_pad = nullptr;               // [rows]
     long long* prompt_pos = nullptr;         // [rows][max_len]
-    const int* kv_first_cur = nullptr;
     int* beam_pad = nullptr;                 // [rows] rgrg_decoder_beam_search_prompted: prompt_pad of every beam row's item
     // > 0: the last greedy generate ran the lm_head with the arg-max epilogue for this many rows - d->logits was not written;
     // rgrg_decoder_copy_last_logits recomputes it from the retained ln_f output (xn16) before copying
@@ -238,8 +254,13 @@ int linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float*
            bool count, const unsigned short* X16 = nullptr, unsigned short* Y16 = nullptr, const GemmLnFold* ln = nullptr);
 int launch_ln_rows(const float* x, const float* g, const float* b, float* xn, int D, unsigned short* xn16, int f16, int rows,
                    hipStream_t st);   // ln_rows_kernel, one wave per row
-int enqueue_step(rgrg_decoder* d, int S, bool count, const int* tok_override = nullptr, const int* src = nullptr,
-                 bool beam = false);
+int enqueue_step(rgrg_decoder* d, const StepSpec& s, bool count);
+// the graph of step `s`: captured on d->stream the first time the spec is seen - body() enqueues the step and whatever belongs to
+// it (rows prepared in front, a ranking behind) -, found by equality afterwards
+int step_graph(rgrg_decoder* d, const StepSpec& s, const std::function<int()>& body, hipGraphExec_t* exec);
+// the step behind a left-padded prompt whose padded slots per row are in `pad`: positions from d->row_pos (the caller's kernel fills
+// them in front of every step), the padded slots out of the attention through the slot mask (fp32 cache) or `pad` itself (16 bit)
+StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad);
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1);
 int decode_begin(rgrg_decoder* d, void* stream);
 // attn_kv8.hip: attn_decode_kv8_wave_kernel on `workgroups` workgroups of 4 waves (grid and argument rules: launch_attn_decode)
@@ -248,7 +269,8 @@ int launch_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kc, uint8_t* v
 // prologue: work enqueued between the prefill and the first step that already produced the tokens of steps 0 .. steps_done - 1
 // (a prompt pass, decoder_prompt.hip); the loop then runs the remaining limit - 1 - steps_done steps
 struct DecodePrologue { int (*fn)(rgrg_decoder*, int S, const void* arg); const void* arg; int steps_done; };
-int run_decode_loop(rgrg_decoder* d, const float* feats, int S, int limit, int graph_key, int (*step)(rgrg_decoder*, int, bool),
+// step: STEP_ARGMAX or STEP_SAMPLE; prepare (or NULL): enqueued in front of every step (the rows of a padded prompt)
+int run_decode_loop(rgrg_decoder* d, const float* feats, const StepSpec& step, int (*prepare)(rgrg_decoder*, int S), int limit,
                     int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len,
                     const DecodePrologue* prologue = nullptr);
 bool lm_head_cand_path(const rgrg_decoder* d, int S);   // greedy many-sequence 16-bit step: the lm_head leaves arg-max candidates, no logits
@@ -269,8 +291,8 @@ int launch_beam_first_mask(const int* first, int R, int T, float* kmask, hipStre
 // and the ln_f row of every item's last prompt position in the lm_head input of its nb rows.  -> *padded, host_ids [S][T].
 struct BeamPrompt { const long long* ids; const float* am; int T; };
 int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, bool* padded, std::vector<long long>* host_ids);
-// a beam step behind a left-padded prompt: per-row positions, the slot mask (fp32 cache) / padded slots (16-bit cache), enqueue_step
-int padded_beam_step(rgrg_decoder* d, int R, const int* src);
+// in front of every beam step behind a left-padded prompt: the rows' embedding positions (beam_row_pos_kernel)
+int enqueue_beam_row_pos(rgrg_decoder* d, int R);
 // decoder_beam.hip: rgrg_decoder_beam_search, from a prompt when one is given
 // groups (or NULL = plain beam search): num_beam_groups and the Hamming diversity penalty of rgrg_decoder_group_beam_search
 struct BeamGroups { int G; float penalty; };
@@ -278,8 +300,8 @@ int beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, i
                     int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream, const BeamPrompt* prompt,
                     const BeamGroups* groups = nullptr);
 int check_beam_groups(const char* who, int num_beams, int num_beam_groups, float diversity_penalty, int num_return_sequences);
-// decoder_sample.hip: the sampling step (graph key 3) and the start of every sampling entry
-int sample_step(rgrg_decoder* d, int S, bool count);
+// decoder_sample.hip: the sampler behind the logits of S rows (the end of a STEP_SAMPLE step) and the start of every sampling entry
+int enqueue_sampler(rgrg_decoder* d, int S);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
 int tf_reserve(rgrg_decoder* d, size_t rows);
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,

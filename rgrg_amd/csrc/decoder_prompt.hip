@@ -139,7 +139,7 @@ struct PromptCall {
     const float* am;     // NULL unless the prompt is padded
     int S, T;
     int row_mul = 1;     // beam search: num_beams - sequence s owns cache row s * row_mul, the cache format is that of S * row_mul rows
-    bool sample = false; // the token behind the prompt is drawn (launch_sample_step), not the arg-max
+    bool sample = false; // the token behind the prompt is drawn (enqueue_sampler), not the arg-max
 };
 
 int store_prompt_kv(rgrg_decoder* d, int l, const float* qkv, const void* arg) {
@@ -158,51 +158,43 @@ int store_prompt_kv(rgrg_decoder* d, int l, const float* qkv, const void* arg) {
     return RGRG_OK;
 }
 
+// The prompt pass of every prompted entry, between the image slot and the head: ids, step counter and position ids (and, with
+// kmask, the additive mask of the S rows' cache slots), the teacher-forced pass over the S x T prompt rows with keys / values into
+// slots 1 .. T of cache row s * row_mul, and the ln_f row of every sequence's last position in the lm_head input of its row_mul rows
+int enqueue_prompt_pass(rgrg_decoder* d, const PromptCall& c, float* kmask) {
+    const int S = c.S, T = c.T, R = S * c.row_mul, fmt = rgrg_decoder_kv_format_in_use(d, R);
+    hipStream_t st = d->stream;
+    int rc;
+    const int n = std::max(S * T, kmask ? S * d->T : 0);
+    hipLaunchKernelGGL(prompt_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c.ids, S, T, d->V, d->ids, d->max_len, d->step,
+                       c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, kmask, d->T);
+    RGRG_LAUNCH_CHECK();
+    if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, &c))) return rc;
+    u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
+    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), c.row_mul);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
 // the prologue of run_decode_loop: everything between the image slot and step T
 int enqueue_prompt(rgrg_decoder* d, int S, const void* arg) {
     const PromptCall& c = *static_cast<const PromptCall*>(arg);
-    const int T = c.T, fmt = rgrg_decoder_kv_format_in_use(d, S);
-    hipStream_t st = d->stream;
     int rc;
-    const bool mask32 = c.am && fmt == KV_F32;   // the fp32 attention kernel takes the additive mask, the 16-bit one pad[] itself
-    const int n = std::max(S * T, mask32 ? S * d->T : 0);
-    hipLaunchKernelGGL(prompt_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c.ids, S, T, d->V, d->ids, d->max_len, d->step,
-                       c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, mask32 ? d->key_mask : (float*)nullptr, d->T);
-    RGRG_LAUNCH_CHECK();
-    if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, arg))) return rc;
-    u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
-    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(S), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), 1);
-    RGRG_LAUNCH_CHECK();
+    // the fp32 attention kernel takes the additive mask, the 16-bit one pad[] itself
+    const bool mask32 = c.am && rgrg_decoder_kv_format_in_use(d, S) == KV_F32;
+    if ((rc = enqueue_prompt_pass(d, c, mask32 ? d->key_mask : nullptr))) return rc;
     if (!c.sample) return enqueue_head_argmax(d, S);
     // the device step word is T - 1: the Philox counter of row r for the token in column T is (r, T - 1), as a step would have it
     if ((rc = enqueue_head_logits(d, S))) return rc;
-    return launch_sample_step(d->logits, d->ld_logits, S, d->V, d->sample_prm, d->ids, d->max_len, d->finished, d->step, d->done_len,
-                              d->sync, d->sample_lp, d->max_len, st);
+    return enqueue_sampler(d, S);
 }
 
-int greedy_step(rgrg_decoder* d, int S, bool count) { return enqueue_step(d, S, count); }
-
-// beam: the step leaves logits (sampling), the caller ranks them
-int padded_step_any(rgrg_decoder* d, int S, bool count, bool beam) {
+// in front of every greedy / sampling step behind a padded prompt
+int enqueue_prompt_step_rows(rgrg_decoder* d, int S) {
     hipLaunchKernelGGL(prompt_step_rows_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, d->ids, d->max_len, d->step, d->prompt_pad,
                        d->beam_tok, d->row_pos, S);
     RGRG_LAUNCH_CHECK();
-    const bool kv16 = rgrg_decoder_kv_format_in_use(d, S) != KV_F32;
-    d->pos_override_cur = d->row_pos;
-    if (kv16) d->kv_first_cur = d->prompt_pad;
-    else d->key_mask_cur = d->key_mask;
-    const int rc = enqueue_step(d, S, count, S <= rgrg_decoder_row_limit(d) ? d->beam_tok : nullptr, nullptr, beam);
-    d->pos_override_cur = nullptr;
-    d->kv_first_cur = nullptr;
-    d->key_mask_cur = nullptr;
-    return rc;
-}
-int padded_step(rgrg_decoder* d, int S, bool count) { return padded_step_any(d, S, count, false); }
-int padded_sample_step(rgrg_decoder* d, int S, bool count) {
-    const int rc = padded_step_any(d, S, count, true);
-    if (rc) return rc;
-    return launch_sample_step(d->logits, d->ld_logits, S, d->V, d->sample_prm, d->ids, d->max_len, d->finished, d->step, d->done_len,
-                              d->sync, d->sample_lp, d->max_len, d->stream);
+    return RGRG_OK;
 }
 
 // The mask scan of every prompted entry on d->stream, with ONE read-back: a mask the kernels cannot honour is refused before any
@@ -238,10 +230,59 @@ int prompt_mask_check(rgrg_decoder* d, const char* who, const float* attention_m
     return RGRG_OK;
 }
 
+// What every prompted entry refuses before any work, as `who`; rows: the token rows of its steps.  -> *limit, the length the call
+// decodes to.  Greedy search and sampling always produce one token: max_length <= 0 means the cache, a shorter one grows to T + 1.
+// Beam search (:541, :597-605): the first iteration always runs, and finalize cannot hold a hypothesis longer than max_length.
+int check_prompted(rgrg_decoder* d, const char* who, int rows, int T, int max_length, bool beam, int out_ld, int* limit_out) {
+    int limit = max_length;
+    if (beam) {
+        if (max_length < T + 1 || max_length > d->max_len) {
+            set_error("%s: max_length %d with a prompt of %d tokens: %d .. %d (the cache) are possible", who, max_length, T, T + 1, d->max_len);
+            return RGRG_EINVAL;
+        }
+    } else {
+        if (T + 1 > d->max_len) {
+            set_error("%s: a prompt of %d tokens and one generated token need %d token slots, the cache has %d", who, T, T + 1, d->max_len);
+            return RGRG_EINVAL;
+        }
+        limit = std::max(max_length > 0 ? max_length : d->max_len, T + 1);   // greedy_search (:622, :649): cur_len starts at T
+        RGRG_CHECK_ARG(limit <= d->max_len && out_ld >= limit);
+    }
+    *limit_out = limit;
+    if (rgrg_decoder_kv_format_in_use(d, rows) == KV_E4M3) {
+        set_error("%s: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first", who);
+        return RGRG_EINVAL;
+    }
+    return RGRG_OK;
+}
+
+// rgrg_decoder_generate_prompted / rgrg_decoder_sample_prompted behind decode_begin / sample_begin: mask scan, prompt pass, loop
+int prompted_decode_loop(rgrg_decoder* d, const char* who, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
+                         int T, int limit, StepEnd end, int use_graph, int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len) {
+    int rc;
+    bool padded = false;
+    if ((rc = prompt_mask_check(d, who, attention_mask, S, T, &padded))) return rc;
+    if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
+    PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
+    call.sample = end == STEP_SAMPLE;
+    const DecodePrologue pro{enqueue_prompt, &call, T};
+    // a mask of ones leaves the steps of the entry without a prompt (and their captured graph); behind a padded prompt the step has
+    // per-row positions and padded slots - and, on the fused plan, which embeds token and position per row together, its tokens
+    // from prompt_step_rows_kernel
+    StepSpec step;
+    step.rows = S; step.end = end;
+    if (padded) {
+        step = padded_step_spec(d, step, d->prompt_pad);
+        if (S <= rgrg_decoder_row_limit(d)) step.tok = d->beam_tok;
+    }
+    return run_decode_loop(d, feats, step, padded ? enqueue_prompt_step_rows : nullptr, limit, use_graph, out_ids, out_ld, out_logprobs,
+                           out_len, &pro);
+}
+
 }  // namespace
 
 int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, bool* padded, std::vector<long long>* host_ids) {
-    const int T = p.T, R = S * nb, fmt = rgrg_decoder_kv_format_in_use(d, R);
+    const int T = p.T, R = S * nb;
     hipStream_t st = d->stream;
     int rc;
     host_ids->resize((size_t)S * T);
@@ -252,33 +293,19 @@ int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, boo
     if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
     PromptCall c{p.ids, *padded ? p.am : nullptr, S, T};
     c.row_mul = nb;
-    // (the id buffer rows written here are not read: beam search keeps its histories on the host)
-    hipLaunchKernelGGL(prompt_setup_kernel, dim3((S * T + 255) / 256), dim3(256), 0, st, c.ids, S, T, d->V, d->ids, d->max_len, d->step,
-                       c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, (float*)nullptr, d->T);
-    RGRG_LAUNCH_CHECK();
-    if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, &c))) return rc;
+    // (the id buffer rows the pass writes are not read: beam search keeps its histories on the host; the slot mask is per beam row)
+    if ((rc = enqueue_prompt_pass(d, c, nullptr))) return rc;
     hipLaunchKernelGGL(beam_prompt_init_kernel, dim3((R * (T + 1) + 255) / 256), dim3(256), 0, st, d->src_a, d->src_b, d->T, nb, R, T,
                        c.am ? d->prompt_pad : (const int*)nullptr, d->beam_pad);
     RGRG_LAUNCH_CHECK();
-    if (*padded && fmt == KV_F32 && (rc = launch_beam_first_mask(d->beam_pad, R, d->T, d->key_mask, st))) return rc;
-    u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
-    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), nb);
-    RGRG_LAUNCH_CHECK();
+    if (*padded && rgrg_decoder_kv_format_in_use(d, R) == KV_F32) return launch_beam_first_mask(d->beam_pad, R, d->T, d->key_mask, st);
     return RGRG_OK;
 }
 
-int padded_beam_step(rgrg_decoder* d, int R, const int* src) {
+int enqueue_beam_row_pos(rgrg_decoder* d, int R) {
     hipLaunchKernelGGL(beam_row_pos_kernel, dim3((R + 255) / 256), dim3(256), 0, d->stream, d->step, d->beam_pad, d->row_pos, R);
     RGRG_LAUNCH_CHECK();
-    const bool kv16 = rgrg_decoder_kv_format_in_use(d, R) != KV_F32;
-    d->pos_override_cur = d->row_pos;
-    if (kv16) d->kv_first_cur = d->beam_pad;
-    else d->key_mask_cur = d->key_mask;
-    const int rc = enqueue_step(d, R, false, d->beam_tok, src, true);
-    d->pos_override_cur = nullptr;
-    d->kv_first_cur = nullptr;
-    d->key_mask_cur = nullptr;
-    return rc;
+    return RGRG_OK;
 }
 
 }  // namespace rgrg
@@ -287,29 +314,11 @@ extern "C" int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feat
                                               int S, int T, int max_length, int64_t* out_ids, int out_ld, int* out_len, int use_graph,
                                               void* stream) {
     RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && S <= d->max_seqs && T >= 1);
-    if (T + 1 > d->max_len) {
-        set_error("rgrg_decoder_generate_prompted: a prompt of %d tokens and one generated token need %d token slots, the cache has %d",
-                  T, T + 1, d->max_len);
-        return RGRG_EINVAL;
-    }
-    // greedy_search (:622, :649): cur_len starts at T, one token is always produced, the loop ends at cur_len >= max_length
-    int limit = (max_length > 0) ? max_length : d->max_len;
-    if (limit < T + 1) limit = T + 1;
-    RGRG_CHECK_ARG(limit <= d->max_len && out_ld >= limit);
-    if (rgrg_decoder_kv_format_in_use(d, S) == KV_E4M3) {
-        set_error("rgrg_decoder_generate_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
-        return RGRG_EINVAL;
-    }
-    int rc;
+    int rc, limit;
+    if ((rc = check_prompted(d, "rgrg_decoder_generate_prompted", S, T, max_length, false, out_ld, &limit))) return rc;
     if ((rc = decode_begin(d, stream))) return rc;
-    bool padded = false;
-    if ((rc = prompt_mask_check(d, "rgrg_decoder_generate_prompted", attention_mask, S, T, &padded))) return rc;
-    if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
-    PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
-    const DecodePrologue pro{enqueue_prompt, &call, T};
-    // a mask of ones leaves the steps of rgrg_decoder_generate (and their captured graph); a padded prompt has its own (key 4)
-    if ((rc = run_decode_loop(d, feats, S, limit, padded ? 4 : 0, padded ? padded_step : greedy_step, use_graph, out_ids, out_ld, nullptr,
-                              out_len, &pro)))
+    if ((rc = prompted_decode_loop(d, "rgrg_decoder_generate_prompted", feats, input_ids, attention_mask, S, T, limit, STEP_ARGMAX, use_graph,
+                                   out_ids, out_ld, nullptr, out_len)))
         return rc;
     d->logits_stale_rows = lm_head_cand_path(d, S) ? S : 0;
     return RGRG_OK;
@@ -320,18 +329,10 @@ extern "C" int rgrg_decoder_beam_search_prompted(rgrg_decoder* d, const float* f
                                                  int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream) {
     RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && T >= 1 && num_beams > 1 && num_beams <= (1 << 14));
     RGRG_CHECK_ARG((long long)S * num_beams <= d->max_seqs);
-    // beam_search (:541, :597-605): the first iteration always runs, and finalize cannot hold a hypothesis longer than max_length
-    if (max_length < T + 1 || max_length > d->max_len) {
-        set_error("rgrg_decoder_beam_search_prompted: max_length %d with a prompt of %d tokens: %d .. %d (the cache) are possible", max_length,
-                  T, T + 1, d->max_len);
-        return RGRG_EINVAL;
-    }
-    if (rgrg_decoder_kv_format_in_use(d, S * num_beams) == KV_E4M3) {
-        set_error("rgrg_decoder_beam_search_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
-        return RGRG_EINVAL;
-    }
+    int rc, limit;
+    if ((rc = check_prompted(d, "rgrg_decoder_beam_search_prompted", S * num_beams, T, max_length, true, out_ld, &limit))) return rc;
     const BeamPrompt p{reinterpret_cast<const long long*>(input_ids), attention_mask, T};
-    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
+    return beam_search_run(d, feats, S, num_beams, limit, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
                            stream, &p);
 }
 
@@ -340,22 +341,14 @@ extern "C" int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const fl
                                                        int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
                                                        int out_ld, int* out_len, void* stream) {
     RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && T >= 1);
-    int rc;
+    int rc, limit;
     if ((rc = check_beam_groups("rgrg_decoder_group_beam_search_prompted", num_beams, num_beam_groups, diversity_penalty, num_return_sequences)))
         return rc;
     RGRG_CHECK_ARG((long long)S * num_beams <= d->max_seqs);
-    if (max_length < T + 1 || max_length > d->max_len) {
-        set_error("rgrg_decoder_group_beam_search_prompted: max_length %d with a prompt of %d tokens: %d .. %d (the cache) are possible",
-                  max_length, T, T + 1, d->max_len);
-        return RGRG_EINVAL;
-    }
-    if (rgrg_decoder_kv_format_in_use(d, S * num_beams) == KV_E4M3) {
-        set_error("rgrg_decoder_group_beam_search_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
-        return RGRG_EINVAL;
-    }
+    if ((rc = check_prompted(d, "rgrg_decoder_group_beam_search_prompted", S * num_beams, T, max_length, true, out_ld, &limit))) return rc;
     const BeamPrompt p{reinterpret_cast<const long long*>(input_ids), attention_mask, T};
     const BeamGroups grp{num_beam_groups, num_beam_groups > 1 ? diversity_penalty : 0.f};
-    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
+    return beam_search_run(d, feats, S, num_beams, limit, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
                            stream, &p, &grp);
 }
 
@@ -363,29 +356,11 @@ extern "C" int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats,
                                             int T, int max_length, float temperature, int top_k, float top_p, uint64_t seed,
                                             int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph, void* stream) {
     RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && S <= d->max_seqs && T >= 1);
-    if (T + 1 > d->max_len) {
-        set_error("rgrg_decoder_sample_prompted: a prompt of %d tokens and one generated token need %d token slots, the cache has %d",
-                  T, T + 1, d->max_len);
-        return RGRG_EINVAL;
-    }
-    int limit = (max_length > 0) ? max_length : d->max_len;   // as rgrg_decoder_generate_prompted: one token is always produced
-    if (limit < T + 1) limit = T + 1;
-    RGRG_CHECK_ARG(limit <= d->max_len && out_ld >= limit);
-    if (rgrg_decoder_kv_format_in_use(d, S) == KV_E4M3) {
-        set_error("rgrg_decoder_sample_prompted: the e4m3 K/V cache takes no prompt: call rgrg_decoder_set_kv_format(d, 0) first");
-        return RGRG_EINVAL;
-    }
-    int rc;
+    int rc, limit;
+    if ((rc = check_prompted(d, "rgrg_decoder_sample_prompted", S, T, max_length, false, out_ld, &limit))) return rc;
     if ((rc = sample_begin(d, S, temperature, top_k, top_p, seed, stream))) return rc;
-    bool padded = false;
-    if ((rc = prompt_mask_check(d, "rgrg_decoder_sample_prompted", attention_mask, S, T, &padded))) return rc;
-    if ((rc = tf_reserve(d, (size_t)S * T))) return rc;
-    PromptCall call{reinterpret_cast<const long long*>(input_ids), padded ? attention_mask : nullptr, S, T};
-    call.sample = true;
-    const DecodePrologue pro{enqueue_prompt, &call, T};
-    // a mask of ones leaves the steps of rgrg_decoder_sample (and their captured graph, key 3); a padded prompt has its own (key 7)
-    if ((rc = run_decode_loop(d, feats, S, limit, padded ? 7 : 3, padded ? padded_sample_step : sample_step, use_graph, out_ids, out_ld,
-                              out_logprobs, out_len, &pro)))
+    if ((rc = prompted_decode_loop(d, "rgrg_decoder_sample_prompted", feats, input_ids, attention_mask, S, T, limit, STEP_SAMPLE, use_graph,
+                                   out_ids, out_ld, out_logprobs, out_len)))
         return rc;
     d->logits_stale_rows = 0;   // the head behind the prompt and every step wrote d->logits
     return RGRG_OK;

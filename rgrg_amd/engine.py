@@ -722,6 +722,41 @@ class HipEngine:
             raise ValueError(f"kv_format_in_use: rows must be positive, got {rows}")
         return fmt
 
+    def _decode_call(self, name: str, call, feats: Tensor, rows: int, out_rows: int, limit: int, bf16, kv_fp8: bool,
+                     logprobs: bool = False):
+        """What every decode method shares: the decoder for ``rows`` token rows, its modes, the output buffers and the slice to the
+        decoded length; ``call(dec, feats_ptr, out_ptr, logprobs_ptr, out_len_ref)`` is the C call ``name`` -> ids int64
+        [out_rows, L'], with ``logprobs`` (ids, log-probs f32 [out_rows, L'])."""
+        dec = self._get_decoder(rows, limit)
+        self._cached = None   # the K/V cache and the step counter are rewritten: presents of an earlier forward(use_cache=True) are stale
+        self._set_modes(dec, bf16, kv_fp8)
+        feats = feats.to(torch.float32).contiguous()
+        out = torch.empty((out_rows, limit), dtype=torch.int64, device=feats.device)
+        lp = torch.empty((out_rows, limit), dtype=torch.float32, device=feats.device) if logprobs else None
+        out_len = C.c_int(0)
+        _hip.check(call(dec, _hip.ptr(feats), _hip.ptr(out), _hip.ptr(lp), C.byref(out_len)), name)
+        ids = out[:, :out_len.value].contiguous()
+        return (ids, lp[:, :out_len.value].contiguous()) if logprobs else ids
+
+    @staticmethod
+    def _prompt_limit(max_length: Optional[int], T: int) -> int:
+        """Greedy search and sampling behind a prompt of T tokens always produce one token (language_model.py:624-650)."""
+        limit = max(int(max_length) if max_length else 1024, T + 1)
+        if limit > 1024:
+            raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
+        return limit
+
+    @staticmethod
+    def _beam_prompt_limit(max_length: int, T: int) -> int:
+        """Beam search behind a prompt of T tokens: ``max_length`` is at least T + 1 and at most the model's 1024 positions."""
+        limit = int(max_length)
+        if limit < T + 1:
+            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens (one iteration always runs and the "
+                             f"scorer cannot hold a hypothesis longer than max_length), but is {limit}")
+        if limit > 1024:
+            raise ValueError(f"max_length {limit} exceeds the 1024 positions of the model")
+        return limit
+
     def greedy_decode(self, feats: Tensor, max_length: Optional[int], use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.generate(num_beams=1): feats [S,1024] -> int64 [S, L'].  bf16 = precision mode (opt-in through
         torch.autocast: False / 0 fp32, True / 1 bfloat16, 2 float16): lets the > 128-sequence path use 16-bit-weight MFMA GEMMs
@@ -730,16 +765,8 @@ class HipEngine:
         _require_gpu(feats.device)
         S = feats.shape[0]
         limit = int(max_length) if max_length else 1024  # reference has no bound when None; positions stop at 1024
-        dec = self._get_decoder(S, limit)
-        self._cached = None   # the K/V cache and the step counter are rewritten: presents of an earlier forward(use_cache=True) are stale
-        self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
-        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_generate(dec, _hip.ptr(feats), S, limit, _hip.ptr(out), limit,
-                                                  C.byref(out_len), 1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_generate")
-        return out[:, :out_len.value].contiguous()
+        return self._decode_call("rgrg_decoder_generate", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_generate(
+            dec, f, S, limit, out, limit, n, 1 if use_graph else 0, self._s()), feats, S, S, limit, bf16, kv_fp8)
 
     def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
                                use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
@@ -750,20 +777,10 @@ class HipEngine:
         mask row, a mask that is not left padding and the e4m3 cache in use raise RgrgHipError."""
         ids, am = self._check_prompt(feats, input_ids, attention_mask)
         S, T = ids.shape
-        limit = int(max_length) if max_length else 1024
-        limit = max(limit, T + 1)   # the reference's loop always produces one token (language_model.py:624-650)
-        if limit > 1024:
-            raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
-        dec = self._get_decoder(S, limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
-        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_generate_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, _hip.ptr(out),
-                                                           limit, C.byref(out_len), 1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_generate_prompted")
-        return out[:, :out_len.value].contiguous()
+        limit = self._prompt_limit(max_length, T)
+        return self._decode_call("rgrg_decoder_generate_prompted", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_generate_prompted(
+            dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, limit, out, limit, n, 1 if use_graph else 0, self._s()),
+            feats, S, S, limit, bf16, kv_fp8)
 
     def _check_prompt(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor]):
         """Shapes, dtypes and ids of a prompted decode call, as ``greedy_decode_prompted`` validates them -> (ids, mask or None)."""
@@ -795,23 +812,11 @@ class HipEngine:
         front.  Validation as ``greedy_decode_prompted``; ``max_length < T + 1`` raises ValueError."""
         ids, am = self._check_prompt(feats, input_ids, attention_mask)
         S, T = ids.shape
-        limit = int(max_length)
-        if limit < T + 1:
-            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens (one iteration always runs and the "
-                             f"scorer cannot hold a hypothesis longer than max_length), but is {limit}")
-        if limit > 1024:
-            raise ValueError(f"max_length {limit} exceeds the 1024 positions of the model")
-        dec = self._get_decoder(S * int(num_beams), limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
-        out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_beam_search_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), limit,
-                                                              1 if early_stopping else 0, float(length_penalty),
-                                                              int(num_return_sequences), _hip.ptr(out), limit, C.byref(out_len), self._s()),
-                   "rgrg_decoder_beam_search_prompted")
-        return out[:, :out_len.value].contiguous()
+        limit = self._beam_prompt_limit(max_length, T)
+        return self._decode_call("rgrg_decoder_beam_search_prompted", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_beam_search_prompted(
+            dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), limit, 1 if early_stopping else 0, float(length_penalty),
+            int(num_return_sequences), out, limit, n, self._s()),
+            feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
 
     def sample_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
                                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
@@ -823,28 +828,16 @@ class HipEngine:
         c from the Philox counter (r, c - 1).  Validation as ``greedy_decode_prompted``."""
         ids, am = self._check_prompt(feats, input_ids, attention_mask)
         n = int(num_return_sequences)
-        feats = feats.to(torch.float32)
         if n > 1:
             feats = feats.repeat_interleave(n, dim=0)
             ids = ids.repeat_interleave(n, dim=0).contiguous()
             am = None if am is None else am.repeat_interleave(n, dim=0).contiguous()
-        feats = feats.contiguous()
         S, T = ids.shape
-        limit = int(max_length) if max_length else 1024
-        limit = max(limit, T + 1)   # one token is always produced, as in greedy_decode_prompted
-        if limit > 1024:
-            raise ValueError(f"a prompt of {T} tokens and one generated token exceed the 1024 positions of the model")
-        dec = self._get_decoder(S, limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
-        lp = torch.empty((S, limit), dtype=torch.float32, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_sample_prompted(dec, _hip.ptr(feats), _hip.ptr(ids), _hip.ptr(am), S, T, limit, float(temperature),
-                                                         int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(out), limit,
-                                                         _hip.ptr(lp), C.byref(out_len), 1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_sample_prompted")
-        return out[:, :out_len.value].contiguous(), lp[:, :out_len.value].contiguous()
+        limit = self._prompt_limit(max_length, T)
+        return self._decode_call("rgrg_decoder_sample_prompted", lambda dec, f, out, lp, n_out: self.lib.rgrg_decoder_sample_prompted(
+            dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, limit, float(temperature), int(top_k), float(top_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, out, limit, lp, n_out, 1 if use_graph else 0, self._s()),
+            feats, S, S, limit, bf16, kv_fp8, logprobs=True)
 
     def sample_decode(self, feats: Tensor, max_length: Optional[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                       seed: int = 0, num_return_sequences: int = 1, bf16=False, use_graph: bool = True,
@@ -854,23 +847,13 @@ class HipEngine:
         uses).  Row r draws step t from the Philox counter (r, t) under ``seed`` (include/rgrg_hip.h "Sampling")."""
         _require_gpu(feats.device)
         n = int(num_return_sequences)
-        feats = feats.to(torch.float32)
         if n > 1:
             feats = feats.repeat_interleave(n, dim=0)
-        feats = feats.contiguous()
         S = feats.shape[0]
         limit = int(max_length) if max_length else 1024
-        dec = self._get_decoder(S, limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        out = torch.empty((S, limit), dtype=torch.int64, device=feats.device)
-        lp = torch.empty((S, limit), dtype=torch.float32, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_sample(dec, _hip.ptr(feats), S, limit, float(temperature), int(top_k), float(top_p),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(out), limit, _hip.ptr(lp), C.byref(out_len),
-                                                1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_sample")
-        return out[:, :out_len.value].contiguous(), lp[:, :out_len.value].contiguous()
+        return self._decode_call("rgrg_decoder_sample", lambda dec, f, out, lp, n_out: self.lib.rgrg_decoder_sample(
+            dec, f, S, limit, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, out, limit, lp, n_out,
+            1 if use_graph else 0, self._s()), feats, S, S, limit, bf16, kv_fp8, logprobs=True)
 
     def sample_logits(self, logits: Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                       step: int = 0, row0: int = 0, ld: Optional[int] = None, vocab: Optional[int] = None) -> Tuple[Tensor, Tensor]:
@@ -892,33 +875,10 @@ class HipEngine:
                     length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.generate(num_beams>1): feats [S,1024] -> int64 [S * num_return_sequences, L]."""
         _require_gpu(feats.device)
-        S = feats.shape[0]
-        limit = int(max_length)
-        dec = self._get_decoder(S * num_beams, limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
-        out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(self.lib.rgrg_decoder_beam_search(dec, _hip.ptr(feats), S, int(num_beams), limit, 1 if early_stopping else 0,
-                                                     float(length_penalty), int(num_return_sequences), _hip.ptr(out), limit,
-                                                     C.byref(out_len), self._s()),
-                   "rgrg_decoder_beam_search")
-        return out[:, :out_len.value].contiguous()
-
-    def _group_beam_call(self, feats: Tensor, limit: int, num_beams: int, num_return_sequences: int, bf16, kv_fp8: bool, name: str,
-                         call) -> Tensor:
-        """What the two diverse entries share: decoder, modes, output buffer; ``call(dec, feats_ptr, out_ptr, out_len_ref)`` is the
-        C call -> int64 [S * num_return_sequences, L]."""
-        S = feats.shape[0]
-        dec = self._get_decoder(S * int(num_beams), limit)
-        self._cached = None   # as in greedy_decode
-        self._set_modes(dec, bf16, kv_fp8)
-        feats = feats.to(torch.float32).contiguous()
-        out = torch.empty((S * int(num_return_sequences), limit), dtype=torch.int64, device=feats.device)
-        out_len = C.c_int(0)
-        _hip.check(call(dec, _hip.ptr(feats), _hip.ptr(out), C.byref(out_len)), name)
-        return out[:, :out_len.value].contiguous()
+        S, limit = feats.shape[0], int(max_length)
+        return self._decode_call("rgrg_decoder_beam_search", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_beam_search(
+            dec, f, S, int(num_beams), limit, 1 if early_stopping else 0, float(length_penalty), int(num_return_sequences), out, limit, n,
+            self._s()), feats, S * num_beams, S * int(num_return_sequences), limit, bf16, kv_fp8)
 
     def group_beam_search(self, feats: Tensor, max_length: int, num_beams: int, num_beam_groups: int, diversity_penalty: float,
                           early_stopping: bool = False, length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
@@ -927,11 +887,10 @@ class HipEngine:
         int64 [S * num_return_sequences, L].  The library refuses what diverse beam search cannot take (RgrgHipError)."""
         _require_gpu(feats.device)
         S, limit = feats.shape[0], int(max_length)
-        return self._group_beam_call(feats, limit, num_beams, num_return_sequences, bf16, kv_fp8, "rgrg_decoder_group_beam_search",
-                                     lambda dec, f, out, n: self.lib.rgrg_decoder_group_beam_search(
-                                         dec, f, S, int(num_beams), int(num_beam_groups), float(diversity_penalty), limit,
-                                         1 if early_stopping else 0, float(length_penalty), int(num_return_sequences), out, limit, n,
-                                         self._s()))
+        return self._decode_call("rgrg_decoder_group_beam_search", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_group_beam_search(
+            dec, f, S, int(num_beams), int(num_beam_groups), float(diversity_penalty), limit, 1 if early_stopping else 0,
+            float(length_penalty), int(num_return_sequences), out, limit, n, self._s()),
+            feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
 
     def group_beam_search_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: int,
                                    num_beams: int, num_beam_groups: int, diversity_penalty: float, early_stopping: bool = False,
@@ -942,17 +901,13 @@ class HipEngine:
         front.  Validation as ``beam_search_prompted``."""
         ids, am = self._check_prompt(feats, input_ids, attention_mask)
         S, T = ids.shape
-        limit = int(max_length)
-        if limit < T + 1:
-            raise ValueError(f"max_length has to be at least {T + 1} for a prompt of {T} tokens (one iteration always runs and the "
-                             f"scorer cannot hold a hypothesis longer than max_length), but is {limit}")
-        if limit > 1024:
-            raise ValueError(f"max_length {limit} exceeds the 1024 positions of the model")
-        return self._group_beam_call(feats, limit, num_beams, num_return_sequences, bf16, kv_fp8, "rgrg_decoder_group_beam_search_prompted",
-                                     lambda dec, f, out, n: self.lib.rgrg_decoder_group_beam_search_prompted(
-                                         dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), int(num_beam_groups),
-                                         float(diversity_penalty), limit, 1 if early_stopping else 0, float(length_penalty),
-                                         int(num_return_sequences), out, limit, n, self._s()))
+        limit = self._beam_prompt_limit(max_length, T)
+        return self._decode_call("rgrg_decoder_group_beam_search_prompted",
+                                 lambda dec, f, out, lp, n: self.lib.rgrg_decoder_group_beam_search_prompted(
+                                     dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), int(num_beam_groups),
+                                     float(diversity_penalty), limit, 1 if early_stopping else 0, float(length_penalty),
+                                     int(num_return_sequences), out, limit, n, self._s()),
+                                 feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
 
     def _raise_pending_id_error(self) -> None:
         """An unreported token-id error of a decoder that has been re-created since (close())."""

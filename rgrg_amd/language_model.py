@@ -287,6 +287,15 @@ class LanguageModel(EngineOwner):
     def _kv_fp8(self) -> bool:
         return self.kv_cache_dtype() == "fp8_e4m3"
 
+    def _decode_modes(self, device=None) -> dict:
+        """What every decode entry does in front of its engine call: "no CPU fallback" for ``device`` (before any engine is built),
+        the weights an optimizer step changed since the engine packed them, and -> the ``bf16`` / ``kv_fp8`` arguments of that call."""
+        if device is not None:
+            from .engine import _require_gpu
+            _require_gpu(device)
+        self.sync_trainable_if_stale()
+        return {"bf16": _hip.autocast_mode(), "kv_fp8": self._kv_fp8()}
+
     @torch.no_grad()
     def sample(self, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None, *, temperature: float = 1.0,
                top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
@@ -299,14 +308,11 @@ class LanguageModel(EngineOwner):
         (include/rgrg_hip.h "Sampling").  ``seed=None`` draws the seed from torch's CPU generator (``torch.manual_seed``
         governs it); the same seed gives the same ids.  torch.autocast opts into the 16-bit modes as for ``generate``."""
         check_sample_args(temperature, top_k, top_p, num_return_sequences)
-        from .engine import _require_gpu
-        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
-        self.sync_trainable_if_stale()
+        modes = self._decode_modes(image_hidden_states.device)
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        low = _hip.autocast_mode()
         ids, logprobs = self.engine().sample_decode(image_hidden_states, max_length, temperature, int(top_k), top_p, int(seed),
-                                                    int(num_return_sequences), bf16=low, kv_fp8=self._kv_fp8())
+                                                    int(num_return_sequences), **modes)
         return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
@@ -324,12 +330,8 @@ class LanguageModel(EngineOwner):
         torch.autocast opts into the 16-bit plans exactly as for ``generate``.  A BOS column with a mask of ones IS
         ``generate()``."""
         attention_mask = self._prompt_kwargs("greedy_search", model_kwargs)
-        from .engine import _require_gpu
-        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
-        self.sync_trainable_if_stale()
-        low = _hip.autocast_mode()
-        return self.engine().greedy_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, bf16=low,
-                                                    kv_fp8=self._kv_fp8())
+        modes = self._decode_modes(image_hidden_states.device)
+        return self.engine().greedy_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, **modes)
 
     @staticmethod
     def _prompt_kwargs(name: str, model_kwargs: dict):
@@ -390,10 +392,9 @@ class LanguageModel(EngineOwner):
 
     def _beam_search_prompts(self, prompts, mask, image_hidden_states, max_length, num_beams, early_stopping, length_penalty, keep):
         """``beam_search`` on unexpanded prompts [S,T] (one per item)."""
-        self.sync_trainable_if_stale()
-        low = _hip.autocast_mode()
+        modes = self._decode_modes()
         return self.engine().beam_search_prompted(image_hidden_states, prompts, mask, max_length, num_beams, early_stopping,
-                                                  length_penalty, bf16=low, num_return_sequences=keep, kv_fp8=self._kv_fp8())
+                                                  length_penalty, num_return_sequences=keep, **modes)
 
     @torch.no_grad()
     def group_beam_search(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, num_beam_groups: int,
@@ -418,18 +419,14 @@ class LanguageModel(EngineOwner):
         if input_ids is not None and int(max_length) < input_ids.shape[-1] + 1:
             raise ValueError(f"max_length has to be at least {input_ids.shape[-1] + 1} for a prompt of {input_ids.shape[-1]} tokens, "
                              f"but is {max_length}")
-        from .engine import _require_gpu
-        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
-        self.sync_trainable_if_stale()
-        low = _hip.autocast_mode()
+        modes = self._decode_modes(image_hidden_states.device)
         if input_ids is None:
             return self.engine().group_beam_search(image_hidden_states, int(max_length), int(num_beams), int(num_beam_groups),
-                                                   float(diversity_penalty), bool(early_stopping), float(length_penalty), bf16=low,
-                                                   num_return_sequences=int(num_return_sequences), kv_fp8=self._kv_fp8())
+                                                   float(diversity_penalty), bool(early_stopping), float(length_penalty),
+                                                   num_return_sequences=int(num_return_sequences), **modes)
         return self.engine().group_beam_search_prompted(image_hidden_states, input_ids, attention_mask, int(max_length), int(num_beams),
                                                         int(num_beam_groups), float(diversity_penalty), bool(early_stopping),
-                                                        float(length_penalty), bf16=low, num_return_sequences=int(num_return_sequences),
-                                                        kv_fp8=self._kv_fp8())
+                                                        float(length_penalty), num_return_sequences=int(num_return_sequences), **modes)
 
     @torch.no_grad()
     def sample_from_prompt(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None,
@@ -444,15 +441,11 @@ class LanguageModel(EngineOwner):
         if attention_mask is None:
             raise AttributeError("'NoneType' object has no attribute 'to' (sample_from_prompt needs attention_mask, like the "
                                  "reference's forward, language_model.py:281)")
-        from .engine import _require_gpu
-        _require_gpu(image_hidden_states.device)   # "no CPU fallback", before any engine is built
-        self.sync_trainable_if_stale()
+        modes = self._decode_modes(image_hidden_states.device)
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
-        low = _hip.autocast_mode()
         ids, logprobs = self.engine().sample_decode_prompted(image_hidden_states, input_ids, attention_mask, max_length, temperature,
-                                                             int(top_k), top_p, int(seed), int(num_return_sequences), bf16=low,
-                                                             kv_fp8=self._kv_fp8())
+                                                             int(top_k), top_p, int(seed), int(num_return_sequences), **modes)
         return (ids, logprobs) if return_logprobs else ids
 
     @torch.no_grad()
