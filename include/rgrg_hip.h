@@ -298,6 +298,41 @@ int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const float* feats,
 int rgrg_debug_beam_group_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
                                 const float* beam_scores, int S, int nb, int G, float penalty, int V, float* out_score, int* out_tok,
                                 int* out_beam, void* stream);
+/* Test hooks: the rank and arg-max kernels of greedy and plain beam search alone on caller buffers.  Each goes through the launch
+ * the decoder makes (the beam hooks through the decoder's own choice of kernel), synchronizes the stream, and refuses with
+ * RGRG_EINVAL, before any launch, what would let a kernel leave the caller's buffers: a NULL pointer and the cases named below.
+ *
+ * rgrg_debug_beam_row_topk: per row of logits f32 [rows][ld] (columns V .. ld - 1 are never read), K = 2 num_beams:
+ *   row_max [rows] = the maximum; row_logsum [rows] = log(sum(exp(x - max))) in fp32 (fixed summation order; a -inf logit counts
+ *   as zero mass - at least one logit of the row must be finite); top_val / top_tok = the K best (value descending, ties to the
+ *   lower token; +0.0 and -0.0 are equal), the value bits as read.  K <= 32: beam_row_topk_kernel<8,1024> (K <= 8), <16,1024>
+ *   (K <= 16), <32,512>, candidate rows 32 wide (entries K .. 31 untouched); K > 32: beam_row_topk_wide_kernel, rows K wide.
+ *   A -inf logit is never listed, so a row needs K logits above -inf.  With RGRG_DEBUG_BEAM_WIDE=1 in the environment (read by
+ *   these two hooks only, at every call) the wide kernels run at K <= 32 as well, on rows K wide.
+ *   RGRG_EINVAL: V < 1, ld < V, rows < 1, K < 2, K odd, K > V.
+ * rgrg_debug_beam_merge: per item s of S, from the nb rows s * nb .. of such lists (K = 2 nb): score = ((v - row_max) - row_logsum)
+ *   + beam_score per candidate, fp32, each operation rounded once; the K best by (score descending, flat index beam * V + token
+ *   ascending) -> out_score f32 / out_tok i32 / out_beam i32 [S][K] (beam: the row within the item).  nb <= 16: beam_merge_kernel on
+ *   rows 32 wide; wider: beam_merge_wide_kernel on rows K wide with score_scratch f32 [S][nb * K] (required, unused when nb <= 16).
+ *   RGRG_EINVAL: S outside 1 .. 65535, nb < 1, V < 2 nb.
+ * rgrg_debug_logits_candidates: logits_candidates_kernel as the tiled greedy step launches it, NT = ceil(V / 32) and a (4, rows) grid:
+ *   cand_val f32 / cand_idx i32 [rows][NT] = maximum and first column holding it of every 32-column tile, columns >= V left out.
+ *   The kernel reads whole tiles with 16-byte loads: RGRG_EINVAL for ld < V, ld < 32 NT, ld % 4 != 0, logits not 16-byte aligned,
+ *   V < 1, rows outside 1 .. 65535.
+ * rgrg_debug_argmax_update: argmax_update_kernel over cand_val / cand_idx [S][NT] - the row's token is the cand_idx of its largest
+ *   cand_val, ties to the lower cand_idx (a row of -inf candidates is such a tie: its lowest cand_idx, which is column 0 behind
+ *   logits_candidates_kernel) - with the bookkeeping of a greedy step at t = *step: a
+ *   finished row takes PAD; ids[s][t + 1] = token; EOS finishes the row; the last row to arrive sets *done_len = t + 2 if every row
+ *   is finished and *done_len was 0, *step = t + 1 and sync[0] = 0 (sync[0] must be 0 at the call).  ids int64 [S][ld_ids].
+ *   RGRG_EINVAL: NT < 1, S outside 1 .. 65535, *step (read back before the launch) outside 0 .. ld_ids - 2. */
+int rgrg_debug_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum, float* top_val,
+                             int* top_tok, void* stream);
+int rgrg_debug_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+                          const float* beam_scores, int S, int nb, int V, float* score_scratch, float* out_score, int* out_tok,
+                          int* out_beam, void* stream);
+int rgrg_debug_logits_candidates(const float* logits, int ld, int V, int rows, float* cand_val, int* cand_idx, void* stream);
+int rgrg_debug_argmax_update(const float* cand_val, const int* cand_idx, int NT, int64_t* ids, int ld_ids, int* finished, int* step,
+                             int* done_len, int* sync, int S, void* stream);
 /* Opt-in reduced precision for MANY sequences (BASELINE configs[2], batch 32): mode 1 (bfloat16) / 2 (float16) makes the
  * > 128-row paths run their projections on the 16-bit MFMA (16-bit weights and GEMM inputs, fp32 accumulate / LayerNorm /
  * softmax / residual) and keep the decode K/V cache in that type (what the reference's torch.autocast does to `present`);

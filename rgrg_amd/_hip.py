@@ -71,6 +71,10 @@ SIGNATURES = {
     "rgrg_decoder_group_beam_search": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
     "rgrg_decoder_group_beam_search_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
     "rgrg_debug_beam_group_merge": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p]),
+    "rgrg_debug_beam_row_topk": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "rgrg_debug_beam_merge": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "rgrg_debug_logits_candidates": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "rgrg_debug_argmax_update": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p]),
     "rgrg_decoder_sample_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_decoder_set_precision": (_i, [_p, _i]),
     "rgrg_decoder_set_kv_format": (_i, [_p, _i]),

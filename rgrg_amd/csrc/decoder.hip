@@ -2527,3 +2527,35 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     if (gemm_launches) *gemm_launches = d->gemm_launches_per_step;
     return RGRG_OK;
 }
+
+// Test hooks: the two kernels behind a greedy step's logits alone on caller buffers, launched as enqueue_head launches them.
+// logits_candidates_kernel: NT = ceil(V / 32) tiles per row on a (4, rows) grid.
+extern "C" int rgrg_debug_logits_candidates(const float* logits, int ld, int V, int rows, float* cand_val, int* cand_idx, void* stream) {
+    RGRG_CHECK_ARG(logits && cand_val && cand_idx && V >= 1 && rows >= 1 && rows <= 65535);
+    const int NT = (V + 31) / 32;
+    RGRG_CHECK_ARG(ld >= V && ld >= 32 * NT && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, rows), dim3(256), 0, st, logits, ld, V, NT, cand_val, cand_idx);
+    hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { set_error("rgrg_debug_logits_candidates: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return RGRG_OK;
+}
+// argmax_update_kernel with record_step_token: one workgroup per row.  *step is read back first: column *step + 1 must exist.
+extern "C" int rgrg_debug_argmax_update(const float* cand_val, const int* cand_idx, int NT, int64_t* ids, int ld_ids, int* finished,
+                                        int* step, int* done_len, int* sync, int S, void* stream) {
+    RGRG_CHECK_ARG(cand_val && cand_idx && ids && finished && step && done_len && sync && NT >= 1 && S >= 1 && S <= 65535 && ld_ids >= 2);
+    hipStream_t st = as_stream(stream);
+    int t = -1;
+    RGRG_HIP(hipMemcpyAsync(&t, step, sizeof(int), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    RGRG_CHECK_ARG(t >= 0 && t + 1 < ld_ids);
+    hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, cand_val, cand_idx, NT, reinterpret_cast<long long*>(ids), ld_ids,
+                       finished, step, done_len, sync, S);
+    hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { set_error("rgrg_debug_argmax_update: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return RGRG_OK;
+}

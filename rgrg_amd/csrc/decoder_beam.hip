@@ -4,6 +4,7 @@
 // STEP_BEAM; the ranking behind it is captured into the step's graph (step_graph).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "decoder_internal.h"
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(THREADS) void beam_row_topk_kernel(const float* __r
             if (i >= V) break;
             const float v = vb[u];
             if (v > tm) { ts = ts * expf(tm - v) + 1.0f; tm = v; }   // (first element: 0 * exp(-inf) + 1)
-            else ts += expf(v - tm);
+            else if (v > -INFINITY) ts += expf(v - tm);   // -inf is zero mass; while tm is still -inf, exp(-inf - -inf) would be NaN
             if (v > lv[LIST - 1]) {  // strided indices ascend, so an equal value never displaces an earlier one
                 lv[LIST - 1] = v; li[LIST - 1] = i;
 #pragma unroll
@@ -346,6 +347,37 @@ __global__ __launch_bounds__(256) void beam_init_kernel(int* __restrict__ src, i
     if (r == 0) *step = 0;
 }
 
+// The two launches of a plain ranking, shared by beam_search_run and the test hooks (rgrg_debug_beam_row_topk / _merge), and the
+// one place that chooses the kernel.  More than 16 beams (K > BEAM_K): the K-round kernels on candidate rows K wide; up to 16: the
+// register lists, LIST >= K, on rows BEAM_K wide.  force_wide (the hooks only): the K-round kernels at any K.
+static bool beam_wide(int K, bool force_wide = false) { return force_wide || K > BEAM_K; }
+// Row ranking of `rows` logits rows, K = 2 num_beams candidates each.
+static void launch_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum, float* top_val,
+                                 int* top_tok, bool force_wide, hipStream_t st) {
+    if (beam_wide(K, force_wide)) {
+        hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(rows), dim3(BEAM_ROW_THREADS), 0, st, logits, ld, V, K, row_max, row_logsum,
+                           top_val, top_tok);
+        return;
+    }
+#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(rows), dim3(THREADS_), 0, st, logits, ld, V, K, \
+                                              row_max, row_logsum, top_val, top_tok)
+    if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
+#undef BEAM_TOPK
+}
+// Item merge of S items with nb rows of K = 2 nb candidates (rows as launch_beam_row_topk left them); `score` [S][nb * K] is the
+// wide form's scratch.
+static void launch_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+                              const float* beam_scores, int S, int nb, int V, float* score, float* out_score, int* out_tok, int* out_beam,
+                              bool force_wide, hipStream_t st) {
+    const int K = 2 * nb;
+    if (beam_wide(K, force_wide))
+        hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, row_max, row_logsum, top_val, top_tok, beam_scores, nb, K, V,
+                           score, out_score, out_tok, out_beam);
+    else
+        hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, row_max, row_logsum, top_val, top_tok, beam_scores,
+                           nb, K, V, out_score, out_tok, out_beam);
+}
+
 }  // namespace rgrg
 
 using namespace rgrg;
@@ -399,7 +431,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     const int G = groups ? groups->G : 1, gs = nb / G;   // K = G * 2 gs candidate slots per item either way
     RGRG_CHECK_ARG(R <= d->max_seqs && max_length >= 2 && max_length <= d->max_len && out_ld >= max_length);
     hipStream_t st = d->stream;
-    const bool wide = K > BEAM_K;   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
+    const bool wide = beam_wide(K);   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
     if (wide && d->wide_cap < (size_t)R * K) {
         RGRG_HIP(hipStreamSynchronize(st));
         for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);   // (captured beam steps bake the buffers in)
@@ -453,23 +485,14 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     bool first_ranking = prompt != nullptr;
     // the ranking of d->logits behind a step (captured with it) or behind the prompt's last position
     auto enqueue_ranking = [&]() {
-        if (!wide) {
-#define BEAM_TOPK(LIST_, THREADS_) hipLaunchKernelGGL((beam_row_topk_kernel<LIST_, THREADS_>), dim3(R), dim3(THREADS_), 0, st, d->logits, d->ld_logits, d->V, K, \
-                                              d->row_max, d->row_logsum, d->top_val, d->top_tok)
-            if (K <= 8) BEAM_TOPK(8, 1024); else if (K <= 16) BEAM_TOPK(16, 1024); else BEAM_TOPK(32, 512);
-#undef BEAM_TOPK
-            if (groups)
-                hipLaunchKernelGGL(beam_group_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
-                                   d->top_tok, d->beam_scores, nb, G, d->group_penalty, d->V, d->cand_score, d->cand_tok, d->cand_beam);
-            else
-                hipLaunchKernelGGL(beam_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
-                                   d->top_tok, d->beam_scores, nb, K, d->V, d->cand_score, d->cand_tok, d->cand_beam);
-        } else {
-            hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(R), dim3(BEAM_ROW_THREADS), 0, st, d->logits, d->ld_logits, d->V, K,
-                               d->row_max, d->row_logsum, d->wide_val, d->wide_tok);
-            hipLaunchKernelGGL(beam_merge_wide_kernel, dim3(S), dim3(256), 0, st, d->row_max, d->row_logsum, d->wide_val, d->wide_tok,
-                               d->beam_scores, nb, K, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam);
-        }
+        launch_beam_row_topk(d->logits, d->ld_logits, d->V, R, K, d->row_max, d->row_logsum, wide ? d->wide_val : d->top_val,
+                             wide ? d->wide_tok : d->top_tok, false, st);
+        if (groups)
+            hipLaunchKernelGGL(beam_group_merge_kernel, dim3(S), dim3(BEAM_MERGE_THREADS), 0, st, d->row_max, d->row_logsum, d->top_val,
+                               d->top_tok, d->beam_scores, nb, G, d->group_penalty, d->V, d->cand_score, d->cand_tok, d->cand_beam);
+        else
+            launch_beam_merge(d->row_max, d->row_logsum, wide ? d->wide_val : d->top_val, wide ? d->wide_tok : d->top_tok, d->beam_scores,
+                              S, nb, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam, false, st);
     };
     std::vector<float> nscore(R);
     std::vector<int> ntok(R), nidx(R);
@@ -649,4 +672,36 @@ extern "C" int rgrg_debug_beam_group_merge(const float* row_max, const float* ro
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) { set_error("rgrg_debug_beam_group_merge: %s", hipGetErrorString(e)); return RGRG_EHIP; }
     return RGRG_OK;
+}
+
+// Test hooks: the plain ranking's two launches alone on caller buffers, through launch_beam_row_topk / launch_beam_merge - the
+// decoder's own choice of kernel.  RGRG_DEBUG_BEAM_WIDE=1 (read per call, by the hooks only) takes the wide form at K <= 32 too.
+static bool debug_force_wide() {
+    const char* e = getenv("RGRG_DEBUG_BEAM_WIDE");
+    return e && e[0] == '1';
+}
+static int debug_sync(const char* who, hipStream_t st) {
+    hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(e)); return RGRG_EHIP; }
+    return RGRG_OK;
+}
+extern "C" int rgrg_debug_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum,
+                                        float* top_val, int* top_tok, void* stream) {
+    RGRG_CHECK_ARG(logits && row_max && row_logsum && top_val && top_tok);
+    RGRG_CHECK_ARG(V >= 1 && ld >= V && rows >= 1 && K >= 2 && K % 2 == 0 && K <= V);
+    hipStream_t st = as_stream(stream);
+    launch_beam_row_topk(logits, ld, V, rows, K, row_max, row_logsum, top_val, top_tok, debug_force_wide(), st);
+    return debug_sync("rgrg_debug_beam_row_topk", st);
+}
+extern "C" int rgrg_debug_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+                                     const float* beam_scores, int S, int nb, int V, float* score_scratch, float* out_score, int* out_tok,
+                                     int* out_beam, void* stream) {
+    RGRG_CHECK_ARG(row_max && row_logsum && top_val && top_tok && beam_scores && score_scratch && out_score && out_tok && out_beam);
+    RGRG_CHECK_ARG(S >= 1 && S <= 65535 && nb >= 1 && nb <= (1 << 14) && V >= 2 * nb);
+    hipStream_t st = as_stream(stream);
+    launch_beam_merge(row_max, row_logsum, top_val, top_tok, beam_scores, S, nb, V, score_scratch, out_score, out_tok, out_beam,
+                      debug_force_wide(), st);
+    return debug_sync("rgrg_debug_beam_merge", st);
 }
