@@ -530,6 +530,14 @@ int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t* Wb, const 
  * LDS and stores whole rows, 16 bytes per lane).  RGRG_WIDE_EPI=0, read per launch, keeps the epilogue that stores from the MFMA's
  * C layout; a test that compares the two reads this counter to know which one a launch ran. */
 int rgrg_debug_wide_epilogue_launches(void);
+/* How many GEMM launches of this process took a consumer instantiation that knows its activation at compile time (csrc/gemm_bf16.hip,
+ * gemm_bf16_glds_kernel CACT: c_fc and c_attn of the many-sequence 16-bit decode step on the 64 x 64 tile; the per-element switch
+ * on the run-time `act` is not hoisted by the compiler and costs ~1 us of a 9.5 us launch).  The launcher takes it for a consumer
+ * with act NONE or GELU_NEW (NONE with the K/V-cache epilogue), N % 64 == 0, ldy % 8 == 0, 16-byte aligned Y / Y16 / shift /
+ * ln_colsum and 8-byte aligned cache planes - the launches of the decode step; everything else keeps the instantiation with the
+ * run-time switch.  RGRG_CONS_EPI, read per launch: unset or 1 = as described, 0 = never.  The arithmetic and the bits are the
+ * same either way; a test that compares the two reads this counter to know which one a launch ran. */
+int rgrg_debug_cons_epilogue_launches(void);
 /* Test hooks for the attention kernels (GPT2PseudoAttention, src/language_model/language_model.py: _attn :84-122 - scores / 8,
  * future token columns replaced by -1e4, the additive padding mask (1 - [1 | attention_mask]) * -1e4 of :316-334, softmax,
  * attn_dropout :116, the product with V - and forward :124-160, which puts the image key / value uk(img) / uv(img) in front of

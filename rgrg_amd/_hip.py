@@ -107,6 +107,7 @@ SIGNATURES = {
     "rgrg_debug_linear_bf16_ln": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln_kp": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_wide_epilogue_launches": (_i, []),
+    "rgrg_debug_cons_epilogue_launches": (_i, []),
     "rgrg_debug_attn_decode": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_linear_bf16_ln_kv": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_qonly": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -379,6 +379,16 @@ __device__ __forceinline__ void glds_compute(const unsigned char* sa, const unsi
     __builtin_amdgcn_sched_group_barrier(0x008, MI * NI, 0);
 }
 
+// The activation of a consumer epilogue.  CACT = RGRG_ACT_NONE / RGRG_ACT_GELU_NEW: known at compile time; -1: the run-time
+// switch on p.act (hipcc does not hoist it out of the element loop although p.act is uniform: ~5 scalar compare-and-branch
+// pairs per element).  Same arithmetic either way.
+template <int CACT>
+__device__ __forceinline__ float cons_act(float v, int act) {
+    if constexpr (CACT == RGRG_ACT_NONE) return v;
+    else if constexpr (CACT == RGRG_ACT_GELU_NEW) return gelu_new_fast(v);
+    else return apply_act_fast(v, act);
+}
+
 // CONV: the A operand is the im2col view of an NHWC bf16 image - row m of a K tile = 64 channels [c0, c0 + 64) of input pixel
 // (oy * stride + kh - pad, ox * stride + kw - pad): still one contiguous 128-byte line per row, so the LDS-DMA path is
 // unchanged; only the per-lane source offset is recomputed per K tile (tap = kt * 64 / Cin, a handful of integer
@@ -387,7 +397,8 @@ __device__ __forceinline__ void glds_compute(const unsigned char* sa, const unsi
 // columns go to the 16-bit K/V cache (kv_k / kv_v / kv_step) - GemmBf16Params.
 // Compile-time so that the plain kernel carries none of it (as runtime branches the conditional loads made hipcc drain
 // the whole operand prologue - vmcnt(0) - at the join in front of the K loop of EVERY variant).
-template <int BM, int BN, int NST, bool CONV, bool F16, int LNF>
+// CACT (consumers on the 64 x 64 tile, launch_glds_cfg decides): the activation as a compile-time constant (cons_act); -1 = p.act.
+template <int BM, int BN, int NST, bool CONV, bool F16, int LNF, int CACT = -1>
 __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Params p, const int mtiles, const int ntiles) {
     constexpr int BK = 64;
     constexpr int MI = BM / 64, NI = BN / 64;   // 32x32 MFMA blocks per wave
@@ -397,6 +408,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     static_assert((NST - 2) * LPW < 64, "counted vmcnt out of range");
     static_assert(NST >= 2 && NST <= 4, "tail is written for up to 3 trailing tiles");
     constexpr bool CONS = LNF >= 2, KVC = LNF == 3;
+    static_assert(CACT == -1 || (CONS && BM == 64 && BN == 64), "compile-time activation: consumers on the 64 x 64 tile");
+    constexpr int ETAG = (CACT + 1) * 256;   // glds_issue: one specialization per kernel instantiation
     extern __shared__ __attribute__((aligned(16))) unsigned char glds_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -458,9 +471,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
                 const bool in_ = (unsigned)iy_ < (unsigned)p.cH && (unsigned)ix_ < (unsigned)p.cW;                     \
                 va[j] = (in_ ? 256 + (cpix[j] + iy_ * p.cW + ix_) * p.cCin * 2 + c0_ * 2 : 0) + cswz[j];               \
             }                                                                                                          \
-            glds_issue<BM, LA, LB, LNF * 64 + NST * 4 + 2 + (F16 ? 1 : 0)>(abase, wbase, glds_smem + (STAGE_) * STAGE + wave * 1024, va, vb, 0, (KT_) * (BK * 2)); \
+            glds_issue<BM, LA, LB, ETAG + LNF * 64 + NST * 4 + 2 + (F16 ? 1 : 0)>(abase, wbase, glds_smem + (STAGE_) * STAGE + wave * 1024, va, vb, 0, (KT_) * (BK * 2)); \
         } else {                                                                                                       \
-            glds_issue<BM, LA, LB, LNF * 64 + NST * 4 + (F16 ? 1 : 0)>(abase, wbase, glds_smem + (STAGE_) * STAGE + wave * 1024, va, vb, (KT_) * (BK * 2),       \
+            glds_issue<BM, LA, LB, ETAG + LNF * 64 + NST * 4 + (F16 ? 1 : 0)>(abase, wbase, glds_smem + (STAGE_) * STAGE + wave * 1024, va, vb, (KT_) * (BK * 2),       \
                                             (KT_) * (BK * 2));                                                         \
         }                                                                                                              \
     }
@@ -663,7 +676,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float2 st = row_stat[lrow0 + (r & 3) + 8 * (r >> 2)];
-                    vv[r] = apply_act_fast(st.y * (acc[mi][ni][r] - st.x * cs) + sh + rv[r], p.act);
+                    vv[r] = cons_act<CACT>(st.y * (acc[mi][ni][r] - st.x * cs) + sh + rv[r], p.act);
                 }
             } else if constexpr (LNF == 0 && !CONV) {
                 if (p.G16) {   // dgrad through gelu_new: the result times gelu_new'(saved pre-activation)
@@ -1176,6 +1189,11 @@ static int glds_attr() {
     RGRG_G_ATTR(false, false, 0); RGRG_G_ATTR(true, false, 0); RGRG_G_ATTR(false, true, 0); RGRG_G_ATTR(true, true, 0);
     RGRG_G_ATTR(false, false, 1); RGRG_G_ATTR(false, true, 1); RGRG_G_ATTR(false, false, 2); RGRG_G_ATTR(false, true, 2);
     RGRG_G_ATTR(false, false, 3); RGRG_G_ATTR(false, true, 3);
+    if constexpr (BM == 64 && BN == 64) {   // the consumers with a compile-time activation (launch_glds_cfg)
+        RGRG_G_ATTR(false, false, 2, RGRG_ACT_NONE); RGRG_G_ATTR(false, true, 2, RGRG_ACT_NONE);
+        RGRG_G_ATTR(false, false, 2, RGRG_ACT_GELU_NEW); RGRG_G_ATTR(false, true, 2, RGRG_ACT_GELU_NEW);
+        RGRG_G_ATTR(false, false, 3, RGRG_ACT_NONE); RGRG_G_ATTR(false, true, 3, RGRG_ACT_NONE);
+    }
 #undef RGRG_G_ATTR
     return RGRG_OK;
 }
@@ -1211,6 +1229,24 @@ static int gemm_gm_override() {
     return v;
 }
 
+// RGRG_CONS_EPI, read per launch like RGRG_WIDE_EPI (A/B runs and tests compare the epilogues in one process): unset or 1 = a
+// consumer on the 64 x 64 tile runs the instantiation that knows its activation at compile time (gemm_bf16_glds_kernel CACT),
+// 0 = the one with the run-time switch on p.act.  Same arithmetic, same bits.
+static std::atomic<int> cons_epi_launches{0};   // rgrg_debug_cons_epilogue_launches
+static bool cons_epi_enabled() {
+    const char* e = getenv("RGRG_CONS_EPI");
+    return !e || (atoi(e) & 1) != 0;
+}
+// c_fc / c_attn as the many-sequence decode step launches them: act NONE or GELU_NEW (NONE with the K/V-cache epilogue), whole
+// 64-column tiles, rows of 16-byte pieces on 16-byte aligned bases (cache planes: 8).  Anything else keeps the run-time switch.
+static bool cons_epi_ok(const GemmBf16Params& p) {
+    const auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
+    if (!p.ln_colsum || p.Yb16 || p.cCin || p.N % 64 != 0 || p.ldy % 8 != 0) return false;
+    if (!al(p.Y, 16) || !al(p.Y16, 16) || !al(p.shift, 16) || !al(p.ln_colsum, 16)) return false;
+    if (p.kv_k) return p.act == RGRG_ACT_NONE && al(p.kv_k, 8) && al(p.kv_v, 8);
+    return p.act == RGRG_ACT_NONE || p.act == RGRG_ACT_GELU_NEW;
+}
+
 template <int BM, int BN, int NST>
 static int launch_glds_cfg(const GemmBf16Params& p0, hipStream_t st) {
     GemmBf16Params p = p0;
@@ -1221,8 +1257,18 @@ static int launch_glds_cfg(const GemmBf16Params& p0, hipStream_t st) {
     }
     const int ks = (!p.cCin && p.ksplit > 1 && p.sk_ws && p.sk_cnt && (p.K / 64) % p.ksplit == 0 && p.K / 64 / p.ksplit >= NST - 1) ? p.ksplit : 1;
     p.ksplit = ks;
-#define RGRG_G_LAUNCH(CONV_, F16_, LNF_) hipLaunchKernelGGL((gemm_bf16_glds_kernel<BM, BN, NST, CONV_, F16_, LNF_>), dim3(mtiles * ntiles * ks), dim3(256), NST * (BM + BN) * 128 + BM * 16, st, p, mtiles, ntiles)
-    if (p.cCin) { if (p.f16) RGRG_G_LAUNCH(true, true, 0); else RGRG_G_LAUNCH(true, false, 0); }
+#define RGRG_G_LAUNCH(...) hipLaunchKernelGGL((gemm_bf16_glds_kernel<BM, BN, NST, __VA_ARGS__>), dim3(mtiles * ntiles * ks), dim3(256), NST * (BM + BN) * 128 + BM * 16, st, p, mtiles, ntiles)
+    bool cons = false;
+    if constexpr (BM == 64 && BN == 64) cons = cons_epi_enabled() && cons_epi_ok(p);
+    if (cons) {
+        cons_epi_launches.fetch_add(1, std::memory_order_relaxed);
+        if constexpr (BM == 64 && BN == 64) {
+            if (p.kv_k) { if (p.f16) RGRG_G_LAUNCH(false, true, 3, RGRG_ACT_NONE); else RGRG_G_LAUNCH(false, false, 3, RGRG_ACT_NONE); }
+            else if (p.act == RGRG_ACT_NONE) { if (p.f16) RGRG_G_LAUNCH(false, true, 2, RGRG_ACT_NONE); else RGRG_G_LAUNCH(false, false, 2, RGRG_ACT_NONE); }
+            else { if (p.f16) RGRG_G_LAUNCH(false, true, 2, RGRG_ACT_GELU_NEW); else RGRG_G_LAUNCH(false, false, 2, RGRG_ACT_GELU_NEW); }
+        }
+    }
+    else if (p.cCin) { if (p.f16) RGRG_G_LAUNCH(true, true, 0); else RGRG_G_LAUNCH(true, false, 0); }
     else if (p.Yb16) { if (p.f16) RGRG_G_LAUNCH(false, true, 1); else RGRG_G_LAUNCH(false, false, 1); }
     else if (p.ln_colsum && p.kv_k) { if (p.f16) RGRG_G_LAUNCH(false, true, 3); else RGRG_G_LAUNCH(false, false, 3); }
     else if (p.ln_colsum) { if (p.f16) RGRG_G_LAUNCH(false, true, 2); else RGRG_G_LAUNCH(false, false, 2); }
@@ -1508,6 +1554,7 @@ extern "C" int rgrg_debug_linear_bf16_ln_kp(const uint16_t* A16, const uint16_t*
 }
 
 extern "C" int rgrg_debug_wide_epilogue_launches(void) { return kp_wide_launches.load(std::memory_order_relaxed); }
+extern "C" int rgrg_debug_cons_epilogue_launches(void) { return cons_epi_launches.load(std::memory_order_relaxed); }
 
 // nn.Conv2d (+ folded eval BatchNorm + residual + ReLU) as an implicit GEMM on the bf16 matrix core, for the detector
 // under torch.autocast (the reference runs trunk / RPN in half precision there, generate_reports_for_images.py:108).
