@@ -10,15 +10,11 @@
 // consecutive k) is conflict free.  A and B fragments use the same (lane half, element) -> k mapping, so
 // the K order inside a tile is irrelevant.  Not bit-exact with the fp32 reference by construction: this
 // path is opt-in (torch.autocast) and its tests are tolerance-based.
-#include "internal.h"
+#include "gemm_bf16_device.h"
 
 #include <atomic>
 
 namespace rgrg {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 
 struct GemmBf16Params {
     const float* A;    // fp32 activations (rounded to bf16 while staged) ...
@@ -79,17 +75,8 @@ struct GemmBf16Params {
     int dbg = 0;   // ping-pong kernel, measurements only (RGRG_PP_DBG): 1 no fragment reads, 2 no refill DMAs, 4 no MFMAs, 8 no stores
 };
 
-constexpr float LN_EPS16 = 1e-5f;   // nn.LayerNorm(eps=1e-5) of GPT-2
-
 constexpr int BK16 = 64;                 // k per tile
 constexpr int LDB = (BK16 * 2 + 16) / 2;  // padded LDS row in bf16 elements (144 B)
-
-// one 32x32x16 matrix-core step on 16-bit fragments of either type (fp32 accumulate)
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma16(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 // Workgroup = BM x BN output tile, THREADS/64 waves in a 2 x (WAVES/2) grid, each wave a (BM/2) x (BN/(WAVES/2))
 // sub-tile of 32x32 MFMA blocks.  M ~ 1000 rows gives only ~1 workgroup per CU, so memory latency cannot be
@@ -180,12 +167,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16w_kernel(const GemmBf16Param
     static_assert(AL + BL == BK16 / 16, "one staging item per 16-wide K step");
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    zero_acc(acc);
 
     // prologue: tiles 0..NS-1 in flight, tile 0 staged
 #pragma unroll
@@ -252,14 +234,11 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16w_kernel(const GemmBf16Param
             for (int r = 0; r < 16; ++r) rv[r] = 0.f;
             if (p.R) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                    rv[r] = p.R[(size_t)row * p.ldy + colc];
-                }
+                for (int r = 0; r < 16; ++r) rv[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2);
+                const int row = c_row(r, rbase);
                 const float v = apply_act(acc[mi][ni][r] + sh + rv[r], p.act);
                 if (row < p.M && col < p.N) {
                     if (p.Y16) p.Y16[(size_t)row * p.ldy + col] = (u16)to16<F16>(v);
@@ -294,39 +273,6 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16w_kernel(const GemmBf16Param
 // waves, an L2-prefetch wave, K rotation, padded pitches: all measured within +-5 %, the prefetch wave -20 %).  What helps
 // is MORE WORKGROUPS PER CU (their prologues / epilogues overlap): 64 x 64 tiles with 2-3 stages where the GEMM has few
 // tiles, 128 x 128 with 2 stages (two workgroups per CU) for the vocabulary-sized lm_head.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bf16_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// gelu_new for a bf16 consumer: x * sigmoid(2 sqrt(2/pi) (x + 0.044715 x^3)) on the hardware exp2 / rcp (~1e-7 relative
-// to the tanhf form, far below bf16 resolution).  tanhf costs ~40 VALU instructions; a lane of the 128 x 128 tile has 64
-// outputs and the wave is alone on its SIMD: the tanhf epilogue was 8 of the 25 us of c_fc.
-__device__ __forceinline__ float gelu_new_fast(float x) {
-    const float u = x * (1.0f + 0.044715f * x * x);
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.302208198f * u));  // -2 * sqrt(2/pi) * log2(e)
-}
-// gelu_new'(x) with s = sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3):  tanh u = 2s - 1, so
-//   0.5 (1 + tanh u) + 0.5 x (1 - tanh^2 u) u'  =  s + 2 x s (1 - s) sqrt(2/pi) (1 + 3 * 0.044715 x^2)
-__device__ __forceinline__ float gelu_new_grad_fast(float x) {
-    const float x2 = x * x;
-    const float u = x * (1.0f + 0.044715f * x2);
-    const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.302208198f * u));
-    return sg + 2.0f * x * sg * (1.0f - sg) * 0.7978845608028654f * (1.0f + 0.134145f * x2);
-}
-__device__ __forceinline__ float apply_act_fast(float v, int act) {
-    if (act == RGRG_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RGRG_ACT_GELU_NEW) return gelu_new_fast(v);
-    return v;
-}
-
 // the LDS-DMA requests of one wave for one K tile: LA + LB wave instructions of 1 KiB (8 tile rows x 128 B); instruction
 // j of wave w covers the rows (j * 4 + w) * 8 .. + 8 of its operand.
 // (TAG: one specialization per calling kernel - hipcc's host-side pass rejects a second kernel template that reuses an
@@ -379,16 +325,6 @@ __device__ __forceinline__ void glds_compute(const unsigned char* sa, const unsi
     __builtin_amdgcn_sched_group_barrier(0x008, MI * NI, 0);
 }
 
-// The activation of a consumer epilogue.  CACT = RGRG_ACT_NONE / RGRG_ACT_GELU_NEW: known at compile time; -1: the run-time
-// switch on p.act (hipcc does not hoist it out of the element loop although p.act is uniform: ~5 scalar compare-and-branch
-// pairs per element).  Same arithmetic either way.
-template <int CACT>
-__device__ __forceinline__ float cons_act(float v, int act) {
-    if constexpr (CACT == RGRG_ACT_NONE) return v;
-    else if constexpr (CACT == RGRG_ACT_GELU_NEW) return gelu_new_fast(v);
-    else return apply_act_fast(v, act);
-}
-
 // CONV: the A operand is the im2col view of an NHWC bf16 image - row m of a K tile = 64 channels [c0, c0 + 64) of input pixel
 // (oy * stride + kh - pad, ox * stride + kw - pad): still one contiguous 128-byte line per row, so the LDS-DMA path is
 // unchanged; only the per-lane source offset is recomputed per K tile (tap = kt * 64 / Cin, a handful of integer
@@ -415,21 +351,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int ks = (!CONV && p.ksplit > 1) ? p.ksplit : 1;   // K slices per output tile (consecutive workgroup ids: one XCD)
-    int t = blockIdx.x;
-    {
-        const int total = mtiles * ntiles * ks, q = total >> 3, r = total & 7, x = t & 7, i = t >> 3;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int t = xcd_band_tile(blockIdx.x, mtiles * ntiles * ks);
     const int slice = t % ks, tile = t / ks;
-    t = tile;
-    int tn, tm;
-    if (p.gm <= 0 || p.gm >= mtiles) {
-        tn = t / mtiles; tm = t - tn * mtiles;
-    } else {   // grouped order (GemmBf16Params::gm): all groups but the last hold gm row tiles
-        const int gsz = p.gm * ntiles, g = t / gsz, r = t - g * gsz;
-        const int rows = min(p.gm, mtiles - g * p.gm);
-        tn = r / rows; tm = g * p.gm + (r - tn * rows);
-    }
+    const int2 tmn = grouped_tile(tile, p.gm, mtiles, ntiles);
+    const int tm = tmn.x, tn = tmn.y;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nk = p.K / BK / ks;          // K tiles of this slice (the launcher checks divisibility and nk >= NST - 1)
     const int lda = p.lda ? p.lda : p.K, ldw = p.ldw ? p.ldw : p.K;
@@ -450,16 +375,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
             cy0[j] = oy * p.cStride - p.cPad;
             cx0[j] = ox * p.cStride - p.cPad;
             cpix[j] = b * p.cH * p.cW;
-            cswz[j] = (lch ^ ((row >> 1) & 7)) << 4;
+            cswz[j] = dma_swizzle(row, lch);
             va[j] = 0;
         } else {
-            va[j] = min(row, p.M - 1 - m0) * lda * 2 + ((lch ^ ((row >> 1) & 7)) << 4);
+            va[j] = dma_src_off(row, p.M - 1 - m0, lda, lch);
         }
     }
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
         const int row = (j * 4 + wave) * 8 + lrow;
-        vb[j] = min(row, p.N - 1 - n0) * ldw * 2 + ((lch ^ ((row >> 1) & 7)) << 4);
+        vb[j] = dma_src_off(row, p.N - 1 - n0, ldw, lch);
     }
 #define RGRG_GLDS_ISSUE(STAGE_, KT_)                                                                                   \
     {                                                                                                                  \
@@ -477,19 +402,13 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
                                             (KT_) * (BK * 2));                                                         \
         }                                                                                                              \
     }
-    // fragment read offsets: lane -> (row = lane & 31, k half = lane >> 5) of a 32-row block; 4 K steps of 16
-    const int frow = lane & 31, fh = lane >> 5, fsw = (frow >> 1) & 7;
+    const int frow = lane & 31, fh = lane >> 5;
     int foff[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) foff[ks] = frow * 128 + (((2 * ks + fh) ^ fsw) << 4);
+    for (int ks = 0; ks < 4; ++ks) foff[ks] = frag_offset(frow, fh, ks);
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    zero_acc(acc);
 
     // Epilogue operands requested NOW, ahead of the operand stream: the per-column shift of every block and - for a 64 x 64
     // tile, where it is 16 registers - the fp32 residual of this lane's outputs.  Loaded in the epilogue they add a cold
@@ -515,10 +434,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
             const int colc = min(n0 + wn * (BN / 2) + ccol, p.N - 1);
             const int rbase = m0 + wm * (BM / 2) + crow4;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                rv_pre[r] = p.R[(size_t)row * p.ldy + colc];
-            }
+            for (int r = 0; r < 16; ++r) rv_pre[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
         }
     }
 
@@ -619,22 +535,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
     // waves), from where the epilogue fetches the 16 rows of its C layout
     float2* row_stat = reinterpret_cast<float2*>(glds_smem + NST * STAGE);   // [BM]
     if constexpr (CONS) {
-        // ONE summation order for every tile shape (a row's result must not depend on the tile the launcher picks for M): the 16
-        // slots are added in groups of four (slot order, from zero), the groups pairwise: (G0 + G1) + (G2 + G3).  64-row tiles:
-        // a thread owns one group, the butterfly below adds them; 128-row tiles: a thread owns two groups and adds them first.
-        static_assert(PER == 4 || PER == 8, "slot reduction is written for 64- and 128-row tiles");
-        float ls1 = 0.f, ls2 = 0.f;
-#pragma unroll
-        for (int j0 = 0; j0 < PER / 2; j0 += 2) {
-            float g1 = 0.f, g2 = 0.f;
-#pragma unroll
-            for (int j = j0; j < j0 + 2; ++j) { g1 += lsq[j][0]; g2 += lsq[j][1]; g1 += lsq[j][2]; g2 += lsq[j][3]; }
-            if (j0 == 0) { ls1 = g1; ls2 = g2; } else { ls1 += g1; ls2 += g2; }
-        }
-#pragma unroll
-        for (int o = 1; o < TPR; o <<= 1) { ls1 += __shfl_xor(ls1, o, 64); ls2 += __shfl_xor(ls2, o, 64); }
-        const float mean = ls1 * (1.0f / 1024.0f);
-        const float var = fmaxf(ls2 * (1.0f / 1024.0f) - mean * mean, 0.f);
+        // ONE summation order for every tile shape and kernel: ln_slot_sums
+        const float2 ls = ln_slot_sums<TPR, PER>(lsq);
+        const float mean = ln_mean(ls.x), var = ln_var(ls.y, mean);
         if (tid % TPR == 0) row_stat[tid / TPR] = make_float2(mean, 1.0f / sqrtf(var + LN_EPS16));
         __syncthreads();
     }
@@ -657,17 +560,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
             for (int r = 0; r < 16; ++r) rv[r] = rv_pre[r];   // 64 x 64 tiles: the residual prefetched above (zeros otherwise)
             if (!PRE_R && !CONS && p.R) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                    rv[r] = p.R[(size_t)row * p.ldy + colc];
-                }
+                for (int r = 0; r < 16; ++r) rv[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
             }
             if (!CONS && p.R16) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                    rv[r] = from16<F16>(p.R16[(size_t)row * p.ldy + colc]);
-                }
+                for (int r = 0; r < 16; ++r) rv[r] = c_load_16<F16>(p.R16, rbase, r, colc, p.M, p.ldy);
             }
             float vv[16];
             if constexpr (CONS) {
@@ -675,26 +572,20 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
                 const int lrow0 = wm * (BM / 2) + mi * 32 + crow4;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float2 st = row_stat[lrow0 + (r & 3) + 8 * (r >> 2)];
+                    const float2 st = row_stat[c_row(r, lrow0)];
                     vv[r] = cons_act<CACT>(st.y * (acc[mi][ni][r] - st.x * cs) + sh + rv[r], p.act);
                 }
             } else if constexpr (LNF == 0 && !CONV) {
                 if (p.G16) {   // dgrad through gelu_new: the result times gelu_new'(saved pre-activation)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                        rv[r] = from16<F16>(p.G16[(size_t)row * p.ldy + colc]);
-                    }
+                    for (int r = 0; r < 16; ++r) rv[r] = c_load_16<F16>(p.G16, rbase, r, colc, p.M, p.ldy);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) vv[r] = (acc[mi][ni][r] + sh) * gelu_new_grad_fast(rv[r]);
                 } else {
                     if (p.Ypre16 && col < p.N) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int dr = (r & 3) + 8 * (r >> 2);
-                            if (rbase + dr < p.M)
-                                p.Ypre16[(size_t)rbase * p.ldy + col + (size_t)(dr * p.ldy)] = (u16)to16<F16>(acc[mi][ni][r] + sh + rv[r]);
-                        }
+                        for (int r = 0; r < 16; ++r)
+                            if (rbase + c_row(r) < p.M) p.Ypre16[c_offset(rbase, r, col, p.ldy)] = (u16)to16<F16>(acc[mi][ni][r] + sh + rv[r]);
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) vv[r] = apply_act_fast(acc[mi][ni][r] + sh + rv[r], p.act);
@@ -714,75 +605,33 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
                 if (kv_slot < p.kv_T) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = rbase + (r & 3) + 8 * (r >> 2);
+                        const int row = c_row(r, rbase);
                         if (row < p.M) plane[(size_t)row * p.kv_H * p.kv_T * 64 + o0] = (u16)to16<F16>(vv[r]);
                     }
                 }
             } else if (col < p.N) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dr = (r & 3) + 8 * (r >> 2);
-                    const float v = vv[r];
-                    if (rbase + dr < p.M) {
-                        const size_t o = (size_t)rbase * p.ldy + col + (size_t)(dr * p.ldy);
-                        if (p.Y16) p.Y16[o] = (u16)to16<F16>(v);
-                        else if (p.N > 8192) __builtin_nontemporal_store(v, &p.Y[o]);  // logits: streamed, keep A / W in L2
-                        else p.Y[o] = v;
-                        if constexpr (LNF == 1) p.Yb16[o] = (u16)to16<F16>(v);
-                    }
-                }
+                for (int r = 0; r < 16; ++r)
+                    if (rbase + c_row(r) < p.M) c_store<F16, true, LNF == 1>(c_offset(rbase, r, col, p.ldy), vv[r], p.Y16, p.N, p.Y, p.Yb16);
             }
             if constexpr (LNF == 1) {
-                // per-row (sum, sum of squares) of this 32-column block: a halving butterfly over the 32 lanes that share the
-                // block's rows (16 -> 8 -> 4 -> 2 -> 1 rows per lane, then the pair), fixed order.  (Written with constant
-                // steps: as nested loops hipcc kept the arrays indexed dynamically - ~900 v_cndmask, 1.5 us per launch.)
-                float a1[16], a2[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { a1[r] = vv[r]; a2[r] = vv[r] * vv[r]; }
-#define RGRG_BFLY(H, BIT)                                                                         \
-                {                                                                                         \
-                    const bool up = (lane & (BIT)) != 0;                                                  \
-                    _Pragma("unroll") for (int i = 0; i < (H); ++i) {                                     \
-                        const float s1 = up ? a1[i] : a1[i + (H)], s2 = up ? a2[i] : a2[i + (H)];         \
-                        const float k1 = up ? a1[i + (H)] : a1[i], k2 = up ? a2[i + (H)] : a2[i];         \
-                        a1[i] = k1 + __shfl_xor(s1, (BIT), 64);                                           \
-                        a2[i] = k2 + __shfl_xor(s2, (BIT), 64);                                           \
-                    }                                                                                     \
-                }
-                RGRG_BFLY(8, 16) RGRG_BFLY(4, 8) RGRG_BFLY(2, 4) RGRG_BFLY(1, 2)
-#undef RGRG_BFLY
-                a1[0] += __shfl_xor(a1[0], 1, 64);
-                a2[0] += __shfl_xor(a2[0], 1, 64);
-                // lane L (and L ^ 1) now holds row (L >> 1) & 15 of its half of the block; blocks of one row block add up in ni order
-                blk1[mi] += a1[0];
-                blk2[mi] += a2[0];
+                // per-row (sum, sum of squares) of this 32-column block; blocks of one row block add up in ni order
+                const float2 bs = ln_block_row_sums(vv, lane);
+                blk1[mi] += bs.x;
+                blk2[mi] += bs.y;
             }
         }
     if constexpr (LNF == 1) {
         // one slot per 64 columns: a 128-wide tile's wave already covers 64 (its two blocks were added above); in a 64-wide tile
         // the two waves of a row block each hold 32 columns and meet in LDS (behind the stages), wn = 0 adds and stores
         float2* xch = reinterpret_cast<float2*>(glds_smem + NST * STAGE);   // [4 waves][MI][32 rows]
-        const int r = (lane >> 1) & 15, lrow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int lrow = ln_block_sum_row(lane);
         if constexpr (NI == 1) {
-            if (wn == 1 && !(lane & 1)) {
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) xch[(wave * MI + mi) * 32 + lrow] = make_float2(blk1[mi], blk2[mi]);
-            }
+            if (wn == 1 && !(lane & 1)) ln_stats_hand_over<MI>(xch, wave, lrow, blk1, blk2);
             __syncthreads();
         }
-        if (!(lane & 1) && (NI == 2 || wn == 0)) {
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                float s1 = blk1[mi], s2 = blk2[mi];
-                if constexpr (NI == 1) {
-                    const float2 o = xch[((wave + 1) * MI + mi) * 32 + lrow];
-                    s1 += o.x; s2 += o.y;
-                }
-                const int row = m0 + wm * (BM / 2) + mi * 32 + lrow;
-                const int slot = NI == 2 ? (n0 + wn * 64) / 64 : n0 / 64;
-                if (row < p.M) *reinterpret_cast<float2*>(p.stats_out + ((size_t)row * 16 + slot) * 2) = make_float2(s1, s2);
-            }
-        }
+        if (!(lane & 1) && (NI == 2 || wn == 0))
+            ln_stats_store<MI, NI>(xch, wave, lrow, blk1, blk2, m0 + wm * (BM / 2), NI == 2 ? (n0 + wn * 64) / 64 : n0 / 64, p.M, p.stats_out);
     }
 }
 
@@ -814,7 +663,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const GemmBf16Param
 //         4kt + 3           group 1   A-lo[64:128] of kt + 2                    W[128:256] of kt + 2
 //     A reading wave issues its 2 or 6 requests behind its ds_reads and then waits `vmcnt(8)`: all but its requests of this and
 //     of its previous reading slot have landed (loads return in order); `lgkmcnt(0)` before the barrier frees the rows it read;
-//   * tile order as in the kernel above (XCD bands, grouped rows); shift, residual, activation, 16-bit outputs, gelu' multiplier.
+//   * tile order: xcd_band_tile / grouped_tile (XCD bands, grouped rows); shift, residual, activation, 16-bit outputs, gelu' multiplier.
 //     No LayerNorm fold, no convolution (the callers of those shapes have few row tiles).
 template <int TAG>
 __device__ __forceinline__ void pp_dma4(const u16* base, unsigned char* dst, const int (&v)[4], int soff) {
@@ -837,27 +686,16 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmBf16Params 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 2, wq = wave & 3;
-    int t = blockIdx.x;
-    {
-        const int total = mtiles * ntiles, q = total >> 3, r = total & 7, x = t & 7, i = t >> 3;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    int tn, tm;
-    if (p.gm <= 0 || p.gm >= mtiles) {
-        tn = t / mtiles; tm = t - tn * mtiles;
-    } else {
-        const int gsz = p.gm * ntiles, gi = t / gsz, r = t - gi * gsz;
-        const int rows = min(p.gm, mtiles - gi * p.gm);
-        tn = r / rows; tm = gi * p.gm + (r - tn * rows);
-    }
+    const int2 tmn = grouped_tile(xcd_band_tile(blockIdx.x, mtiles * ntiles), p.gm, mtiles, ntiles);
+    const int tm = tmn.x, tn = tmn.y;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nk = p.K / BK;
     const int lda = p.lda ? p.lda : p.K, ldw = p.ldw ? p.ldw : p.K;
     const u16* abase = p.A16 + (size_t)m0 * lda;
     const u16* wbase = p.Wb + (size_t)n0 * ldw;
     const int lrow = lane >> 3, lch = lane & 7;
-    // per-lane source offset (bytes) of the 8 tile rows [row0, row0 + 8) of an operand: row clamp + XOR-swizzled 16-byte chunk
-    auto src_off = [&](int row0, int limit, int ld) { const int row = row0 + lrow; return min(row, limit) * ld * 2 + ((lch ^ ((row >> 1) & 7)) << 4); };
+    // per-lane source offset (bytes) of the 8 tile rows [row0, row0 + 8) of an operand
+    auto src_off = [&](int row0, int limit, int ld) { return dma_src_off(row0 + lrow, limit, ld, lch); };
     // steady state (table above): in its first reading slot of a K tile a wave refills 16 rows of one A unit, in its second
     // 16 rows of another A unit and 16 rows of each of two 64-row W units
     const int ra0 = (g == 0 ? 192 : 0) + wq * 16, ra1 = (g == 0 ? 128 : 64) + wq * 16;
@@ -870,11 +708,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmBf16Params 
     unsigned char* const da1 = pp_smem + ra1 * 128;
     unsigned char* const dw0 = pp_smem + WOFF + rw0 * 128;
     unsigned char* const dw1 = pp_smem + WOFF + rw1 * 128;
-    // fragment reads: lane -> (row = lane & 31, k half = lane >> 5) of a 32-row block, 4 K steps of 16 per tile
-    const int frow = lane & 31, fh = lane >> 5, fsw = (frow >> 1) & 7;
+    const int frow = lane & 31, fh = lane >> 5;
     int foff[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) foff[ks] = frow * 128 + (((2 * ks + fh) ^ fsw) << 4);
+    for (int ks = 0; ks < 4; ++ks) foff[ks] = frag_offset(frow, fh, ks);
     const unsigned char* const fa_base = pp_smem + g * (128 * 128);
     const unsigned char* const fb_base = pp_smem + WOFF + wq * (64 * 128);
 
@@ -896,7 +733,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmBf16Params 
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) { fa[ks][i] = bf16x8{1, 2, 3, 4, 5, 6, 7, 8}; fb[ks][i] = bf16x8{8, 7, 6, 5, 4, 3, 2, 1}; }
+            for (int i = 0; i < 2; ++i) { fa[ks][i] = dbg_frag_a(); fb[ks][i] = dbg_frag_b(); }
     }
 
 #define PP_READ_A(ST_, H_)                                                                                       \
@@ -1091,6 +928,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const GemmBf16Params 
         }
         return;
     }
+    // (This kernel's accumulator zeroing and epilogue keep their own text - the C-layout rows, the gathers, the offsets, the
+    // stores: through the helpers of gemm_bf16_device.h the kernel got another schedule (1 SGPR less, 1 VGPR more) and FAILED the
+    // time check: lm_head at 923 rows 154.1 us against 149.7 - 151.4 for the parent, profiles/gemm_shared_epilogue.md section 4.)
     // epilogue straight from the C layout of the 32x32 MFMA (register r of block (mi, ni) = column lane & 31, row
     // (r & 3) + 8 (r >> 2) + 4 (lane >> 5)): a store instruction writes two rows x 128 contiguous bytes (fp32).  Measured
     // against two alternatives on the store-heavy shapes (c_attn / lm_head at 14 848 rows: 182 MB / 3 GB of fp32 output,
@@ -1182,32 +1022,93 @@ static int bf16_attr() {
     return RGRG_OK;
 }
 
-template <int BM, int BN, int NST>
-static int glds_attr() {
-    constexpr int lds = NST * (BM + BN) * 128 + BM * 16;
-#define RGRG_G_ATTR(...) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_glds_kernel<BM, BN, NST, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    RGRG_G_ATTR(false, false, 0); RGRG_G_ATTR(true, false, 0); RGRG_G_ATTR(false, true, 0); RGRG_G_ATTR(true, true, 0);
-    RGRG_G_ATTR(false, false, 1); RGRG_G_ATTR(false, true, 1); RGRG_G_ATTR(false, false, 2); RGRG_G_ATTR(false, true, 2);
-    RGRG_G_ATTR(false, false, 3); RGRG_G_ATTR(false, true, 3);
-    if constexpr (BM == 64 && BN == 64) {   // the consumers with a compile-time activation (launch_glds_cfg)
-        RGRG_G_ATTR(false, false, 2, RGRG_ACT_NONE); RGRG_G_ATTR(false, true, 2, RGRG_ACT_NONE);
-        RGRG_G_ATTR(false, false, 2, RGRG_ACT_GELU_NEW); RGRG_G_ATTR(false, true, 2, RGRG_ACT_GELU_NEW);
-        RGRG_G_ATTR(false, false, 3, RGRG_ACT_NONE); RGRG_G_ATTR(false, true, 3, RGRG_ACT_NONE);
-    }
-#undef RGRG_G_ATTR
+// RGRG_GEMM_GM: row tiles per group of the tile order (GemmBf16Params::gm); unset = 8 when there are more than 16 row tiles,
+// -1 = column-major order always (the round-3/4 order; A/B runs of tools/gemm_bf16_bench.py)
+static int gemm_gm_override() {
+    static const int v = [] { const char* e = getenv("RGRG_GEMM_GM"); return e ? atoi(e) : 0; }();
+    return v;
+}
+// the gm of a launch that does not set one: the override, or groups of 8 row tiles when there are more than `threshold`
+static int default_gm(int mtiles, int threshold) {
+    const int o = gemm_gm_override();
+    return o < 0 ? 0 : o > 0 ? o : (mtiles > threshold ? 8 : 0);
+}
+// RGRG_PP_DBG (GemmBf16Params::dbg), read at every launch: tests and A/B tools switch it inside one process
+static int pp_dbg_env() {
+    const char* e = getenv("RGRG_PP_DBG");
+    return e ? atoi(e) : 0;
+}
+
+// The run-time variant of a launch.  Every kernel family (LDS-DMA, K-parity, row-split, 256 x 256 ping-pong) has ONE function
+// GemmVariant -> kernel address (null: not instantiated), the only place that names the family's instantiations:
+// init_gemm_bf16_attrs walks it over every variant (set_dynamic_lds), a launcher calls it once (launch_variant) - a kernel
+// that can be launched cannot be missing from the attribute setup.
+typedef void (*gemm_kernel_t)(const GemmBf16Params, const int, const int);
+struct GemmVariant {
+    bool f16 = false;    // the 16-bit type (GemmBf16Params::f16)
+    bool conv = false;   // implicit-GEMM convolution
+    int lnf = 0;         // LayerNorm fold: 0 plain, 1 producer, 2 consumer, 3 consumer with the K/V-cache epilogue
+    int cact = -1;       // the consumer's activation as a compile-time constant (cons_act), -1 = p.act
+    bool wide = false;   // K-parity 64 x 64 producer: the epilogue staged in LDS
+};
+typedef gemm_kernel_t (*gemm_variant_fn)(const GemmVariant&);
+static int set_dynamic_lds(gemm_variant_fn kernel_of, int lds) {
+    for (int f16 = 0; f16 < 2; ++f16)
+        for (int conv = 0; conv < 2; ++conv)
+            for (int lnf = 0; lnf < 4; ++lnf)
+                for (int cact : {-1, RGRG_ACT_NONE, RGRG_ACT_GELU_NEW})
+                    for (int wide = 0; wide < 2; ++wide) {
+                        const gemm_kernel_t k = kernel_of(GemmVariant{f16 != 0, conv != 0, lnf, cact, wide != 0});
+                        if (k) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                    }
     return RGRG_OK;
 }
+static int launch_variant(gemm_kernel_t k, int grid, int threads, int lds, const GemmBf16Params& p, int mtiles, int ntiles, hipStream_t st) {
+    if (!k) { set_error("bf16 GEMM: this variant of the kernel is not instantiated"); return RGRG_EINVAL; }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, st, p, mtiles, ntiles);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+template <int BM, int BN, int NST>
+static gemm_kernel_t glds_kernel(const GemmVariant& v) {
+#define RGRG_G_KERNEL(CONV_, ...) \
+    (v.f16 ? gemm_bf16_glds_kernel<BM, BN, NST, CONV_, true, __VA_ARGS__> : gemm_bf16_glds_kernel<BM, BN, NST, CONV_, false, __VA_ARGS__>)
+    if (v.wide) return nullptr;
+    if (v.cact != -1) {   // the consumers with a compile-time activation (launch_glds_cfg): 64 x 64 tile only
+        if constexpr (BM == 64 && BN == 64) {
+            if (!v.conv && v.lnf == 2 && v.cact == RGRG_ACT_NONE) return RGRG_G_KERNEL(false, 2, RGRG_ACT_NONE);
+            if (!v.conv && v.lnf == 2 && v.cact == RGRG_ACT_GELU_NEW) return RGRG_G_KERNEL(false, 2, RGRG_ACT_GELU_NEW);
+            if (!v.conv && v.lnf == 3 && v.cact == RGRG_ACT_NONE) return RGRG_G_KERNEL(false, 3, RGRG_ACT_NONE);
+        }
+        return nullptr;
+    }
+    if (v.conv) return v.lnf == 0 ? RGRG_G_KERNEL(true, 0) : nullptr;
+    switch (v.lnf) {
+        case 0: return RGRG_G_KERNEL(false, 0);
+        case 1: return RGRG_G_KERNEL(false, 1);
+        case 2: return RGRG_G_KERNEL(false, 2);
+        case 3: return RGRG_G_KERNEL(false, 3);
+    }
+#undef RGRG_G_KERNEL
+    return nullptr;
+}
+template <int BM, int BN, int NST>
+constexpr int glds_lds() { return NST * (BM + BN) * 128 + BM * 16; }
 template <int BM, int BN>
 static int glds_attrs() {
     int rc;
-    if ((rc = glds_attr<BM, BN, 2>()) || (rc = glds_attr<BM, BN, 3>())) return rc;
-    return glds_attr<BM, BN, 4>();
+    if ((rc = set_dynamic_lds(glds_kernel<BM, BN, 2>, glds_lds<BM, BN, 2>())) || (rc = set_dynamic_lds(glds_kernel<BM, BN, 3>, glds_lds<BM, BN, 3>()))) return rc;
+    return set_dynamic_lds(glds_kernel<BM, BN, 4>, glds_lds<BM, BN, 4>());
 }
 
-static int gemm_gm_override();
 #include "gemm_kp.inc"
 
 constexpr int PP_LDS = 2 * (256 + 256) * 128;   // two stages of the 256 x 256 ping-pong kernel
+static gemm_kernel_t pp_kernel(const GemmVariant& v) {
+    if (v.conv || v.lnf != 0 || v.cact != -1 || v.wide) return nullptr;
+    return v.f16 ? gemm_bf16_pp_kernel<true> : gemm_bf16_pp_kernel<false>;
+}
 
 int init_gemm_bf16_attrs() {
     static bool done = false;  // hipFuncSetAttribute is not capturable and not free: once per process
@@ -1215,18 +1116,10 @@ int init_gemm_bf16_attrs() {
     int rc;
     if ((rc = bf16_attr<128, 128, 512>()) || (rc = bf16_attr<64, 64, 256>())) return rc;
     if ((rc = glds_attrs<128, 128>()) || (rc = glds_attrs<64, 64>()) || (rc = glds_attrs<128, 64>()) || (rc = glds_attrs<64, 128>())) return rc;
-    RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS));
-    RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS));
-    if ((rc = kp_attr<128, 128, 2>()) || (rc = kp_attr<64, 64, 4>()) || (rc = kp_attr<64, 64, 3>()) || (rc = kp_attr<128, 64, 3>()) || (rc = kp_attr<64, 128, 3>()) || (rc = kp_attr<64, 64, 2>()) || (rc = pr_attrs())) return rc;
+    if ((rc = set_dynamic_lds(pp_kernel, PP_LDS))) return rc;
+    if ((rc = kp_attr<128, 128, 2>()) || (rc = kp_attr<64, 64, 4>()) || (rc = kp_attr<64, 64, 3>()) || (rc = kp_attr<128, 64, 3>()) || (rc = kp_attr<64, 128, 3>()) || (rc = kp_attr<64, 64, 2>()) || (rc = set_dynamic_lds(pr_kernel, PR_LDS))) return rc;
     done = true;
     return RGRG_OK;
-}
-
-// RGRG_GEMM_GM: row tiles per group of the tile order (GemmBf16Params::gm); unset = 8 when there are more than 16 row tiles,
-// -1 = column-major order always (the round-3/4 order; A/B runs of tools/gemm_bf16_bench.py)
-static int gemm_gm_override() {
-    static const int v = [] { const char* e = getenv("RGRG_GEMM_GM"); return e ? atoi(e) : 0; }();
-    return v;
 }
 
 // RGRG_CONS_EPI, read per launch like RGRG_WIDE_EPI (A/B runs and tests compare the epilogues in one process): unset or 1 = a
@@ -1251,31 +1144,22 @@ template <int BM, int BN, int NST>
 static int launch_glds_cfg(const GemmBf16Params& p0, hipStream_t st) {
     GemmBf16Params p = p0;
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-    if (p.gm == 0) {
-        const int o = gemm_gm_override();
-        p.gm = o < 0 ? 0 : o > 0 ? o : (mtiles > 16 ? 8 : 0);
-    }
+    if (p.gm == 0) p.gm = default_gm(mtiles, 16);
     const int ks = (!p.cCin && p.ksplit > 1 && p.sk_ws && p.sk_cnt && (p.K / 64) % p.ksplit == 0 && p.K / 64 / p.ksplit >= NST - 1) ? p.ksplit : 1;
     p.ksplit = ks;
-#define RGRG_G_LAUNCH(...) hipLaunchKernelGGL((gemm_bf16_glds_kernel<BM, BN, NST, __VA_ARGS__>), dim3(mtiles * ntiles * ks), dim3(256), NST * (BM + BN) * 128 + BM * 16, st, p, mtiles, ntiles)
+    GemmVariant v;
+    v.f16 = p.f16 != 0;
     bool cons = false;
     if constexpr (BM == 64 && BN == 64) cons = cons_epi_enabled() && cons_epi_ok(p);
-    if (cons) {
+    if (cons) {   // cons_epi_ok: the activation is NONE or GELU_NEW (NONE with the K/V-cache epilogue)
         cons_epi_launches.fetch_add(1, std::memory_order_relaxed);
-        if constexpr (BM == 64 && BN == 64) {
-            if (p.kv_k) { if (p.f16) RGRG_G_LAUNCH(false, true, 3, RGRG_ACT_NONE); else RGRG_G_LAUNCH(false, false, 3, RGRG_ACT_NONE); }
-            else if (p.act == RGRG_ACT_NONE) { if (p.f16) RGRG_G_LAUNCH(false, true, 2, RGRG_ACT_NONE); else RGRG_G_LAUNCH(false, false, 2, RGRG_ACT_NONE); }
-            else { if (p.f16) RGRG_G_LAUNCH(false, true, 2, RGRG_ACT_GELU_NEW); else RGRG_G_LAUNCH(false, false, 2, RGRG_ACT_GELU_NEW); }
-        }
+        v.lnf = p.kv_k ? 3 : 2;
+        v.cact = p.act;
     }
-    else if (p.cCin) { if (p.f16) RGRG_G_LAUNCH(true, true, 0); else RGRG_G_LAUNCH(true, false, 0); }
-    else if (p.Yb16) { if (p.f16) RGRG_G_LAUNCH(false, true, 1); else RGRG_G_LAUNCH(false, false, 1); }
-    else if (p.ln_colsum && p.kv_k) { if (p.f16) RGRG_G_LAUNCH(false, true, 3); else RGRG_G_LAUNCH(false, false, 3); }
-    else if (p.ln_colsum) { if (p.f16) RGRG_G_LAUNCH(false, true, 2); else RGRG_G_LAUNCH(false, false, 2); }
-    else { if (p.f16) RGRG_G_LAUNCH(false, true, 0); else RGRG_G_LAUNCH(false, false, 0); }
-#undef RGRG_G_LAUNCH
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    else if (p.cCin) v.conv = true;
+    else if (p.Yb16) v.lnf = 1;
+    else if (p.ln_colsum) v.lnf = p.kv_k ? 3 : 2;
+    return launch_variant(glds_kernel<BM, BN, NST>(v), mtiles * ntiles * ks, 256, glds_lds<BM, BN, NST>(), p, mtiles, ntiles, st);
 }
 template <int BM, int BN>
 static int launch_glds_nst(const GemmBf16Params& p, int nst, hipStream_t st) {
@@ -1291,15 +1175,11 @@ static bool pp_eligible(const GemmBf16Params& p) {
 static int launch_pp(const GemmBf16Params& p0, hipStream_t st) {
     GemmBf16Params p = p0;
     const int mtiles = (p.M + 255) / 256, ntiles = (p.N + 255) / 256;
-    if (p.gm == 0) {
-        const int o = gemm_gm_override();
-        p.gm = o < 0 ? 0 : o > 0 ? o : (mtiles > 8 ? 8 : 0);
-    }
-    { const char* e = getenv("RGRG_PP_DBG"); p.dbg = e ? atoi(e) : 0; }
-    if (p.f16) hipLaunchKernelGGL(gemm_bf16_pp_kernel<true>, dim3(mtiles * ntiles), dim3(512), PP_LDS, st, p, mtiles, ntiles);
-    else hipLaunchKernelGGL(gemm_bf16_pp_kernel<false>, dim3(mtiles * ntiles), dim3(512), PP_LDS, st, p, mtiles, ntiles);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    if (p.gm == 0) p.gm = default_gm(mtiles, 8);
+    p.dbg = pp_dbg_env();
+    GemmVariant v;
+    v.f16 = p.f16 != 0;
+    return launch_variant(pp_kernel(v), mtiles * ntiles, 512, PP_LDS, p, mtiles, ntiles, st);
 }
 // RGRG_GEMM_PP=0: never pick the ping-pong kernel (A/B runs)
 static bool pp_enabled() {

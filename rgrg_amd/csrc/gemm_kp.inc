@@ -65,19 +65,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 2, w4 = wave & 3;
     const int wm = w4 >> 1, wn = w4 & 1;
-    int t = blockIdx.x;
-    {
-        const int total = mtiles * ntiles, q = total >> 3, r = total & 7, x = t & 7, i = t >> 3;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    int tn, tm;
-    if (p.gm <= 0 || p.gm >= mtiles) {
-        tn = t / mtiles; tm = t - tn * mtiles;
-    } else {
-        const int gsz = p.gm * ntiles, gi = t / gsz, r = t - gi * gsz;
-        const int rows = min(p.gm, mtiles - gi * p.gm);
-        tn = r / rows; tm = gi * p.gm + (r - tn * rows);
-    }
+    const int2 tmn = grouped_tile(xcd_band_tile(blockIdx.x, mtiles * ntiles), p.gm, mtiles, ntiles);
+    const int tm = tmn.x, tn = tmn.y;
     const int m0 = tm * BM, n0 = tn * BN;
     const int n = p.K / (2 * BK);               // K tiles per group (the launcher checks K % 128 == 0 and n >= NST)
     const int lda = p.lda ? p.lda : p.K, ldw = p.ldw ? p.ldw : p.K;
@@ -89,28 +78,23 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
 #pragma unroll
     for (int j = 0; j < LA; ++j) {
         const int row = (j * 4 + w4) * 8 + lrow;
-        va[j] = min(row, p.M - 1 - m0) * lda * 2 + ((lch ^ ((row >> 1) & 7)) << 4);
+        va[j] = dma_src_off(row, p.M - 1 - m0, lda, lch);
     }
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
         const int row = (j * 4 + w4) * 8 + lrow;
-        vb[j] = min(row, p.N - 1 - n0) * ldw * 2 + ((lch ^ ((row >> 1) & 7)) << 4);
+        vb[j] = dma_src_off(row, p.N - 1 - n0, ldw, lch);
     }
     unsigned char* const gs = kp_smem + g * GROUP;
 #define KP_ISSUE(STAGE_, T_) \
     glds_issue<BM, LA, LB, TAG>(abase, wbase, gs + (STAGE_) * STAGE + w4 * 1024, va, vb, (T_) * (4 * BK), (T_) * (4 * BK))
-    const int frow = lane & 31, fh = lane >> 5, fsw = (frow >> 1) & 7;
+    const int frow = lane & 31, fh = lane >> 5;
     int foff[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) foff[ks] = frow * 128 + (((2 * ks + fh) ^ fsw) << 4);
+    for (int ks = 0; ks < 4; ++ks) foff[ks] = frag_offset(frow, fh, ks);
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    zero_acc(acc);
 
     // epilogue operands, requested ahead of the operand stream (the oldest loads: the counted waits below are unaffected).
     // Only group 0 uses them; group 1's waves request the same addresses (its twin wave's lines: L1 / L2 hits) so that no load
@@ -134,10 +118,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
             const int colc = min(n0 + wn * (BN / 2) + ccol, p.N - 1);
             const int rbase = m0 + wm * (BM / 2) + crow4;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                rv_pre[r] = p.R[(size_t)row * p.ldy + colc];
-            }
+            for (int r = 0; r < 16; ++r) rv_pre[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
         }
     }
     // WIDE: this thread's 32 bytes of the residual tile (the launcher checks R, N % 64 == 0 and the alignment)
@@ -163,9 +144,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
-            for (int i = 0; i < MI; ++i) fa[ks][i] = bf16x8{1, 2, 3, 4, 5, 6, 7, 8};
+            for (int i = 0; i < MI; ++i) fa[ks][i] = dbg_frag_a();
 #pragma unroll
-            for (int i = 0; i < NI; ++i) fb[ks][i] = bf16x8{8, 7, 6, 5, 4, 3, 2, 1};
+            for (int i = 0; i < NI; ++i) fb[ks][i] = dbg_frag_b();
         }
     }
 #define KP_READ(STAGE_)                                                                                              \
@@ -265,23 +246,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
     }
 
     if (dbg & 8) return;   // measurements only: no epilogue (nothing is written)
-    // ---- epilogue: group 0's four waves, as in gemm_bf16_glds_kernel (same formulas, same orders); the workgroup barriers are
-    // passed by all eight waves
+    // ---- epilogue: group 0's four waves, the formulas and orders of gemm_bf16_glds_kernel through the same helpers
+    // (gemm_bf16_device.h); the workgroup barriers are passed by all eight waves
     float2* row_stat = reinterpret_cast<float2*>(kp_smem + 2 * GROUP);   // [BM]
     if constexpr (LNF == 2) {
-        static_assert(PER == 4 || PER == 8, "slot reduction is written for 64- and 128-row tiles");
-        float ls1 = 0.f, ls2 = 0.f;
-#pragma unroll
-        for (int j0 = 0; j0 < PER / 2; j0 += 2) {
-            float g1 = 0.f, g2 = 0.f;
-#pragma unroll
-            for (int j = j0; j < j0 + 2; ++j) { g1 += lsq[j][0]; g2 += lsq[j][1]; g1 += lsq[j][2]; g2 += lsq[j][3]; }
-            if (j0 == 0) { ls1 = g1; ls2 = g2; } else { ls1 += g1; ls2 += g2; }
-        }
-#pragma unroll
-        for (int o = 1; o < TPR; o <<= 1) { ls1 += __shfl_xor(ls1, o, 64); ls2 += __shfl_xor(ls2, o, 64); }
-        const float mean = ls1 * (1.0f / 1024.0f);
-        const float var = fmaxf(ls2 * (1.0f / 1024.0f) - mean * mean, 0.f);
+        const float2 ls = ln_slot_sums<TPR, PER>(lsq);
+        const float mean = ln_mean(ls.x), var = ln_var(ls.y, mean);
         if (g == 0 && tid % TPR == 0) row_stat[tid / TPR] = make_float2(mean, 1.0f / sqrtf(var + LN_EPS16));
         __syncthreads();
     }
@@ -310,14 +280,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                 for (int r = 0; r < 16; ++r) rv[r] = rv_pre[r];
                 if constexpr (WIDE) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) rv[r] = wide_res[((r & 2) ? wide_e1 : wide_e0) + ((r & 3) + 8 * (r >> 2)) * 64];
+                    for (int r = 0; r < 16; ++r) rv[r] = wide_res[((r & 2) ? wide_e1 : wide_e0) + c_row(r) * 64];
                 }
                 if (!PRE_R && !WIDE && LNF != 2 && p.R) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                        rv[r] = p.R[(size_t)row * p.ldy + colc];
-                    }
+                    for (int r = 0; r < 16; ++r) rv[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
                 }
                 float vv[16];
                 if constexpr (LNF == 2) {
@@ -325,7 +292,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                     const int lrow0 = wm * (BM / 2) + mi * 32 + crow4;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const float2 st = row_stat[lrow0 + (r & 3) + 8 * (r >> 2)];
+                        const float2 st = row_stat[c_row(r, lrow0)];
                         vv[r] = apply_act_fast(st.y * (acc[mi][ni][r] - st.x * cs) + sh + rv[r], p.act);
                     }
                 } else if constexpr (WIDE) {   // no activation (the launcher checks): 16 scalar switches on p.act less
@@ -337,51 +304,24 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                 }
                 if constexpr (WIDE) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) wide_out[((r & 2) ? wide_e1 : wide_e0) + ((r & 3) + 8 * (r >> 2)) * 64] = vv[r];
+                    for (int r = 0; r < 16; ++r) wide_out[((r & 2) ? wide_e1 : wide_e0) + c_row(r) * 64] = vv[r];
                 } else if (col < p.N) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int dr = (r & 3) + 8 * (r >> 2);
-                        const float v = vv[r];
-                        if (rbase + dr < p.M) {
-                            const size_t o = (size_t)rbase * p.ldy + col + (size_t)(dr * p.ldy);
-                            if (p.Y16) p.Y16[o] = (u16)to16<F16>(v);
-                            else p.Y[o] = v;
-                            if constexpr (LNF == 1) p.Yb16[o] = (u16)to16<F16>(v);
-                        }
-                    }
+                    for (int r = 0; r < 16; ++r)
+                        if (rbase + c_row(r) < p.M) c_store<F16, false, LNF == 1>(c_offset(rbase, r, col, p.ldy), vv[r], p.Y16, p.N, p.Y, p.Yb16);
                 }
                 if constexpr (LNF == 1) {
-                    float a1[16], a2[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { a1[r] = vv[r]; a2[r] = vv[r] * vv[r]; }
-#define RGRG_BFLY(H, BIT)                                                                         \
-                    {                                                                                         \
-                        const bool up = (lane & (BIT)) != 0;                                                  \
-                        _Pragma("unroll") for (int i = 0; i < (H); ++i) {                                     \
-                            const float s1 = up ? a1[i] : a1[i + (H)], s2 = up ? a2[i] : a2[i + (H)];         \
-                            const float k1 = up ? a1[i + (H)] : a1[i], k2 = up ? a2[i + (H)] : a2[i];         \
-                            a1[i] = k1 + __shfl_xor(s1, (BIT), 64);                                           \
-                            a2[i] = k2 + __shfl_xor(s2, (BIT), 64);                                           \
-                        }                                                                                     \
-                    }
-                    RGRG_BFLY(8, 16) RGRG_BFLY(4, 8) RGRG_BFLY(2, 4) RGRG_BFLY(1, 2)
-#undef RGRG_BFLY
-                    a1[0] += __shfl_xor(a1[0], 1, 64);
-                    a2[0] += __shfl_xor(a2[0], 1, 64);
-                    blk1[mi] += a1[0];
-                    blk2[mi] += a2[0];
+                    const float2 bs = ln_block_row_sums(vv, lane);
+                    blk1[mi] += bs.x;
+                    blk2[mi] += bs.y;
                 }
             }
     }
     if constexpr (LNF == 1) {
         float2* xch = reinterpret_cast<float2*>(kp_smem + 2 * GROUP);   // [4 waves][MI][32 rows]
-        const int r = (lane >> 1) & 15, lrow_s = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int lrow_s = ln_block_sum_row(lane);
         if constexpr (NI == 1) {
-            if (g == 0 && wn == 1 && !(lane & 1)) {
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) xch[(w4 * MI + mi) * 32 + lrow_s] = make_float2(blk1[mi], blk2[mi]);
-            }
+            if (g == 0 && wn == 1 && !(lane & 1)) ln_stats_hand_over<MI>(xch, w4, lrow_s, blk1, blk2);
             __syncthreads();
         }
         if constexpr (WIDE) {   // all eight waves: whole rows of the finished tile, 8 columns per thread
@@ -400,31 +340,31 @@ __global__ __launch_bounds__(512) void gemm_bf16_kp_kernel(const GemmBf16Params 
                 *reinterpret_cast<u32x4*>(p.Yb16 + o) = h;
             }
         }
-        if (g == 0 && !(lane & 1) && (NI == 2 || wn == 0)) {
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                float s1 = blk1[mi], s2 = blk2[mi];
-                if constexpr (NI == 1) {
-                    const float2 o = xch[((w4 + 1) * MI + mi) * 32 + lrow_s];
-                    s1 += o.x; s2 += o.y;
-                }
-                const int row = m0 + wm * (BM / 2) + mi * 32 + lrow_s;
-                const int slot = NI == 2 ? (n0 + wn * 64) / 64 : n0 / 64;
-                if (row < p.M) *reinterpret_cast<float2*>(p.stats_out + ((size_t)row * 16 + slot) * 2) = make_float2(s1, s2);
-            }
-        }
+        if (g == 0 && !(lane & 1) && (NI == 2 || wn == 0))
+            ln_stats_store<MI, NI>(xch, w4, lrow_s, blk1, blk2, m0 + wm * (BM / 2), NI == 2 ? (n0 + wn * 64) / 64 : n0 / 64, p.M, p.stats_out);
     }
 }
 
 template <int BM, int BN, int NST>
-static int kp_attr() {
-    constexpr int lds = 2 * NST * (BM + BN) * 128 + BM * 16;
-#define RGRG_KP_ATTR(...) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kp_kernel<BM, BN, NST, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    RGRG_KP_ATTR(false, 0); RGRG_KP_ATTR(true, 0); RGRG_KP_ATTR(false, 1); RGRG_KP_ATTR(true, 1); RGRG_KP_ATTR(false, 2); RGRG_KP_ATTR(true, 2);
-    if constexpr (BM == 64 && BN == 64) { RGRG_KP_ATTR(false, 1, true); RGRG_KP_ATTR(true, 1, true); }
-#undef RGRG_KP_ATTR
-    return RGRG_OK;
+static gemm_kernel_t kp_kernel(const GemmVariant& v) {
+#define RGRG_KP_KERNEL(...) (v.f16 ? gemm_bf16_kp_kernel<BM, BN, NST, true, __VA_ARGS__> : gemm_bf16_kp_kernel<BM, BN, NST, false, __VA_ARGS__>)
+    if (v.conv || v.cact != -1) return nullptr;
+    if (v.wide) {
+        if constexpr (BM == 64 && BN == 64) { if (v.lnf == 1) return RGRG_KP_KERNEL(1, true); }
+        return nullptr;
+    }
+    switch (v.lnf) {
+        case 0: return RGRG_KP_KERNEL(0);
+        case 1: return RGRG_KP_KERNEL(1);
+        case 2: return RGRG_KP_KERNEL(2);
+    }
+#undef RGRG_KP_KERNEL
+    return nullptr;
 }
+template <int BM, int BN, int NST>
+constexpr int kp_lds() { return 2 * NST * (BM + BN) * 128 + BM * 16; }
+template <int BM, int BN, int NST>
+static int kp_attr() { return set_dynamic_lds(kp_kernel<BM, BN, NST>, kp_lds<BM, BN, NST>()); }
 
 // plain, producer (Yb16 + stats_out) or consumer (ln_stats + ln_colsum) of a folded LayerNorm; no convolution, no 16-bit
 // residual, no training epilogues, no split-K, no arg-max candidates
@@ -452,25 +392,18 @@ static int launch_kp_cfg(const GemmBf16Params& p0, hipStream_t st) {
     GemmBf16Params p = p0;
     if (!kp_eligible(p, NST)) { set_error("bf16 GEMM: the K-parity kernel does not take this variant"); return RGRG_EINVAL; }
     const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-    if (p.gm == 0) {
-        const int o = gemm_gm_override();
-        p.gm = o < 0 ? 0 : o > 0 ? o : (mtiles > 16 ? 8 : 0);
-    }
-    { const char* e = getenv("RGRG_PP_DBG"); p.dbg = e ? atoi(e) : 0; }
-    constexpr int lds = 2 * NST * (BM + BN) * 128 + BM * 16;
-#define RGRG_KP_LAUNCH(...) hipLaunchKernelGGL((gemm_bf16_kp_kernel<BM, BN, NST, __VA_ARGS__>), dim3(mtiles * ntiles), dim3(512), lds, st, p, mtiles, ntiles)
-    bool wide = false;
-    if constexpr (BM == 64 && BN == 64) wide = kp_wide_enabled() && kp_wide_ok(p);
-    if (wide) {
+    if (p.gm == 0) p.gm = default_gm(mtiles, 16);
+    p.dbg = pp_dbg_env();
+    GemmVariant v;
+    v.f16 = p.f16 != 0;
+    if constexpr (BM == 64 && BN == 64) v.wide = kp_wide_enabled() && kp_wide_ok(p);
+    if (v.wide) {
         kp_wide_launches.fetch_add(1, std::memory_order_relaxed);
-        if constexpr (BM == 64 && BN == 64) { if (p.f16) RGRG_KP_LAUNCH(true, 1, true); else RGRG_KP_LAUNCH(false, 1, true); }
+        v.lnf = 1;
     }
-    else if (p.Yb16) { if (p.f16) RGRG_KP_LAUNCH(true, 1); else RGRG_KP_LAUNCH(false, 1); }
-    else if (p.ln_colsum) { if (p.f16) RGRG_KP_LAUNCH(true, 2); else RGRG_KP_LAUNCH(false, 2); }
-    else { if (p.f16) RGRG_KP_LAUNCH(true, 0); else RGRG_KP_LAUNCH(false, 0); }
-#undef RGRG_KP_LAUNCH
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    else if (p.Yb16) v.lnf = 1;
+    else if (p.ln_colsum) v.lnf = 2;
+    return launch_variant(kp_kernel<BM, BN, NST>(v), mtiles * ntiles, 512, kp_lds<BM, BN, NST>(), p, mtiles, ntiles, st);
 }
 
 // the K-parity tile of a GEMM: a function of (N, K) only - never of M (a row's bits must not depend on the row range)
@@ -503,19 +436,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 2, wq = wave & 3;
-    int t = blockIdx.x;
-    {
-        const int total = mtiles * ntiles, q = total >> 3, r = total & 7, x = t & 7, i = t >> 3;
-        t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    int tn, tm;
-    if (p.gm <= 0 || p.gm >= mtiles) {
-        tn = t / mtiles; tm = t - tn * mtiles;
-    } else {
-        const int gsz = p.gm * ntiles, gi = t / gsz, r = t - gi * gsz;
-        const int rows = min(p.gm, mtiles - gi * p.gm);
-        tn = r / rows; tm = gi * p.gm + (r - tn * rows);
-    }
+    const int2 tmn = grouped_tile(xcd_band_tile(blockIdx.x, mtiles * ntiles), p.gm, mtiles, ntiles);
+    const int tm = tmn.x, tn = tmn.y;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nk = p.K / BK;                    // the launcher checks nk >= 4
     const int lda = p.lda ? p.lda : p.K, ldw = p.ldw ? p.ldw : p.K;
@@ -527,22 +449,19 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int row = (j * 4 + wq) * 8 + lrow;
-        vo[j] = min(row, olim) * old_ * 2 + ((lch ^ ((row >> 1) & 7)) << 4);
+        vo[j] = dma_src_off(row, olim, old_, lch);
     }
     unsigned char* const odst = pr_smem + (g == 0 ? WOFF : 0) + wq * 1024;
 #define PR_ISSUE(KT_) pr_dma4<TAG>(obase, odst + ((KT_) & 3) * STAGE, vo, (KT_) * (BK * 2))
-    const int frow = lane & 31, fh = lane >> 5, fsw = (frow >> 1) & 7;
+    const int frow = lane & 31, fh = lane >> 5;
     int foff[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) foff[ks] = frow * 128 + (((2 * ks + fh) ^ fsw) << 4);
+    for (int ks = 0; ks < 4; ++ks) foff[ks] = frag_offset(frow, fh, ks);
     const unsigned char* const fa_base = pr_smem + g * (64 * 128);
     const unsigned char* const fb_base = pr_smem + WOFF + wq * (32 * 128);
 
-    f32x16 acc[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
+    f32x16 acc[2][1];   // 2 x 1 blocks per wave
+    zero_acc(acc);
     // epilogue operands ahead of the operand stream
     const int ccol = lane & 31, crow4 = 4 * (lane >> 5);
     const int col = n0 + wq * 32 + ccol, colc = min(col, p.N - 1);
@@ -560,7 +479,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
     const int dbg = __builtin_amdgcn_readfirstlane(p.dbg);
     if (dbg) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { fa[ks][0] = fa[ks][1] = bf16x8{1, 2, 3, 4, 5, 6, 7, 8}; fb[ks] = bf16x8{8, 7, 6, 5, 4, 3, 2, 1}; }
+        for (int ks = 0; ks < 4; ++ks) { fa[ks][0] = fa[ks][1] = dbg_frag_a(); fb[ks] = dbg_frag_b(); }
     }
 #define PR_READ(KT_)                                                                                 \
     if (!(dbg & 1)) {                                                                                \
@@ -576,8 +495,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
     if (!(dbg & 4)) {                                                                                \
         __builtin_amdgcn_s_setprio(1);                                                               \
         _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                           \
-            acc[0] = mfma16<F16>(fa[ks][0], fb[ks], acc[0]);                                         \
-            acc[1] = mfma16<F16>(fa[ks][1], fb[ks], acc[1]);                                         \
+            acc[0][0] = mfma16<F16>(fa[ks][0], fb[ks], acc[0][0]);                                   \
+            acc[1][0] = mfma16<F16>(fa[ks][1], fb[ks], acc[1][0]);                                   \
         }                                                                                            \
         __builtin_amdgcn_s_setprio(0);                                                               \
     }
@@ -639,18 +558,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
 
     float2* row_stat = reinterpret_cast<float2*>(pr_smem + NST * STAGE);   // [128]
     if constexpr (LNF == 2) {
-        // the LDS-DMA kernel's order for 128-row tiles: a thread adds two groups of four slots, the pair of a row meets by shuffle
-        float ls1 = 0.f, ls2 = 0.f;
-#pragma unroll
-        for (int j0 = 0; j0 < 4; j0 += 2) {
-            float g1 = 0.f, g2 = 0.f;
-#pragma unroll
-            for (int j = j0; j < j0 + 2; ++j) { g1 += lsq[j][0]; g2 += lsq[j][1]; g1 += lsq[j][2]; g2 += lsq[j][3]; }
-            if (j0 == 0) { ls1 = g1; ls2 = g2; } else { ls1 += g1; ls2 += g2; }
-        }
-        ls1 += __shfl_xor(ls1, 1, 64); ls2 += __shfl_xor(ls2, 1, 64);
-        const float mean = ls1 * (1.0f / 1024.0f);
-        const float var = fmaxf(ls2 * (1.0f / 1024.0f) - mean * mean, 0.f);
+        // 128-row tile (ln_slot_sums): a thread adds two groups of four slots, the pair of a row meets by shuffle
+        const float2 ls = ln_slot_sums<2, 8>(lsq);
+        const float mean = ln_mean(ls.x), var = ln_var(ls.y, mean);
         if (tid < 256 && !(tid & 1)) row_stat[tid >> 1] = make_float2(mean, 1.0f / sqrtf(var + LN_EPS16));
         __syncthreads();
     }
@@ -663,41 +573,32 @@ __global__ __launch_bounds__(512) void gemm_bf16_pr_kernel(const GemmBf16Params 
         for (int r = 0; r < 16; ++r) rv[r] = 0.f;
         if (LNF != 2 && p.R) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = min(rbase + (r & 3) + 8 * (r >> 2), p.M - 1);
-                rv[r] = p.R[(size_t)row * p.ldy + colc];
-            }
+            for (int r = 0; r < 16; ++r) rv[r] = c_load_f32(p.R, rbase, r, colc, p.M, p.ldy);
         }
         if constexpr (LNF == 2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float2 st = row_stat[lrow0 + (r & 3) + 8 * (r >> 2)];
-                vv[r] = apply_act_fast(st.y * (acc[mi][r] - st.x * cs) + sh + rv[r], p.act);
+                const float2 st = row_stat[c_row(r, lrow0)];
+                vv[r] = apply_act_fast(st.y * (acc[mi][0][r] - st.x * cs) + sh + rv[r], p.act);
             }
         } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) vv[r] = apply_act_fast(acc[mi][r] + sh + rv[r], p.act);
+            for (int r = 0; r < 16; ++r) vv[r] = apply_act_fast(acc[mi][0][r] + sh + rv[r], p.act);
         }
         if (col < p.N) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int dr = (r & 3) + 8 * (r >> 2);
-                if (rbase + dr < p.M) {
-                    const size_t o = (size_t)rbase * p.ldy + col + (size_t)(dr * p.ldy);
-                    if (p.Y16) p.Y16[o] = (u16)to16<F16>(vv[r]);
-                    else p.Y[o] = vv[r];
-                }
-            }
+            for (int r = 0; r < 16; ++r)
+                if (rbase + c_row(r) < p.M) c_store<F16, false, false>(c_offset(rbase, r, col, p.ldy), vv[r], p.Y16, p.N, p.Y, p.Yb16);
         }
     }
 }
 
 constexpr int PR_LDS = 4 * (128 + 128) * 128 + 128 * 8;
-static int pr_attrs() {
-#define RGRG_PR_ATTR(...) RGRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pr_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, PR_LDS))
-    RGRG_PR_ATTR(false, 0); RGRG_PR_ATTR(true, 0); RGRG_PR_ATTR(false, 2); RGRG_PR_ATTR(true, 2);
-#undef RGRG_PR_ATTR
-    return RGRG_OK;
+static gemm_kernel_t pr_kernel(const GemmVariant& v) {
+    if (v.conv || v.cact != -1 || v.wide) return nullptr;
+    if (v.lnf == 0) return v.f16 ? gemm_bf16_pr_kernel<true, 0> : gemm_bf16_pr_kernel<false, 0>;
+    if (v.lnf == 2) return v.f16 ? gemm_bf16_pr_kernel<true, 2> : gemm_bf16_pr_kernel<false, 2>;
+    return nullptr;
 }
 static bool pr_eligible(const GemmBf16Params& p) {
     return !p.cCin && !p.R16 && !p.Ypre16 && !p.G16 && !p.cand_val && !p.Yb16 && p.ksplit <= 1 && p.K % 64 == 0 && p.K / 64 >= 4 && !(p.ln_colsum && p.R);
@@ -706,17 +607,12 @@ static int launch_pr(const GemmBf16Params& p0, hipStream_t st) {
     GemmBf16Params p = p0;
     if (!pr_eligible(p)) { set_error("bf16 GEMM: the row-split ping-pong kernel does not take this variant"); return RGRG_EINVAL; }
     const int mtiles = (p.M + 127) / 128, ntiles = (p.N + 127) / 128;
-    if (p.gm == 0) {
-        const int o = gemm_gm_override();
-        p.gm = o < 0 ? 0 : o > 0 ? o : (mtiles > 16 ? 8 : 0);
-    }
-    { const char* e = getenv("RGRG_PP_DBG"); p.dbg = e ? atoi(e) : 0; }
-#define RGRG_PR_LAUNCH(F16_, LNF_) hipLaunchKernelGGL((gemm_bf16_pr_kernel<F16_, LNF_>), dim3(mtiles * ntiles), dim3(512), PR_LDS, st, p, mtiles, ntiles)
-    if (p.ln_colsum) { if (p.f16) RGRG_PR_LAUNCH(true, 2); else RGRG_PR_LAUNCH(false, 2); }
-    else { if (p.f16) RGRG_PR_LAUNCH(true, 0); else RGRG_PR_LAUNCH(false, 0); }
-#undef RGRG_PR_LAUNCH
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    if (p.gm == 0) p.gm = default_gm(mtiles, 16);
+    p.dbg = pp_dbg_env();
+    GemmVariant v;
+    v.f16 = p.f16 != 0;
+    v.lnf = p.ln_colsum ? 2 : 0;
+    return launch_variant(pr_kernel(v), mtiles * ntiles, 512, PR_LDS, p, mtiles, ntiles, st);
 }
 
 // The tile of a many-sequence decode projection: a function of (N, K) only - never of M (a row's bits must not depend on the row
