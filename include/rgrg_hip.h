@@ -488,6 +488,16 @@ int rgrg_linear_bf16_f32(const uint16_t* A16, const uint16_t* Wb, const float* s
  * pitches lda / ldw in elements (0 = K). */
 int rgrg_debug_linear_bf16_tile(const uint16_t* A16, const uint16_t* Wb, const float* shift, const float* R, float* Y,
                                 int M, int N, int K, int ldy, int act, int tile, int lda, int ldw, int fp16, void* stream);
+/* Test hook: rgrg_conv2d_nhwc_bf16 on a forced configuration of the LDS-DMA kernel (tile = shape + 16 * stages as above).  Shapes
+ * 0 .. 4 only: no other kernel family has a convolution instantiation, every other shape is RGRG_EINVAL.  A K of fewer than
+ * stages - 1 tiles of 64 runs with 2 stages, as in every launch. */
+int rgrg_debug_conv2d_nhwc_bf16_tile(const uint16_t* X16, const uint16_t* Wb, const float* shift, const uint16_t* R16, float* Y,
+                                     uint16_t* Y16, int B, int H, int Wd, int Cin, int Cout, int KH, int KW, int stride,
+                                     int pad, int act, int fp16, int tile, void* stream);
+/* Test hook: the configuration (shape + 16 * stages, the 2-stage fall-back of a short K applied) the launcher's heuristic picks on
+ * the LDS-DMA kernel for a plain or convolution launch of M x N x K (convolution: M = B OH OW, N = Cout, K = KH KW Cin).  For a
+ * plain GEMM this is the choice before the 256 x 256 kernel takes the large shapes.  Launches nothing and needs no device. */
+int rgrg_debug_bf16_tile_choice(int M, int N, int K);
 /* Test / measurement hook for the 16-bit training pass (torch.autocast around the reference's training step,
  * src/full_model/train_full_model.py:172-237): the same GEMM on a forced tile (as above; 5 = the 256 x 256 ping-pong kernel
  * of the large shapes) with the training epilogues - Y (f32) or Y16 (16 bit) = act(A16 Wb^T + shift + R); Ypre16 (optional):

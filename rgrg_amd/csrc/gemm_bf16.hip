@@ -1192,6 +1192,28 @@ static bool pp_lm_head() {   // RGRG_GEMM_PP_LMHEAD=0: keep the decode lm_head o
     return v;
 }
 
+// The heuristic's configuration (shape + 16 * stages, the comment below) of the LDS-DMA kernel for a plain or conv launch of
+// (M, N, K): launch_glds and rgrg_debug_bf16_tile_choice both ask here.
+static int glds_auto_tile(int M, int N, int K) {
+    int shape, nst;
+    const long tiles_big = (long)((M + 127) / 128) * ((N + 127) / 128);
+    if (N <= 64) { shape = 3; nst = 2; }            // a 64-channel conv: no point in a 128-wide column tile
+    else if (tiles_big >= 512) { shape = 1; nst = 2; }   // >= one round of two workgroups per CU (round 5: was 1024 - the
+                                                          // M = 14 848 training GEMMs with N = 1024 ran on 64 x 64 tiles)
+    else if (K >= 8192 && tiles_big >= 192) { shape = 1; nst = 2; }   // fc6 at 8 images (6 650 x 1024 x 131 072): 2.1 ms, 64 x 64: 4.2
+    else if (K > 1024) { shape = 2; nst = 4; }
+    else if (tiles_big >= 256) { shape = 3; nst = 3; }
+    else if (tiles_big >= 128) { shape = 2; nst = 3; }
+    else { shape = 2; nst = 4; }
+    return shape + 16 * nst;
+}
+// The pipeline depth a launch runs with: 0 = 4, and 2 when K has fewer than stages - 1 tiles to prefetch
+static int glds_stages(int nst, int K) {
+    if (nst == 0) nst = 4;
+    if (K / 64 < nst - 1) nst = 2;
+    return nst;
+}
+
 // tile = shape + 16 * stages; shape: 0 = heuristic, 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 64x128, 5 = 256x256 ping-pong;
 // stages: 0 (= 4), 2, 3, 4
 // (tools/gemm_bf16_bench.py measures them).  Heuristic from the COLD-weights table at M = 923
@@ -1235,19 +1257,8 @@ static int launch_glds(const GemmBf16Params& p, int tile, hipStream_t st) {
         static const int o = [] { const char* e = getenv("RGRG_CONS_TILE_SMALLM"); return e ? atoi(e) : 0; }();
         if (o) { shape = o & 15; nst = o >> 4; }
     }
-    if (shape == 0) {
-        const long tiles_big = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-        if (p.N <= 64) { shape = 3; nst = 2; }            // a 64-channel conv: no point in a 128-wide column tile
-        else if (tiles_big >= 512) { shape = 1; nst = 2; }   // >= one round of two workgroups per CU (round 5: was 1024 - the
-                                                              // M = 14 848 training GEMMs with N = 1024 ran on 64 x 64 tiles)
-        else if (p.K >= 8192 && tiles_big >= 192) { shape = 1; nst = 2; }   // fc6 at 8 images (6 650 x 1024 x 131 072): 2.1 ms, 64 x 64: 4.2
-        else if (p.K > 1024) { shape = 2; nst = 4; }
-        else if (tiles_big >= 256) { shape = 3; nst = 3; }
-        else if (tiles_big >= 128) { shape = 2; nst = 3; }
-        else { shape = 2; nst = 4; }
-    }
-    if (nst == 0) nst = 4;
-    if (p.K / 64 < nst - 1) nst = 2;
+    if (shape == 0) { const int t = glds_auto_tile(p.M, p.N, p.K); shape = t & 15; nst = t >> 4; }
+    nst = glds_stages(nst, p.K);
     switch (shape) {
         case 1: return launch_glds_nst<128, 128>(p, nst, st);
         case 2: return launch_glds_nst<64, 64>(p, nst, st);
@@ -1441,9 +1452,9 @@ extern "C" int rgrg_debug_cons_epilogue_launches(void) { return cons_epi_launche
 //   X16 [B,H,W,Cin] bf16 NHWC with 128 zero elements in front of it (X16[-128 .. -1] == 0), Cin % 64 == 0
 //   Wb  [Cout][KH][KW][Cin] bf16 (BatchNorm scale folded in), shift [Cout] f32 (bias / folded BatchNorm shift) or NULL
 //   R16 [B,OH,OW,Cout] bf16 or NULL; exactly one of Y (f32) / Y16 (bf16) [B,OH,OW,Cout]
-extern "C" int rgrg_conv2d_nhwc_bf16(const uint16_t* X16, const uint16_t* Wb, const float* shift, const uint16_t* R16, float* Y,
-                                     uint16_t* Y16, int B, int H, int Wd, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                     int act, int fp16, void* stream) {
+static int conv2d_nhwc_bf16_tile(const uint16_t* X16, const uint16_t* Wb, const float* shift, const uint16_t* R16, float* Y,
+                                 uint16_t* Y16, int B, int H, int Wd, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                 int act, int fp16, int tile, void* stream) {
     int rc = init_gemm_bf16_attrs();
     if (rc) return rc;
     RGRG_CHECK_ARG(X16 && Wb && ((Y != nullptr) != (Y16 != nullptr)) && B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cin % 64 == 0);
@@ -1457,5 +1468,29 @@ extern "C" int rgrg_conv2d_nhwc_bf16(const uint16_t* X16, const uint16_t* Wb, co
     RGRG_CHECK_ARG(p.cOH > 0 && p.cOW > 0);
     p.M = B * p.cOH * p.cOW; p.N = Cout; p.K = KH * KW * Cin; p.ldy = Cout; p.act = act;
     RGRG_CHECK_ARG((size_t)128 * p.K * 2 < ((size_t)1 << 31));
-    return launch_glds(p, 0, as_stream(stream));
+    return launch_glds(p, tile, as_stream(stream));
+}
+
+extern "C" int rgrg_conv2d_nhwc_bf16(const uint16_t* X16, const uint16_t* Wb, const float* shift, const uint16_t* R16, float* Y,
+                                     uint16_t* Y16, int B, int H, int Wd, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                     int act, int fp16, void* stream) {
+    return conv2d_nhwc_bf16_tile(X16, Wb, shift, R16, Y, Y16, B, H, Wd, Cin, Cout, KH, KW, stride, pad, act, fp16, 0, stream);
+}
+
+// Test hook: the same convolution on a forced tile of the LDS-DMA kernel (tile = shape + 16 * stages as in
+// rgrg_debug_linear_bf16_tile; shapes 0 .. 4 only - no other kernel family has a CONV instantiation).
+extern "C" int rgrg_debug_conv2d_nhwc_bf16_tile(const uint16_t* X16, const uint16_t* Wb, const float* shift, const uint16_t* R16, float* Y,
+                                                uint16_t* Y16, int B, int H, int Wd, int Cin, int Cout, int KH, int KW, int stride,
+                                                int pad, int act, int fp16, int tile, void* stream) {
+    const int nst = tile >> 4;
+    RGRG_CHECK_ARG(tile >= 0 && (tile & 15) <= 4 && (nst == 0 || (nst >= 2 && nst <= 4)));
+    return conv2d_nhwc_bf16_tile(X16, Wb, shift, R16, Y, Y16, B, H, Wd, Cin, Cout, KH, KW, stride, pad, act, fp16, tile, stream);
+}
+
+// shape + 16 * stages that launch_glds picks for a plain or conv launch of (M, N, K) on the LDS-DMA kernel, the fall-back to
+// 2 stages of a short K included (plain launches: before the 256 x 256 kernel takes the large ones).  Launches nothing.
+extern "C" int rgrg_debug_bf16_tile_choice(int M, int N, int K) {
+    RGRG_CHECK_ARG(M > 0 && N > 0 && K > 0);
+    const int t = glds_auto_tile(M, N, K);
+    return (t & 15) + 16 * glds_stages(t >> 4, K);
 }
