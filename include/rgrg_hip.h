@@ -292,6 +292,55 @@ int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const float* feats,
                                             int S, int T, int num_beams, int num_beam_groups, float diversity_penalty, int max_length,
                                             int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids,
                                             int out_ld, int* out_len, void* stream);
+/* ---- Beam-search sampling (transformers' beam_sample; the reference's generate() refuses do_sample with num_beams > 1,
+ * LanguageModel.beam_sample is this build's own entry).  rgrg_decoder_beam_search whose ranking DRAWS the item's 2 num_beams
+ * candidates without replacement from the joint distribution over its num_beams x V continuations.  The order of operations is that
+ * of transformers' later releases: the row's log-probabilities are warped, THEN the beam score is added (4.19.2 warped the sum,
+ * which multiplies the running beam score by 1 / temperature at every step).  Contract of the ranking, for beam row r (item r / nb,
+ * beam j = r % nb) with fp32 logits x[0..V), beam_score[r], temperature > 0, top_k >= 0, 0 < top_p <= 1, a 64-bit seed and step t:
+ *   log-prob     lp_i = (x_i - max x) - log(sum exp(x - max x)), fp32, fixed summation order.
+ *   temperature  w_i = lp_i * inv_T, inv_T = 1.0f / temperature computed once on the host.
+ *   kept set     top-k, then top-p, exactly as in "Sampling" above, on x with inv_T (the softmax of w IS the softmax of x * inv_T),
+ *                with min_tokens_to_keep = 2 (transformers' rule for num_beams > 1): top_k = 1 acts as 2, and top-p always keeps
+ *                the two largest logits and everything tied with the second.  A -inf logit is never kept.  A row with two
+ *                finite logits therefore keeps >= 2 tokens and an item has >= 2 num_beams candidates.  NaN: outside the contract.
+ *   score        s_i = beam_score[r] + w_i for kept i, fp32, every operation rounded once.
+ *   noise        g_i = -log(-log u_i), u_i = ((word >> 8) + 0.5) * 2^-24 - a 25-bit dyadic number, used EXACTLY (never rounded to
+ *                fp32: below 1/2 it is an fp32 number, above it 1 - u_i is, and -log u_i = -log1p(-(1 - u_i))); word = output word
+ *                i & 3 of Philox4x32-10 with key = seed (low word, high word) and counter (r, t, i >> 2, 1) - the trailing 1 keeps
+ *                the stream apart from the token sampler's (r, t, 0, 0).
+ *   key          key_i = s_i + g_i, fp32.
+ *   selection    per item: the K = 2 num_beams kept entries of its num_beams rows with the largest keys, equal keys to the lower
+ *                flat index j * V + i; emitted in the order s descending, equal s to the lower flat index:
+ *                cand_score = s, cand_tok = i, cand_beam = j.
+ * Independent Gumbel noise on the scores and the K largest keys are K sequential draws without replacement from softmax(s)
+ * (Plackett-Luce) - what torch.multinomial(probs, 2 * num_beams) gives beam_sample.  Everything behind the ranking is
+ * rgrg_decoder_beam_search's: BeamSearchScorer.process / finalize, the ancestor table, early stopping, the length penalty,
+ * num_return_sequences.  t is the device step word (0 for the first generated token).  Runs on every step plan, precision mode and
+ * K/V cache format; the step is captured once per (rows, num_beams) under a key of its own - never shared with a plain or grouped
+ * beam step - and reads seed and parameters from a device block, so it serves every seed and parameter set.  Deterministic: the
+ * same inputs give the same ids.
+ *   RGRG_EINVAL (with a message): num_beams < 2 or > 16 (the row candidate lists hold 32 entries); num_return_sequences outside
+ *   1 .. num_beams; temperature not a finite float > 0; top_k < 0; top_p outside (0, 1]. */
+int rgrg_decoder_beam_sample(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping,
+                             float length_penalty, int num_return_sequences, float temperature, int top_k, float top_p, uint64_t seed,
+                             int64_t* out_ids, int out_ld, int* out_len, void* stream);
+/* ... from a prompt: the prompt arguments, mask rules and refusals of rgrg_decoder_beam_search_prompted (max_length < T + 1, the mask
+ * refusals, the e4m3 K/V cache in use for S * num_beams rows) on top of the refusals above.  The first ranking, of the item's last
+ * prompt position on num_beams identical rows with beam scores [0, -1e9, ...], uses t = T - 1: a [S,1] BOS prompt with a mask of
+ * ones returns the ids of rgrg_decoder_beam_sample. */
+int rgrg_decoder_beam_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
+                                      int T, int num_beams, int max_length, int early_stopping, float length_penalty,
+                                      int num_return_sequences, float temperature, int top_k, float top_p, uint64_t seed,
+                                      int64_t* out_ids, int out_ld, int* out_len, void* stream);
+/* Test hook: the two launches of that ranking alone on caller buffers, through the decoder's launcher.  logits f32 [S * nb][ld]
+ * (2 <= V <= 53248, ld >= V; 16-byte loads when ld % 4 == 0 and logits is 16-byte aligned), beam_scores f32 [S * nb]; row s * nb + j
+ * draws with the counter row row0 + s * nb + j at step `step` -> out_score f32 / out_tok i32 / out_beam i32 [S][2 nb]; row_key /
+ * row_s f32 and row_tok i32 [S * nb][32], all three or none: the 2 nb largest keys of every row, key descending, with their s and
+ * token ((-inf, -inf, 0) where a row keeps fewer than 2 nb tokens).  nb <= 16.  Synchronizes the stream. */
+int rgrg_debug_beam_sample_rank(const float* logits, int64_t ld, int V, int S, int nb, const float* beam_scores, float temperature,
+                                int top_k, float top_p, uint64_t seed, int step, int row0, float* out_score, int* out_tok, int* out_beam,
+                                float* row_key, float* row_s, int* row_tok, void* stream);
 /* Test hook: beam_group_merge_kernel alone on caller buffers.  row_max / row_logsum / beam_scores f32 [S * nb], top_val f32 /
  * top_tok i32 [S * nb][32] (rows as wide as in the decoder, the first 2 nb entries used) -> out_score f32 / out_tok i32 /
  * out_beam i32 [S][2 nb] (out_beam: the row within the item).  nb <= 16, G divides nb.  Synchronizes the stream. */

@@ -16,7 +16,7 @@ c_float_p = C.c_void_p  # device pointers travel as void*
 _i, _f, _p = C.c_int, C.c_float, C.c_void_p
 
 ACT_NONE, ACT_RELU, ACT_GELU_NEW = 0, 1, 2
-ABI_VERSION = 28  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change
+ABI_VERSION = 28  # must equal rgrg_abi_version() of the loaded library; bump both on ANY signature change (new entries change none)
 
 
 class RgrgHipError(RuntimeError):
@@ -70,6 +70,9 @@ SIGNATURES = {
     "rgrg_decoder_beam_search_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
     "rgrg_decoder_group_beam_search": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
     "rgrg_decoder_group_beam_search_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
+    "rgrg_decoder_beam_sample": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _f, _i, _f, C.c_uint64, _p, _i, C.POINTER(_i), _p]),
+    "rgrg_decoder_beam_sample_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _f, _i, _f, C.c_uint64, _p, _i, C.POINTER(_i), _p]),
+    "rgrg_debug_beam_sample_rank": (_i, [_p, C.c_int64, _i, _i, _i, _p, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "rgrg_debug_beam_group_merge": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p]),
     "rgrg_debug_beam_row_topk": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "rgrg_debug_beam_merge": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),

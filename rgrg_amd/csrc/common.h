@@ -190,10 +190,10 @@ __host__ __device__ __forceinline__ float dropout_mask(const DropoutParams& d, u
     const unsigned e = (unsigned)idx & 3u;
     return dropout_word_mask(d, e == 0 ? w.w[0] : e == 1 ? w.w[1] : e == 2 ? w.w[2] : w.w[3]);
 }
-// Philox4x32-10 (Salmon et al., SC'11; pinned against the Random123 known-answer vectors), first output word: the generator
-// of the detector's training samplers (det_train.hip) and of the token sampler (sample.hip).
-__host__ __device__ __forceinline__ unsigned philox4x32_10_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                                                 unsigned k1) {
+// Philox4x32-10 (Salmon et al., SC'11; pinned against the Random123 known-answer vectors): the generator of the detector's
+// training samplers (det_train.hip) and of the token sampler (sample.hip), which take the first output word, and of the
+// beam-sampling ranking (beam_sample.hip), which takes all four.
+__host__ __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
@@ -202,7 +202,11 @@ __host__ __device__ __forceinline__ unsigned philox4x32_10_first(unsigned c0, un
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    return c0;
+    return Philox4{{c0, c1, c2, c3}};
+}
+__host__ __device__ __forceinline__ unsigned philox4x32_10_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                                                 unsigned k1) {
+    return philox4x32_10(c0, c1, c2, c3, k0, k1).w[0];
 }
 // Attention-probability masks (site 1) are indexed [sentence][head][query][key] with the key pitch rounded up to a multiple of 4,
 // so that 4 consecutive keys of one query share a generator call whatever T is.

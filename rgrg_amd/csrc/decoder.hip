@@ -1802,7 +1802,7 @@ int step_graph(rgrg_decoder* d, const StepSpec& s, const std::function<int()>& b
     const int rc = body();
     hipError_t e = hipStreamEndCapture(d->stream, &graph);   // also behind a failed step: the stream must not stay in capture mode
     if (rc) return rc;
-    if (e != hipSuccess) { set_error("%shipStreamEndCapture: %s", s.end == STEP_BEAM ? "beam: " : "", hipGetErrorString(e)); return RGRG_EHIP; }
+    if (e != hipSuccess) { set_error("%shipStreamEndCapture: %s", (s.end == STEP_BEAM || s.end == STEP_BEAM_SAMPLE) ? "beam: " : "", hipGetErrorString(e)); return RGRG_EHIP; }
     RGRG_HIP(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
     d->graphs.push_back({s, *exec});

@@ -419,13 +419,17 @@ struct BeamHyps {
 // prompt == NULL: the BOS start of rgrg_decoder_beam_search.  With a prompt (rgrg_decoder_beam_search_prompted, decoder_prompt.hip)
 // the first iteration ranks the logits of the prompt's last position instead of running a step - the reference's first iteration
 // on nb identical rows - and ids / cur_len start at the prompt.
+// sample != NULL (never with groups): beam-search sampling (rgrg_decoder_beam_sample[_prompted]; the caller has checked the
+// parameters and nb <= 16) - the ranking is the Gumbel top-2nb draw of beam_sample.hip under its own StepEnd, everything behind it
+// (process / finalize below) is plain beam search's.
 // groups != NULL: diverse beam search (rgrg_decoder_group_beam_search[_prompted]; the caller has checked G and the penalty) - G
 // groups of gs = nb / G rows per item, ranked by beam_group_merge_kernel; BeamSearchScorer.process runs per item and group with
 // group_size gs on the item's shared heap and `done` flag.  groups == NULL is G = 1 on beam_merge_kernel: plain beam search.
 int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping,
                           float length_penalty, int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream,
-                          const BeamPrompt* prompt, const BeamGroups* groups) {
+                          const BeamPrompt* prompt, const BeamGroups* groups, const BeamSample* sample) {
     RGRG_CHECK_ARG(d && feats && out_ids && out_len && S > 0 && num_beams > 1 && num_beams <= (1 << 14));
+    RGRG_CHECK_ARG(!(groups && sample) && (!sample || num_beams <= BEAM_K / 2));
     RGRG_CHECK_ARG(num_return_sequences >= 1 && num_return_sequences <= num_beams);
     const int nb = num_beams, K = 2 * nb, R = S * nb;
     const int G = groups ? groups->G : 1, gs = nb / G;   // K = G * 2 gs candidate slots per item either way
@@ -454,8 +458,18 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         int r = dmalloc(d, (void**)&d->group_penalty, sizeof(float), true);
         if (r) return r;
     }
+    if (sample) {
+        int r;
+        if (!d->sample_prm && (r = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return r;
+        if (!d->bsample_s && (r = dmalloc(d, (void**)&d->bsample_s, (size_t)d->rows * BEAM_K * sizeof(float), true))) return r;
+    }
     RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
+    // ... and the sampling step its seed and parameters from this block: the graph of a spec serves every seed and parameter set
+    if (sample) {
+        int r = enqueue_sample_params(d->sample_prm, sample->temperature, sample->top_k, sample->top_p, sample->seed, st);
+        if (r) return r;
+    }
     // the captured group step reads the penalty from this word: the graph of a spec serves every penalty
     if (groups) RGRG_HIP(hipMemcpyAsync(d->group_penalty, &groups->penalty, sizeof(float), hipMemcpyHostToDevice, st));
     // prefill for the S image features; the image key/value of item s is stored in cache row s*nb (slot 0)
@@ -484,7 +498,10 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     int cur_len = prompt ? prompt->T : 1;
     bool first_ranking = prompt != nullptr;
     // the ranking of d->logits behind a step (captured with it) or behind the prompt's last position
-    auto enqueue_ranking = [&]() {
+    auto enqueue_ranking = [&]() -> int {
+        if (sample)   // t = *d->step: the step word, T - 1 for the first ranking behind a prompt of T tokens
+            return launch_beam_sample_rank(d->logits, (size_t)d->ld_logits, d->V, S, nb, d->beam_scores, d->sample_prm, nullptr, d->step, 0, 0,
+                                           d->top_val, d->bsample_s, d->top_tok, d->cand_score, d->cand_tok, d->cand_beam, st);
         launch_beam_row_topk(d->logits, d->ld_logits, d->V, R, K, d->row_max, d->row_logsum, wide ? d->wide_val : d->top_val,
                              wide ? d->wide_tok : d->top_tok, false, st);
         if (groups)
@@ -493,6 +510,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         else
             launch_beam_merge(d->row_max, d->row_logsum, wide ? d->wide_val : d->top_val, wide ? d->wide_tok : d->top_tok, d->beam_scores,
                               S, nb, d->V, d->wide_score, d->cand_score, d->cand_tok, d->cand_beam, false, st);
+        return RGRG_OK;
     };
     std::vector<float> nscore(R);
     std::vector<int> ntok(R), nidx(R);
@@ -503,18 +521,18 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         RGRG_HIP(hipMemcpyAsync(d->beam_scores, beam_scores.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
         if (first_ranking) {   // the prompt pass left the ln_f row of every item's last position in its nb rows: head, ranking, no step
             if ((rc = enqueue_head_logits(d, R))) return rc;
-            enqueue_ranking();
+            if ((rc = enqueue_ranking())) return rc;
             RGRG_LAUNCH_CHECK();
         } else {
             // the step (embed .. lm_head .. ranking) is captured once per spec - the ancestor table it reads is part of it - and
             // replayed; behind a left-padded prompt it carries per-row positions and the padded slots of every row
             StepSpec step;
-            step.rows = R; step.tok = d->beam_tok; step.src = src_cur; step.end = STEP_BEAM; step.nb = nb; step.G = groups ? G : 0;
+            step.rows = R; step.tok = d->beam_tok; step.src = src_cur; step.end = sample ? STEP_BEAM_SAMPLE : STEP_BEAM; step.nb = nb; step.G = groups ? G : 0;
             if (padded) step = padded_step_spec(d, step, d->beam_pad);
             hipGraphExec_t exec = nullptr;
             rc = step_graph(d, step, [&]() -> int {
                 int r = padded ? enqueue_beam_row_pos(d, R) : RGRG_OK;
-                if (!r && !(r = enqueue_step(d, step, false))) enqueue_ranking();
+                if (!r && !(r = enqueue_step(d, step, false))) r = enqueue_ranking();
                 return r;
             }, &exec);
             if (rc) return rc;
@@ -619,6 +637,34 @@ extern "C" int rgrg_decoder_beam_search(rgrg_decoder* d, const float* feats, int
                                         int out_ld, int* out_len, void* stream) {
     return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld,
                            out_len, stream, nullptr);
+}
+
+// the refusals the two beam-sampling entries share, each with a message
+int rgrg::check_beam_sample(const char* who, int num_beams, int num_return_sequences, float temperature, int top_k, float top_p) {
+    const int nb = num_beams;
+    if (nb < 2) { set_error("%s: num_beams %d: beam sampling needs more than one beam", who, nb); return RGRG_EINVAL; }
+    if (nb > BEAM_K / 2) {
+        set_error("%s: num_beams %d: beam sampling ranks at most %d beams (the row candidate lists hold %d entries)", who, nb, BEAM_K / 2, BEAM_K);
+        return RGRG_EINVAL;
+    }
+    if (num_return_sequences < 1 || num_return_sequences > nb) {
+        set_error("%s: num_return_sequences %d outside 1 .. num_beams %d", who, num_return_sequences, nb);
+        return RGRG_EINVAL;
+    }
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) { set_error("%s: temperature has to be a finite float > 0, but is %g", who, (double)temperature); return RGRG_EINVAL; }
+    if (top_k < 0) { set_error("%s: top_k has to be >= 0 (0 = off), but is %d", who, top_k); return RGRG_EINVAL; }
+    if (!(top_p > 0.f && top_p <= 1.0f)) { set_error("%s: top_p has to be in (0, 1], but is %g", who, (double)top_p); return RGRG_EINVAL; }
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_beam_sample(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping,
+                                        float length_penalty, int num_return_sequences, float temperature, int top_k, float top_p,
+                                        uint64_t seed, int64_t* out_ids, int out_ld, int* out_len, void* stream) {
+    int rc;
+    if ((rc = check_beam_sample("rgrg_decoder_beam_sample", num_beams, num_return_sequences, temperature, top_k, top_p))) return rc;
+    const BeamSample smp{temperature, top_k, top_p, seed};
+    return beam_search_run(d, feats, S, num_beams, max_length, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld,
+                           out_len, stream, nullptr, nullptr, &smp);
 }
 
 // the refusals the two diverse entries share, each with a message

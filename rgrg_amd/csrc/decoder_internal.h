@@ -87,7 +87,8 @@ enum StepEnd {
     STEP_ARGMAX,   // arg-max and the bookkeeping of record_step_token
     STEP_LOGITS,   // d->logits, nothing else (forward(use_cache=True))
     STEP_SAMPLE,   // d->logits, then the sampler and its bookkeeping (enqueue_sampler)
-    STEP_BEAM      // d->logits, then the ranking of nb beams per item in G groups, which the caller enqueues behind the step (G = 0: plain)
+    STEP_BEAM,     // d->logits, then the ranking of nb beams per item in G groups, which the caller enqueues behind the step (G = 0: plain)
+    STEP_BEAM_SAMPLE   // d->logits, then the beam-sampling ranking of nb beams per item (beam_sample.hip), enqueued by the caller likewise
 };
 struct StepSpec {
     int rows = 0;                      // sequences, or beam rows
@@ -97,7 +98,7 @@ struct StepSpec {
     const int* kv_first = nullptr;     // [rows] 16-bit cache: the attention skips slots 1 .. kv_first[r] (padding in front of a prompt)
     const float* key_mask = nullptr;   // [rows][T] fp32 cache: added to the scores of the slots
     StepEnd end = STEP_ARGMAX;
-    int nb = 0, G = 0;                 // STEP_BEAM
+    int nb = 0, G = 0;                 // STEP_BEAM (nb, G), STEP_BEAM_SAMPLE (nb)
     bool operator==(const StepSpec& o) const {
         return rows == o.rows && tok == o.tok && src == o.src && row_pos == o.row_pos && kv_first == o.kv_first && key_mask == o.key_mask &&
                end == o.end && nb == o.nb && G == o.G;
@@ -135,6 +136,7 @@ struct rgrg_decoder {
     // sampling (decoder_sample.hip): device-side parameter block the captured step reads, log-probs [rows][max_len]
     void* sample_prm = nullptr;
     float* sample_lp = nullptr;
+    float* bsample_s = nullptr;   // beam sampling: s of the row candidates [rows][BEAM_K], next to their keys (top_val) and tokens (top_tok)
     int* h_done;  // pinned: [0] final read, [1..2] the two in-flight "all finished" polls of the greedy loop
     hipEvent_t ev_poll[2] = {nullptr, nullptr};
     // Token-id validation of the teacher-forced passes, without a host round trip.  id_error[0]: raised by the CURRENT
@@ -296,9 +298,20 @@ int enqueue_beam_row_pos(rgrg_decoder* d, int R);
 // decoder_beam.hip: rgrg_decoder_beam_search, from a prompt when one is given
 // groups (or NULL = plain beam search): num_beam_groups and the Hamming diversity penalty of rgrg_decoder_group_beam_search
 struct BeamGroups { int G; float penalty; };
+// sample (or NULL; never together with groups): beam-search sampling - the ranking of beam_sample.hip under these parameters (the
+// caller has checked them and num_beams <= BEAM_K / 2)
+struct BeamSample { float temperature; int top_k; float top_p; unsigned long long seed; };
 int beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_beams, int max_length, int early_stopping, float length_penalty,
                     int num_return_sequences, int64_t* out_ids, int out_ld, int* out_len, void* stream, const BeamPrompt* prompt,
-                    const BeamGroups* groups = nullptr);
+                    const BeamGroups* groups = nullptr, const BeamSample* sample = nullptr);
+// the refusals the two beam-sampling entries share, each with a message
+int check_beam_sample(const char* who, int num_beams, int num_return_sequences, float temperature, int top_k, float top_p);
+// beam_sample.hip: the row and item launches of the beam-sampling ranking over S items of nb <= BEAM_K / 2 rows of logits [S * nb][ld];
+// parameters from the device block prm_dev or, when null, from *prm_val (both SampleParams); t = *step_dev or, when null, step;
+// row lists [S * nb][BEAM_K] -> out_score / out_tok / out_beam [S][2 nb]
+int launch_beam_sample_rank(const float* logits, size_t ld, int V, int S, int nb, const float* beam_scores, const void* prm_dev,
+                            const void* prm_val, const int* step_dev, int step, int row0, float* row_key, float* row_s, int* row_tok,
+                            float* out_score, int* out_tok, int* out_beam, hipStream_t st);
 int check_beam_groups(const char* who, int num_beams, int num_beam_groups, float diversity_penalty, int num_return_sequences);
 // decoder_sample.hip: the sampler behind the logits of S rows (the end of a STEP_SAMPLE step) and the start of every sampling entry
 int enqueue_sampler(rgrg_decoder* d, int S);

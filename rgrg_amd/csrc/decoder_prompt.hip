@@ -352,6 +352,21 @@ extern "C" int rgrg_decoder_group_beam_search_prompted(rgrg_decoder* d, const fl
                            stream, &p, &grp);
 }
 
+extern "C" int rgrg_decoder_beam_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask,
+                                                 int S, int T, int num_beams, int max_length, int early_stopping, float length_penalty,
+                                                 int num_return_sequences, float temperature, int top_k, float top_p, uint64_t seed,
+                                                 int64_t* out_ids, int out_ld, int* out_len, void* stream) {
+    int rc, limit;
+    if ((rc = check_beam_sample("rgrg_decoder_beam_sample_prompted", num_beams, num_return_sequences, temperature, top_k, top_p))) return rc;
+    RGRG_CHECK_ARG(d && feats && input_ids && out_ids && out_len && S > 0 && T >= 1);
+    RGRG_CHECK_ARG((long long)S * num_beams <= d->max_seqs);
+    if ((rc = check_prompted(d, "rgrg_decoder_beam_sample_prompted", S * num_beams, T, max_length, true, out_ld, &limit))) return rc;
+    const BeamPrompt p{reinterpret_cast<const long long*>(input_ids), attention_mask, T};
+    const BeamSample smp{temperature, top_k, top_p, seed};
+    return beam_search_run(d, feats, S, num_beams, limit, early_stopping, length_penalty, num_return_sequences, out_ids, out_ld, out_len,
+                           stream, &p, nullptr, &smp);
+}
+
 extern "C" int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
                                             int T, int max_length, float temperature, int top_k, float top_p, uint64_t seed,
                                             int64_t* out_ids, int out_ld, float* out_logprobs, int* out_len, int use_graph, void* stream) {

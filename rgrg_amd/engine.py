@@ -909,6 +909,62 @@ class HipEngine:
                                      int(num_return_sequences), out, limit, n, self._s()),
                                  feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
 
+    def beam_sample(self, feats: Tensor, max_length: int, num_beams: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                    seed: int = 0, early_stopping: bool = False, length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
+                    kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.beam_sample without a prompt (rgrg_decoder_beam_sample): feats [S,1024] -> int64 [S * num_return_sequences, L].
+        The library refuses what the ranking cannot take (RgrgHipError)."""
+        _require_gpu(feats.device)
+        S, limit = feats.shape[0], int(max_length)
+        return self._decode_call("rgrg_decoder_beam_sample", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_beam_sample(
+            dec, f, S, int(num_beams), limit, 1 if early_stopping else 0, float(length_penalty), int(num_return_sequences),
+            float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, out, limit, n, self._s()),
+            feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
+
+    def beam_sample_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: int, num_beams: int,
+                             temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, early_stopping: bool = False,
+                             length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1, kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.beam_sample with a prompt (rgrg_decoder_beam_sample_prompted): input_ids int64 [S,T] and attention_mask
+        [S,T] (or None = ones) hold ONE prompt per item -> int64 [S * num_return_sequences, L], the prompt in front.  Validation as
+        ``beam_search_prompted``."""
+        ids, am = self._check_prompt(feats, input_ids, attention_mask)
+        S, T = ids.shape
+        limit = self._beam_prompt_limit(max_length, T)
+        return self._decode_call("rgrg_decoder_beam_sample_prompted",
+                                 lambda dec, f, out, lp, n: self.lib.rgrg_decoder_beam_sample_prompted(
+                                     dec, f, _hip.ptr(ids), _hip.ptr(am), S, T, int(num_beams), limit, 1 if early_stopping else 0,
+                                     float(length_penalty), int(num_return_sequences), float(temperature), int(top_k), float(top_p),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, out, limit, n, self._s()),
+                                 feats, S * int(num_beams), S * int(num_return_sequences), limit, bf16, kv_fp8)
+
+    def beam_sample_rank(self, logits: Tensor, beam_scores: Tensor, num_beams: int, temperature: float = 1.0, top_k: int = 0,
+                         top_p: float = 1.0, seed: int = 0, step: int = 0, row0: int = 0, ld: Optional[int] = None,
+                         vocab: Optional[int] = None, row_lists: bool = False):
+        """The beam-sampling ranking alone (rgrg_debug_beam_sample_rank) on fp32 logits [S * num_beams, ld] and beam scores
+        [S * num_beams] -> (score f32, token i32, beam i32), each [S, 2 num_beams]; with ``row_lists`` also (key f32, s f32,
+        token i32), each [S * num_beams, 32]."""
+        _require_gpu(logits.device)
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and beam_scores.dtype == torch.float32
+        nb, R = int(num_beams), logits.shape[0]
+        assert R % nb == 0 and beam_scores.numel() == R
+        S, K = R // nb, 2 * nb
+        ld = int(logits.shape[1]) if ld is None else int(ld)
+        V = ld if vocab is None else int(vocab)
+        dev = logits.device
+        score = torch.full((S, K), float("nan"), dtype=torch.float32, device=dev)
+        tok = torch.full((S, K), -1, dtype=torch.int32, device=dev)
+        beam = torch.full((S, K), -1, dtype=torch.int32, device=dev)
+        rk = rs = rt = None
+        if row_lists:
+            rk = torch.full((R, 32), float("nan"), dtype=torch.float32, device=dev)
+            rs = torch.full((R, 32), float("nan"), dtype=torch.float32, device=dev)
+            rt = torch.full((R, 32), -1, dtype=torch.int32, device=dev)
+        _hip.check(self.lib.rgrg_debug_beam_sample_rank(_hip.ptr(logits), ld, V, S, nb, _hip.ptr(beam_scores.contiguous()),
+                                                        float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                        int(step), int(row0), _hip.ptr(score), _hip.ptr(tok), _hip.ptr(beam), _hip.ptr(rk),
+                                                        _hip.ptr(rs), _hip.ptr(rt), self._s()), "rgrg_debug_beam_sample_rank")
+        return (score, tok, beam, rk, rs, rt) if row_lists else (score, tok, beam)
+
     def _raise_pending_id_error(self) -> None:
         """An unreported token-id error of a decoder that has been re-created since (close())."""
         if getattr(self, "_pending_id_error", False):

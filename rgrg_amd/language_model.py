@@ -134,6 +134,20 @@ def check_group_beam_args(max_length, num_beams, num_beam_groups, diversity_pena
         raise ValueError("'num_return_sequences' has to be between 1 and 'num_beams'.")
 
 
+def check_beam_sample_args(max_length, num_beams, temperature, top_k, top_p, num_return_sequences) -> None:
+    """Argument errors of ``beam_sample`` (LanguageModel) / ``generate_beam_sample`` (ReportGenerationModel): ``check_sample_args``
+    plus the beam checks, raised before any GPU work."""
+    check_sample_args(temperature, top_k, top_p, num_return_sequences)
+    if max_length is None:
+        raise ValueError("max_length has to be set for beam generation.")
+    if int(num_beams) != num_beams or num_beams < 2:
+        raise ValueError(f"num_beams has to be an integer > 1 for beam sampling, but is {num_beams}")
+    if num_beams > 16:
+        raise ValueError(f"beam sampling ranks at most 16 beams, but num_beams is {num_beams}")
+    if num_return_sequences > num_beams:
+        raise ValueError("'num_return_sequences' has to be smaller or equal to 'num_beams'.")
+
+
 class LanguageModel(EngineOwner):
     _engine_prefix = "language_model."
 
@@ -427,6 +441,37 @@ class LanguageModel(EngineOwner):
         return self.engine().group_beam_search_prompted(image_hidden_states, input_ids, attention_mask, int(max_length), int(num_beams),
                                                         int(num_beam_groups), float(diversity_penalty), bool(early_stopping),
                                                         float(length_penalty), num_return_sequences=int(num_return_sequences), **modes)
+
+    @torch.no_grad()
+    def beam_sample(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, *, temperature: float = 1.0,
+                    top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, early_stopping: bool = False,
+                    num_return_sequences: int = 1, length_penalty: float = 1.0, input_ids: Optional[torch.LongTensor] = None,
+                    attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
+        """Beam-search sampling (transformers' ``beam_sample``; ``generate`` keeps raising for ``do_sample=True`` with
+        ``num_beams > 1``, as the reference does): beam search whose every step DRAWS the item's 2 * ``num_beams`` candidates
+        without replacement from the joint distribution over its ``num_beams`` x vocabulary continuations - log-probabilities
+        warped by ``temperature`` / ``top_k`` / ``top_p`` (at least two tokens per row are kept), then the beam score added
+        (contract in include/rgrg_hip.h).  Scorer, early stopping, length penalty and ``num_return_sequences``
+        are beam search's.  Returns int64 [S * num_return_sequences, L], best hypothesis first.  ``seed=None`` draws the seed from
+        torch's CPU generator (``torch.manual_seed`` governs it); the same seed gives the same ids.  ``input_ids`` /
+        ``attention_mask`` [S,T] hold ONE prompt per item, unexpanded, as in ``group_beam_search``; both or neither.
+        ValueError: the errors of ``sample``; ``num_beams`` outside 2 .. 16; ``num_return_sequences > num_beams``; ``max_length``
+        None or smaller than T + 1.  torch.autocast and ``set_kv_cache_dtype`` act as for ``generate``."""
+        check_beam_sample_args(max_length, num_beams, temperature, top_k, top_p, num_return_sequences)
+        if (input_ids is None) != (attention_mask is None):
+            raise ValueError("input_ids and attention_mask have to be given together (one prompt per item), or neither")
+        if input_ids is not None and int(max_length) < input_ids.shape[-1] + 1:
+            raise ValueError(f"max_length has to be at least {input_ids.shape[-1] + 1} for a prompt of {input_ids.shape[-1]} tokens, "
+                             f"but is {max_length}")
+        modes = self._decode_modes(image_hidden_states.device)
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        args = (int(max_length), int(num_beams), float(temperature), int(top_k), float(top_p), int(seed), bool(early_stopping),
+                float(length_penalty))
+        if input_ids is None:
+            return self.engine().beam_sample(image_hidden_states, *args, num_return_sequences=int(num_return_sequences), **modes)
+        return self.engine().beam_sample_prompted(image_hidden_states, input_ids, attention_mask, *args,
+                                                  num_return_sequences=int(num_return_sequences), **modes)
 
     @torch.no_grad()
     def sample_from_prompt(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int] = None,

@@ -14,7 +14,7 @@ from torch import Tensor
 from . import _hip
 from ._owner import EngineOwner
 from .binary_classifier import BinaryClassifierRegionAbnormal, BinaryClassifierRegionSelection
-from .language_model import LanguageModel, check_group_beam_args, check_sample_args
+from .language_model import LanguageModel, check_beam_sample_args, check_group_beam_args, check_sample_args
 from .object_detector import ObjectDetector
 
 _LM = "language_model."
@@ -206,6 +206,27 @@ class ReportGenerationModel(EngineOwner):
         output_ids = self.language_model.group_beam_search(selected_region_features, max_length, num_beams, num_beam_groups,
                                                            diversity_penalty, early_stopping=early_stopping,
                                                            num_return_sequences=num_return_sequences)
+        del selected_region_features
+        return output_ids, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def generate_beam_sample(self, images: torch.FloatTensor, max_length: int, num_beams: int, *, temperature: float = 1.0,
+                             top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, early_stopping: bool = False,
+                             num_return_sequences: int = 1):
+        """``generate`` with the sentences of the selected regions decoded by ``LanguageModel.beam_sample`` (beam-search sampling,
+        length penalty 1.0): the 4-tuple of ``generate`` (output_ids [S * num_return_sequences, L]) or ``-1`` when no region is
+        selected.  Argument errors are ``beam_sample``'s, raised before the detector runs."""
+        check_beam_sample_args(max_length, num_beams, temperature, top_k, top_p, num_return_sequences)
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        output_ids = self.language_model.beam_sample(selected_region_features, max_length, num_beams, temperature=temperature,
+                                                     top_k=top_k, top_p=top_p, seed=seed, early_stopping=early_stopping,
+                                                     num_return_sequences=num_return_sequences)
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
 
