@@ -200,6 +200,29 @@ int rgrg_decoder_generate(rgrg_decoder* d, const float* feats, int S, int max_le
  * :281), so the host mirror refuses that call and NULL here simply means ones. */
 int rgrg_decoder_generate_prompted(rgrg_decoder* d, const float* feats, const int64_t* input_ids, const float* attention_mask, int S,
                                    int T, int max_length, int64_t* out_ids, int out_ld, int* out_len, int use_graph, void* stream);
+/* Rolling-batch greedy decoding: the S sequences of feats [S,1024] flow through R decoder rows (1 <= R <= max_seqs of the decoder; S
+ * is not bounded by it).  Every step runs the R rows; a row whose sequence has ended - EOS, or max_length tokens with the BOS - takes
+ * the next pending sequence in the same step (pending sequences go to the free rows in ascending row order), starting again from BOS
+ * at position 0 with that sequence's image key / value in slot 0 of the row; rows without a sequence idle.  Every row keeps its own
+ * step: its attention reads the keys of ITS sequence only.  Sequence s produces the tokens rgrg_decoder_generate produces for it.
+ * ids_out int64 [S][max_length] on the device: BOS, the tokens, PAD behind the last one; lens_out int32 [S] on the device: tokens
+ * of every sequence, the BOS and the EOS included; *steps_out (host, optional): steps in which at least one row held a sequence.
+ * The step plan, the precision and the cache format are those of a decode step of R rows.  Synchronises `stream` before returning;
+ * use_graph = 0 launches the kernels eagerly.
+ *   RGRG_EINVAL (with a message): R outside 1 .. max_seqs; max_length outside 2 .. max_len; the e4m3 K/V cache in use for R rows.
+ *   RGRG_EHIP: sequences unfinished after (ceil(S / R) + 1) * (max_length - 1) steps - the bound of any schedule; the loop stops there. */
+int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats, int S, int R, int max_length, int64_t* ids_out, int* lens_out,
+                                  int* steps_out, int use_graph, void* stream);
+/* Test hook: ONE retire-and-refill step of rgrg_decoder_generate_rolling (the kernels behind the arg-max of its step) on the caller's
+ * state, all on the device.  int32 [R]: row_seq (the sequence a row holds, -1 = idle), row_len (its tokens so far), row_tok / row_pos
+ * / row_step (token, embedding position and step of the row's next step), arg (the arg-max of the step just run); shared int32 [4]
+ * = {next pending sequence, unfinished sequences, refills of this step, steps that had an active row}; ids int64 [S][ld_ids], lens
+ * int32 [S].  ukv f32 [S][ld_ukv >= n_layer * 2 * H * 64] and the cache kv [n_layer][K | V][R][H][T_slots][64] (kv16 = 0 fp32, 1 the
+ * 16-bit type of fp16; layer_stride / kv_stride in elements) are given together or both NULL (no refill launch): slot 0 of a
+ * refilled row receives the sequence's image key / value in the cache's rounding.  Synchronises `stream`. */
+int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                         int64_t* ids, int ld_ids, int* lens, int S, int R, int max_length, const float* ukv, int ld_ukv, void* kv,
+                         size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, void* stream);
 /* ---- Sampling.  The sampler is a pure function of one fp32 logits row x[0..V), temperature > 0, top_k >= 0 (0 = off),
  * 0 < top_p <= 1 (1 = off), a 64-bit seed, a row counter r and a step t:
  *   temperature  z_i = x_i * inv_T, inv_T = 1.0f / temperature computed once on the host in fp32.
@@ -626,6 +649,15 @@ int rgrg_debug_attn_decode_qonly(const float* q, int ld_q, const void* kcache, c
 int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* step_dev, float* out,
                                  uint16_t* out16, int S, int H, int T_slots, const int* first, int fp16, int q_only,
                                  int max_workgroups, void* stream);
+/* rgrg_debug_attn_decode_rowstep: the per-row-step variants, attn_decode_kernel<false, ni, false, true> (kv16 = 0) and
+ * attn_decode_kv16_wave_kernel<false, fp16, false, false, true> (kv16 = 1) - the steps of rgrg_decoder_generate_rolling: row_step int32
+ * [S] on the device replaces *step_dev, row s has the keys of slots 0 .. row_step[s] + 1 and stores its new k / v to slot
+ * row_step[s] + 1 of its own row.  A row at step t computes the bits rgrg_debug_attn_decode computes for it at *step_dev = t.
+ * Everything else as rgrg_debug_attn_decode (no src, no kmask, no frag_out).  row_step is read back and checked first (the call
+ * synchronises `stream`): RGRG_EINVAL for a value outside 0 .. T_slots - 2. */
+int rgrg_debug_attn_decode_rowstep(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* row_step, float* out,
+                                   uint16_t* out16, int S, int H, int T_slots, int kv16, int fp16, int ni, int max_workgroups,
+                                   void* stream);
 /* rgrg_debug_attn_decode_beam_first: a beam step behind a left-padded prompt (rgrg_decoder_beam_search_prompted) - ancestor table
  * src [S][T_slots] AND first int32 [S] together (first is constant inside a beam group in the product; any values in [0, t] here).
  *   kv16 = 1: attn_decode_kv16_wave_kernel<true, fp16, false, true>, slots 1 .. first[s] left out of the softmax;

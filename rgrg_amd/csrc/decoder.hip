@@ -464,7 +464,10 @@ __device__ __forceinline__ void attn_chunk(const float* __restrict__ kc, const f
 // tail sizes and between the two instantiations.
 // HAS_MASK (round 6, forward(use_cache=True) with padding): kmask [S][T] = the additive mask of every cache slot (slot 0, the image,
 // holds 0); the default instantiation carries none of it.
-template <bool HAS_SRC, int ATT_NI, bool HAS_MASK = false>  // HAS_SRC (beam search): per-slot ancestor table (one more dependent load per key, requested first)
+// ROWSTEP (rolling-batch decoding, decoder_roll.hip): `step` is [S], the step of every sequence's OWN row - the workgroup of sequence s
+// reads step[s] where the others read the one word *step; everything behind t is the same code, so a row at its own step t gives the
+// bits the default instantiation gives at *step = t.
+template <bool HAS_SRC, int ATT_NI, bool HAS_MASK = false, bool ROWSTEP = false>  // HAS_SRC (beam search): per-slot ancestor table (one more dependent load per key, requested first)
 __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                           float* __restrict__ kc, float* __restrict__ vc,
                                                           const int* __restrict__ step, float* __restrict__ out,
@@ -474,7 +477,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
     __shared__ __attribute__((aligned(16))) float pacc[16][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x / H, hd = blockIdx.x - s * H;
-    const int t = *step, nkeys = t + 2, slot = t + 1;
+    const int t = ROWSTEP ? step[s] : *step, nkeys = t + 2, slot = t + 1;
     const int g = lane >> 4, d4 = lane & 15;
     const float* row = qkv + (size_t)s * ld_qkv;
     const int D = H * 64;
@@ -653,14 +656,17 @@ __device__ __forceinline__ void kv16_wave_chunk(const __amdgpu_buffer_rsrc_t kc,
 // HAS_FIRST without HAS_SRC: `src` is [S], the padded prompt slots of every sequence (kv16_wave_chunk).  HAS_FIRST with HAS_SRC
 // (beam search from a left-padded prompt, rgrg_decoder_beam_search_prompted): `src` is the ancestor table and the padded slots
 // come in `first` [S], an operand only that instantiation reads
-template <bool HAS_SRC, bool F16, bool QONLY = false, bool HAS_FIRST = false>
+// ROWSTEP (rolling-batch decoding, decoder_roll.hip): `step` is [S] and a wave reads its item's step[s] inside the item loop: key
+// count, slot of the new key / value and the chunk switch follow the ROW (all of them uniform over the wave, which owns one item at a
+// time); the key-to-group-to-register mapping and the order of the sums are those of the default instantiation at *step = step[s]
+template <bool HAS_SRC, bool F16, bool QONLY = false, bool HAS_FIRST = false, bool ROWSTEP = false>
 __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                                     u16* __restrict__ kc, u16* __restrict__ vc,
                                                                     const int* __restrict__ step, float* __restrict__ out,
                                                                     int S, int H, int T, const int* __restrict__ src,
                                                                     u16* __restrict__ out16, const int* __restrict__ first = nullptr) {
     const int lane = threadIdx.x & 63;
-    const int t = *step, nkeys = t + 2, slot = t + 1;
+    int t = ROWSTEP ? 0 : *step, nkeys = t + 2, slot = t + 1;
     const int g = lane >> 3, d8 = lane & 7;
     const int D = H * 64;
     const __amdgpu_buffer_rsrc_t rk = dx_rsrc(kc), rv = dx_rsrc(vc);
@@ -670,6 +676,7 @@ __global__ __launch_bounds__(256) void attn_decode_kv16_wave_kernel(const float*
     // the GEMM workgroups of the other row ranges that run beside it (decoder.hip run_row_ranges).
     for (int item = blockIdx.x * 4 + (threadIdx.x >> 6); item < S * H; item += gridDim.x * 4) {
     const int s = item / H, hd = item - s * H;
+    if constexpr (ROWSTEP) { t = step[s]; nkeys = t + 2; slot = t + 1; }
     const float* row = qkv + (size_t)s * ld_qkv;
     const int* srow = HAS_SRC ? src + (size_t)s * T : nullptr;
     const int npad = HAS_FIRST ? (HAS_SRC ? first[s] : src[s]) : 0;
@@ -780,46 +787,17 @@ __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__
 // bookkeeping (:629-650).  The lm_head GEMM already reduced every 16- / 32-column tile to one
 // (max, index) candidate (ties: lower index), so a row is NT <= 3142 candidates: a thread requests its
 // (up to 13) candidates up front with clamped indices - one memory latency instead of one per loop trip.
-// The bookkeeping (PAD / EOS / the packed arrival ticket) is record_step_token (decoder_internal.h).
-constexpr int ARGMAX_U = 13;
+// The bookkeeping (PAD / EOS / the packed arrival ticket) is record_step_token, the reduction argmax_candidates_row (decoder_internal.h).
 __global__ __launch_bounds__(256) void argmax_update_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
                                                             int NT, long long* __restrict__ ids, int ld_ids,
                                                             int* __restrict__ finished, int* __restrict__ step,
                                                             int* __restrict__ done_len, int* __restrict__ sync, int S) {
     __shared__ float bv[4];
     __shared__ int bi[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.x;
     const int t = *step;
-    const float* cv = cand_val + (size_t)row * NT;
-    const int* cx = cand_idx + (size_t)row * NT;
-    float v[ARGMAX_U];
-    int ci[ARGMAX_U];
-#pragma unroll
-    for (int u = 0; u < ARGMAX_U; ++u) {
-        const int i = min(tid + 256 * u, NT - 1);
-        v[u] = cv[i];
-        ci[u] = cx[i];
-    }
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-#pragma unroll
-    for (int u = 0; u < ARGMAX_U; ++u)
-        if (tid + 256 * u < NT && (v[u] > best || (v[u] == best && ci[u] < idx))) { best = v[u]; idx = ci[u]; }
-    for (int i = tid + 256 * ARGMAX_U; i < NT; i += 256) {   // more than 3328 candidates per row: not a shape of this model
-        const float w = cv[i];
-        const int wi = cx[i];
-        if (w > best || (w == best && wi < idx)) { best = w; idx = wi; }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+    const int idx = argmax_candidates_row(cand_val + (size_t)row * NT, cand_idx + (size_t)row * NT, NT, bv, bi);
+    if (threadIdx.x == 0) {
         const StepBook bk{ids, ld_ids, finished, step, done_len, sync, S};
         record_step_token(bk, row, t, idx == 0x7fffffff ? 0 : idx);
     }
@@ -1148,6 +1126,8 @@ struct AttnDecodeLaunch {
     bool q_only = false;                   // 16-bit cache without src: slot t + 1 already holds the new k / v (c_attn's K/V-cache epilogue) -
                                            // the kernel reads q only and stores nothing to the cache
     const int* first = nullptr;            // 16-bit cache: [S] padded prompt slots, cache slots 1 .. first[s] are left out (with src: not q_only)
+    const int* row_step = nullptr;         // fp32 / 16-bit cache: [S] the step of every row on its own, instead of the one word *step (rolling-batch
+                                           // decoding); the plain form only - no table, no mask, no padded slots, not q_only
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
     if (a.kmask && a.fmt != KV_F32) {
@@ -1159,6 +1139,12 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
                   a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "fp32 K/V cache: pass the additive mask");
         return RGRG_EINVAL;
     }
+    if (a.row_step && (a.src || a.kmask || a.first || a.q_only || a.fmt == KV_E4M3)) {
+        set_error("decode attention: the per-row step exists for the plain fp32 and 16-bit kernels (%s)",
+                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.src ? "ancestor table" : a.q_only ? "q-only" : "padding mask");
+        return RGRG_EINVAL;
+    }
+    const int* step = a.row_step ? a.row_step : a.step;   // the ROWSTEP instantiations take the rows' steps where the others take *step
     if (a.fmt != KV_F32) {
         // one wave per (sequence, head); the cache rows are addressed with 32-bit byte offsets into one layer's K (V)
         // plane through a buffer descriptor, which bounds a plane at 2 GiB (8128 sequences at max_length 128 in 16 bit)
@@ -1184,8 +1170,9 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
             return launch_attn_decode_kv8(a.qkv, a.ld_qkv, static_cast<uint8_t*>(a.kc), static_cast<uint8_t*>(a.vc), a.step, a.out, a.out16,
                                           a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
 #define KV16_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<__VA_ARGS__>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
-                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), a.step, a.out, a.S, a.H, a.T, (a.first && !a.src) ? a.first : a.src, a.out16, a.first)
-        if (a.first && a.src) {   // beam search behind a left-padded prompt
+                                                  static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), step, a.out, a.S, a.H, a.T, (a.first && !a.src) ? a.first : a.src, a.out16, a.first)
+        if (a.row_step) { if (a.f16) KV16_LAUNCH(false, true, false, false, true); else KV16_LAUNCH(false, false, false, false, true); }
+        else if (a.first && a.src) {   // beam search behind a left-padded prompt
             if (a.f16) KV16_LAUNCH(true, true, false, true); else KV16_LAUNCH(true, false, false, true);
         } else if (a.first) {
             if (a.q_only) { if (a.f16) KV16_LAUNCH(false, true, true, true); else KV16_LAUNCH(false, false, true, true); }
@@ -1199,9 +1186,10 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
         const dim3 grid(a.S * a.H), blk(256);
         const int ni = a.ni ? a.ni : (a.S * a.H <= 4096 ? 9 : 2);
         if (ni != 9 && ni != 2) { set_error("decode attention: %d keys per group, the kernel is built for 9 and 2", ni); return RGRG_EINVAL; }
-#define ATT_LAUNCH(SRC_, NI_, MASK_) hipLaunchKernelGGL((attn_decode_kernel<SRC_, NI_, MASK_>), grid, blk, 0, a.st, a.qkv, a.ld_qkv, static_cast<float*>(a.kc), \
-                                                       static_cast<float*>(a.vc), a.step, a.out, a.S, a.H, a.T, a.src, a.frag_out, a.kmask)
-        if (a.kmask && a.src) {   // beam search behind a left-padded prompt (rgrg_decoder_beam_search_prompted)
+#define ATT_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kernel<__VA_ARGS__>), grid, blk, 0, a.st, a.qkv, a.ld_qkv, static_cast<float*>(a.kc), \
+                                                       static_cast<float*>(a.vc), step, a.out, a.S, a.H, a.T, a.src, a.frag_out, a.kmask)
+        if (a.row_step) { if (ni == 9) ATT_LAUNCH(false, 9, false, true); else ATT_LAUNCH(false, 2, false, true); }
+        else if (a.kmask && a.src) {   // beam search behind a left-padded prompt (rgrg_decoder_beam_search_prompted)
             if (ni == 9) ATT_LAUNCH(true, 9, true); else ATT_LAUNCH(true, 2, true);
         } else if (a.kmask) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
             if (ni == 9) ATT_LAUNCH(false, 9, true); else ATT_LAUNCH(false, 2, true);
@@ -1236,9 +1224,11 @@ static int launch_attention(rgrg_decoder* d, int l, const StepSpec& s, int r0, i
         a.qkv = d->qkv + (size_t)r0 * 3 * D; a.kc = kcr; a.vc = kcr + d->kv_kv_stride * esz;
         a.out = d->att + (size_t)r0 * D; a.out16 = att16;
         a.first = s.kv_first ? s.kv_first + r0 : nullptr;
+        a.row_step = s.row_step ? s.row_step + r0 : nullptr;
     } else {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
         a.qkv = d->qkv; a.kc = kc; a.vc = kc + d->kv_kv_stride; a.out = d->att;
+        a.row_step = s.row_step;
     }
     return launch_attn_decode(a);
 }
@@ -1354,7 +1344,7 @@ static int enqueue_step_fused(rgrg_decoder* d, const StepSpec& s, bool count) {
     if (count) { d->gemm_bytes_per_step = 0; d->gemm_flops_per_step = 0.0; d->gemm_launches_per_step = 0; }
     hipStream_t st = d->stream;
     const int S = s.rows;
-    const bool logits = s.end != STEP_ARGMAX;
+    const bool logits = s.end != STEP_ARGMAX && s.end != STEP_ROLL;
     int rc;
     float* cur = d->x;
     float* nxt = d->x2;
@@ -1368,6 +1358,7 @@ static int enqueue_step_fused(rgrg_decoder* d, const StepSpec& s, bool count) {
     h.Xf = cur; h.part = d->part; h.Y = d->logits; h.ldy = d->ld_logits; h.act = RGRG_ACT_NONE;
     if ((rc = direct_linear(d, d->lm_head, h, DX_COMBINE4, S, count, !logits))) return rc;
     if (logits) return RGRG_OK;
+    if (s.end == STEP_ROLL) return enqueue_roll_end(d, S, d->lm_head.NT);
     hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, d->lm_head.NT, d->ids,
                        d->max_len, d->finished, d->step, d->done_len, d->sync, S);
     RGRG_LAUNCH_CHECK();
@@ -1457,8 +1448,9 @@ static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, i
 }
 
 // The end of a step: lm_head over the ln_f rows (d->xn, or xn16 where the step's GEMMs read 16-bit activations).  logits: d->logits
-// and nothing else (the sampler or a ranking follows); otherwise per-tile arg-max candidates, arg-max and the bookkeeping.
-static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigned short* xn16) {
+// and nothing else (the sampler or a ranking follows); otherwise per-tile arg-max candidates, arg-max and the bookkeeping - of the
+// greedy loop, or (roll) of rolling-batch decoding, from the same candidates.
+static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigned short* xn16, bool roll = false) {
     hipStream_t st = d->stream;
     int rc;
     if (!logits && xn16 && lm_head_cand_path(d, S)) {
@@ -1467,6 +1459,7 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigne
         ce.cand_val = d->cand_val; ce.cand_idx = d->cand_idx;
         if ((rc = linear(d, d->lm_head, d->xn, nullptr, nullptr, S, d->ld_logits, RGRG_ACT_NONE, count, xn16, nullptr, &ce))) return rc;
         if ((rc = trace_mark(d, 0, 1002))) return rc;
+        if (roll) return enqueue_roll_end(d, S, (d->lm_head.N + 255) / 256);
         hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, (d->lm_head.N + 255) / 256, d->ids,
                            d->max_len, d->finished, d->step, d->done_len, d->sync, S);
         RGRG_LAUNCH_CHECK();
@@ -1478,6 +1471,7 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigne
     hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, S), dim3(256), 0, st, d->logits, d->ld_logits, d->V,
                        cand_nt, d->cand_val, d->cand_idx);
     RGRG_LAUNCH_CHECK();
+    if (roll) return enqueue_roll_end(d, S, cand_nt);
     hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, cand_nt, d->ids,
                        d->max_len, d->finished, d->step, d->done_len, d->sync, S);
     RGRG_LAUNCH_CHECK();
@@ -1580,7 +1574,7 @@ static int enqueue_step_tiled(rgrg_decoder* d, const StepSpec& s, bool count) {
         return RGRG_OK;
     };
     if ((rc = run_row_ranges(d, S, step_chains(d, S, s.end == STEP_ARGMAX && !s.tok && !s.src, fold), run_rows))) return rc;
-    return enqueue_head(d, S, count, s.end != STEP_ARGMAX, xn16);
+    return enqueue_head(d, S, count, s.end != STEP_ARGMAX && s.end != STEP_ROLL, xn16, s.end == STEP_ROLL);
 }
 // One decode step: the fused plan up to its row limit (128 token rows; 64 under autocast), the tiled plan above
 int enqueue_step(rgrg_decoder* d, const StepSpec& s, bool count) {
@@ -1768,6 +1762,7 @@ extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
     d->tf.free();
     d->tr.free();
     if (d->tr.a16_scratch) (void)hipFree(d->tr.a16_scratch);
+    if (d->roll.ukv) (void)hipFree(d->roll.ukv);
     if (d->h_done) (void)hipHostFree(d->h_done);
     for (hipEvent_t e : d->ev_poll)
         if (e) (void)hipEventDestroy(e);
@@ -2045,6 +2040,32 @@ extern "C" int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* 
     a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
     a.step = step_dev; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots; a.first = first;
     a.fmt = fp16 ? KV_F16 : KV_BF16; a.f16 = fp16 ? 1 : 0; a.max_wgs = max_workgroups; a.st = as_stream(stream); a.q_only = q_only != 0;
+    return launch_attn_decode(a);
+}
+
+// Test hook: the per-row-step variants (the steps of rgrg_decoder_generate_rolling) through the same launcher, on either cache format:
+// attn_decode_kernel<false, ni, false, true> / attn_decode_kv16_wave_kernel<false, fp16, false, false, true>.  row_step int32 [S] on
+// the device; it is read back and checked first (one synchronisation: 0 <= row_step[s] <= T_slots - 2, the slot a row writes).
+extern "C" int rgrg_debug_attn_decode_rowstep(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* row_step, float* out,
+                                              uint16_t* out16, int S, int H, int T_slots, int kv16, int fp16, int ni, int max_workgroups,
+                                              void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && row_step && S > 0 && H > 0 && T_slots >= 2 && ld_qkv >= 3 * H * 64);
+    RGRG_CHECK_ARG(out || (kv16 && out16));
+    RGRG_CHECK_ARG(kv16 || (!out16 && max_workgroups == 0));
+    RGRG_CHECK_ARG(!kv16 || ni == 0);
+    std::vector<int> host(S);
+    RGRG_HIP(hipStreamSynchronize(as_stream(stream)));
+    RGRG_HIP(hipMemcpy(host.data(), row_step, (size_t)S * sizeof(int), hipMemcpyDeviceToHost));
+    for (int s = 0; s < S; ++s)
+        if (host[s] < 0 || host[s] > T_slots - 2) {
+            set_error("rgrg_debug_attn_decode_rowstep: row_step[%d] = %d, a cache of %d slots takes 0 .. %d", s, host[s], T_slots, T_slots - 2);
+            return RGRG_EINVAL;
+        }
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.row_step = row_step; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots;
+    a.fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.max_wgs = max_workgroups;
+    a.st = as_stream(stream);
     return launch_attn_decode(a);
 }
 

@@ -1,5 +1,5 @@
 // What the decoder's translation units (decoder.hip: the decode step and the object; decoder_beam.hip: beam search;
-// decoder_lm.hip: the teacher-forced and training passes) share: the rgrg_decoder object, its constants and the few host
+// decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch greedy decoding) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
 #include <functional>
@@ -49,6 +49,45 @@ __device__ __forceinline__ int record_step_token(const StepBook& bk, int row, in
     }
     return tok;
 }
+
+// First-occurrence arg-max of one row of NT (value, column) candidates by the row's workgroup of 256 threads (bv / bi: 4 words of
+// LDS each): a thread requests its (up to 13) candidates up front with clamped indices - one memory latency instead of one per
+// loop trip.  -> the column in thread 0 (0x7fffffff for a row without any comparable value: the callers take token 0); shared by argmax_update_kernel (decoder.hip)
+// and roll_argmax_kernel (decoder_roll.hip).
+constexpr int ARGMAX_U = 13;
+__device__ __forceinline__ int argmax_candidates_row(const float* __restrict__ cv, const int* __restrict__ cx, int NT, float* bv, int* bi) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float v[ARGMAX_U];
+    int ci[ARGMAX_U];
+#pragma unroll
+    for (int u = 0; u < ARGMAX_U; ++u) {
+        const int i = min(tid + 256 * u, NT - 1);
+        v[u] = cv[i];
+        ci[u] = cx[i];
+    }
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < ARGMAX_U; ++u)
+        if (tid + 256 * u < NT && (v[u] > best || (v[u] == best && ci[u] < idx))) { best = v[u]; idx = ci[u]; }
+    for (int i = tid + 256 * ARGMAX_U; i < NT; i += 256) {   // more than 3328 candidates per row: not a shape of this model
+        const float w = cv[i];
+        const int wi = cx[i];
+        if (w > best || (w == best && wi < idx)) { best = w; idx = wi; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+    }
+    return idx;
+}
 #endif
 
 struct Lin {
@@ -88,7 +127,8 @@ enum StepEnd {
     STEP_LOGITS,   // d->logits, nothing else (forward(use_cache=True))
     STEP_SAMPLE,   // d->logits, then the sampler and its bookkeeping (enqueue_sampler)
     STEP_BEAM,     // d->logits, then the ranking of nb beams per item in G groups, which the caller enqueues behind the step (G = 0: plain)
-    STEP_BEAM_SAMPLE   // d->logits, then the beam-sampling ranking of nb beams per item (beam_sample.hip), enqueued by the caller likewise
+    STEP_BEAM_SAMPLE,  // d->logits, then the beam-sampling ranking of nb beams per item (beam_sample.hip), enqueued by the caller likewise
+    STEP_ROLL          // arg-max into d->roll.arg, then the retire-and-refill kernels of rolling-batch decoding (decoder_roll.hip enqueue_roll_end)
 };
 struct StepSpec {
     int rows = 0;                      // sequences, or beam rows
@@ -97,11 +137,12 @@ struct StepSpec {
     const int* row_pos = nullptr;      // [rows] embedding positions; NULL: *d->step
     const int* kv_first = nullptr;     // [rows] 16-bit cache: the attention skips slots 1 .. kv_first[r] (padding in front of a prompt)
     const float* key_mask = nullptr;   // [rows][T] fp32 cache: added to the scores of the slots
+    const int* row_step = nullptr;     // [rows] every row at a step of its own: key count t + 2 and slot t + 1 per row; NULL: *d->step for all
     StepEnd end = STEP_ARGMAX;
     int nb = 0, G = 0;                 // STEP_BEAM (nb, G), STEP_BEAM_SAMPLE (nb)
     bool operator==(const StepSpec& o) const {
         return rows == o.rows && tok == o.tok && src == o.src && row_pos == o.row_pos && kv_first == o.kv_first && key_mask == o.key_mask &&
-               end == o.end && nb == o.nb && G == o.G;
+               row_step == o.row_step && end == o.end && nb == o.nb && G == o.G;
     }
 };
 
@@ -240,6 +281,18 @@ struct rgrg_decoder {
     hipEvent_t ev_fork = nullptr, ev_join[rgrg::MAX_CHAINS - 1] = {};
     int kv8 = 0;      // rgrg_decoder_set_kv_format: 1 = the many-sequence 16-bit step keeps its K/V cache as e4m3 bytes (attn_kv8.hip); survives
                       // precision changes and has no effect where the cache is fp32 (fp32 mode, the fused plans, forward_cached)
+    // rolling-batch greedy decoding (decoder_roll.hip).  Per decoder row [rows]: the sequence it holds (-1 = idle), that sequence's
+    // length so far (BOS included), the token and the embedding position of its next step, its step (= the key count - 2), the arg-max
+    // of the step just run; list[2 k], list[2 k + 1] = row and sequence of the k-th refill of the step; shared[0] = the next pending
+    // sequence, [1] = unfinished sequences, [2] = refills of the step, [3] = steps that had an active row.  call: the device block of
+    // RollCall the captured kernels read what changes from call to call from; ukv [ukv_seqs][ld_ukv]: the image key / value rows of
+    // every sequence of the call (grown on demand, freed with the decoder)
+    struct RollWork {
+        int *seq = nullptr, *len = nullptr, *tok = nullptr, *pos = nullptr, *step = nullptr, *arg = nullptr, *list = nullptr, *shared = nullptr;
+        void* call = nullptr;
+        float* ukv = nullptr;
+        size_t ukv_seqs = 0;
+    } roll;
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
                       // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
@@ -316,6 +369,8 @@ int check_beam_groups(const char* who, int num_beams, int num_beam_groups, float
 // decoder_sample.hip: the sampler behind the logits of S rows (the end of a STEP_SAMPLE step) and the start of every sampling entry
 int enqueue_sampler(rgrg_decoder* d, int S);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
+// decoder_roll.hip: the end of a STEP_ROLL step - the arg-max of R rows over their NT candidates, retire, refill
+int enqueue_roll_end(rgrg_decoder* d, int R, int NT);
 int tf_reserve(rgrg_decoder* d, size_t rows);
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
                    int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr);

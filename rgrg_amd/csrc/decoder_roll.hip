@@ -1,0 +1,331 @@
+// Rolling-batch greedy decoding (rgrg_decoder_generate_rolling): R decoder rows through which any number of sequences flow.  A row
+// whose sequence has ended - EOS, or max_length tokens - takes the next pending sequence in the same step, so the work follows the
+// sum of the sequence lengths instead of sequences x the longest one, and the K/V cache is sized by R.
+//
+// The step is the decode step of every other mode (enqueue_step) with per-row tokens, positions and - new - per-row steps
+// (StepSpec::row_step: every attention item reads its own key count).  Its end (STEP_ROLL) is three launches:
+//   roll_argmax_kernel   the row's arg-max over the step's candidates -> roll.arg[r]
+//   roll_retire_kernel   ONE workgroup: append, retire, hand pending sequences to the free rows in ascending row order (a prefix
+//                        scan, no atomics: which row gets which sequence is a function of the tokens alone)
+//   roll_refill_kernel   the image key / value of every sequence handed out -> slot 0 of its row's cache, all layers
+// What changes from call to call (output buffers, sequence count, max_length) is read from a device block, so one captured graph
+// per (R, plan) serves every call.
+#include <algorithm>
+
+#include "decoder_internal.h"
+
+namespace rgrg {
+
+struct RollCall {
+    long long* ids;       // [S][ld] the caller's output: column 0 BOS, PAD behind a sequence's last token
+    int* len;             // [S] tokens of every sequence, BOS included (0 until it has ended)
+    const float* ukv;     // [S][ld_ukv] image key / value rows of every layer (the ukv GEMM's output)
+    int ld, S, max_length, ld_ukv;
+};
+struct RollRows {
+    int *seq, *len, *tok, *pos, *step, *list, *shared;
+};
+constexpr int ROLL_NEXT = 0, ROLL_UNFINISHED = 1, ROLL_REFILLS = 2, ROLL_STEPS = 3;
+
+__global__ __launch_bounds__(256) void roll_argmax_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx, int NT,
+                                                          int* __restrict__ arg) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int row = blockIdx.x;
+    const int idx = argmax_candidates_row(cand_val + (size_t)row * NT, cand_idx + (size_t)row * NT, NT, bv, bi);
+    if (threadIdx.x == 0) arg[row] = idx == 0x7fffffff ? 0 : idx;
+}
+
+// The start of a call: the call block, every row idle, nothing handed out, and the output in its final form for a sequence that
+// never runs a step (BOS, then PAD).  One launch of roll_retire_kernel behind it hands out the first min(S, R) sequences.
+__global__ __launch_bounds__(256) void roll_begin_kernel(const RollCall c, RollCall* __restrict__ call, const RollRows st, int R) {
+    const size_t total = (size_t)c.S * c.max_length;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        c.ids[(i / c.max_length) * c.ld + (i % c.max_length)] = (i % c.max_length) == 0 ? BOS_ID : PAD_ID;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < c.S; s += gridDim.x * blockDim.x) c.len[s] = 0;
+    if (blockIdx.x == 0) {
+        for (int r = threadIdx.x; r < R; r += 256) {
+            st.seq[r] = -1; st.len[r] = 0; st.tok[r] = BOS_ID; st.pos[r] = 0; st.step[r] = 0;
+        }
+        if (threadIdx.x == 0) {
+            *call = c;
+            st.shared[ROLL_NEXT] = 0; st.shared[ROLL_UNFINISHED] = c.S; st.shared[ROLL_REFILLS] = 0; st.shared[ROLL_STEPS] = 0;
+        }
+    }
+}
+
+// Retire and refill, one workgroup of 256 threads over the R rows in passes of 256 (tests/rolling_reference.py is the model):
+//   an ACTIVE row (seq >= 0) appends arg[r] at ids[seq][len]; on EOS, or when that was the max_length-th token, the sequence's
+//   length is recorded and the row is free; otherwise the token, len - 1 as position and step are the row's next input.
+//   FREE rows - just retired, or idle - take the pending sequences next, next + 1, ... in ascending row order as long as there
+//   are any: BOS, position 0, step 0, and (row, sequence) goes to the refill list.  A free row without a sequence is idle: it
+//   keeps the BOS state, runs along and writes nothing.
+// `next` advances by the sequences handed out, not by the free rows.
+__global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, const int* __restrict__ arg, const RollCall* __restrict__ call,
+                                                          int R) {
+    __shared__ int wave_free[4];
+    const RollCall c = *call;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int next0 = st.shared[ROLL_NEXT];
+    int base_rank = 0;      // free rows in front of this pass
+    int active_in = 0;      // this thread's rows that were active on entry
+    for (int r0 = 0; r0 < R; r0 += 256) {
+        const int r = r0 + tid;
+        bool is_free = false;
+        if (r < R) {
+            const int seq = st.seq[r];
+            is_free = seq < 0;
+            if (seq >= 0) {
+                ++active_in;
+                const int tok = arg[r];
+                int len = st.len[r];
+                c.ids[(size_t)seq * c.ld + len] = tok;
+                ++len;
+                if (tok == EOS_ID || len >= c.max_length) {
+                    c.len[seq] = len;
+                    is_free = true;
+                } else {
+                    st.len[r] = len; st.tok[r] = tok; st.pos[r] = len - 1; st.step[r] = len - 1;
+                }
+            }
+        }
+        // exclusive prefix count of the free rows of this pass: inside the wave from the ballot, across the 4 waves through LDS
+        const unsigned long long b = __ballot(is_free);
+        const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_free[wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, pass_free = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += wave_free[w];
+            pass_free += wave_free[w];
+        }
+        if (is_free) {
+            const int k = base_rank + before + in_wave;
+            const int seq = next0 + k;
+            const bool given = seq < c.S;
+            st.seq[r] = given ? seq : -1;
+            st.len[r] = given ? 1 : 0;
+            st.tok[r] = BOS_ID; st.pos[r] = 0; st.step[r] = 0;
+            if (given) { st.list[2 * k] = r; st.list[2 * k + 1] = seq; }
+        }
+        base_rank += pass_free;
+        __syncthreads();   // wave_free is rewritten by the next pass
+    }
+    // base_rank = free rows of the step (the same in every thread)
+    const int given = min(base_rank, c.S - next0);
+    const unsigned long long any = __ballot(active_in > 0);
+    if (lane == 0) wave_free[wave] = any != 0ull;
+    __syncthreads();
+    if (tid == 0) {
+        st.shared[ROLL_NEXT] = next0 + given;
+        st.shared[ROLL_REFILLS] = given;
+        st.shared[ROLL_UNFINISHED] = (c.S - (next0 + given)) + (R - (base_rank - given));   // pending + rows that hold a sequence now
+        if (wave_free[0] | wave_free[1] | wave_free[2] | wave_free[3]) st.shared[ROLL_STEPS] += 1;
+    }
+}
+
+// The image key / value of every sequence handed out in this step (the refill list) -> cache slot 0 of its row, every layer, with
+// kv_slot0_kernel's rounding for the cache format (16 bit: to16_rt; fp32: the value).  Grid (layers * 2, ROLL_REFILL_ROWS): workgroup
+// (x, y) copies the D values of plane x for list entries y, y + gridDim.y, ...; a step without refills costs the empty launch.
+constexpr int ROLL_REFILL_ROWS = 32;
+template <typename KV>
+__global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict__ list, const int* __restrict__ shared,
+                                                          const RollCall* __restrict__ call, KV* __restrict__ kv_all, size_t layer_stride,
+                                                          size_t kv_stride, int H, int T, int f16) {
+    const int n = shared[ROLL_REFILLS];
+    const int l = blockIdx.x >> 1, kv = blockIdx.x & 1, D = H * 64;
+    const float* ukv = call->ukv;
+    const int ld = call->ld_ukv;
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const int r = list[2 * k], seq = list[2 * k + 1];
+        for (int d = threadIdx.x; d < D; d += 256) {
+            const int hd = d >> 6, e = d & 63;
+            const float val = ukv[(size_t)seq * ld + ((size_t)l * 2 + kv) * D + d];
+            const size_t o = (size_t)l * layer_stride + (size_t)kv * kv_stride + (((size_t)r * H + hd) * T) * 64 + e;
+            if constexpr (sizeof(KV) == 2) kv_all[o] = (KV)to16_rt(val, f16);
+            else kv_all[o] = val;
+        }
+    }
+}
+
+namespace {
+
+int launch_retire_refill(const RollRows& st, const int* arg, const RollCall* call, int R, void* kv, size_t layer_stride, size_t kv_stride,
+                         int H, int T, int n_layer, KvFormat fmt, int f16, hipStream_t s) {
+    hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, s, st, arg, call, R);
+    RGRG_LAUNCH_CHECK();
+    const dim3 grid(n_layer * 2, std::min(R, ROLL_REFILL_ROWS));
+    if (fmt == KV_F32)
+        hipLaunchKernelGGL(roll_refill_kernel<float>, grid, dim3(256), 0, s, st.list, st.shared, call, static_cast<float*>(kv), layer_stride,
+                           kv_stride, H, T, 0);
+    else
+        hipLaunchKernelGGL(roll_refill_kernel<unsigned short>, grid, dim3(256), 0, s, st.list, st.shared, call,
+                           static_cast<unsigned short*>(kv), layer_stride, kv_stride, H, T, f16);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+RollRows roll_rows(const rgrg_decoder* d) {
+    const rgrg_decoder::RollWork& w = d->roll;
+    return RollRows{w.seq, w.len, w.tok, w.pos, w.step, w.list, w.shared};
+}
+
+int roll_reserve(rgrg_decoder* d, int S) {
+    rgrg_decoder::RollWork& w = d->roll;
+    int rc;
+    if (!w.seq) {
+        const size_t R = d->rows;
+        int** rows[] = {&w.seq, &w.len, &w.tok, &w.pos, &w.step, &w.arg};
+        for (int** p : rows)
+            if ((rc = dmalloc(d, (void**)p, R * sizeof(int), true))) return rc;
+        if ((rc = dmalloc(d, (void**)&w.list, 2 * R * sizeof(int), true))) return rc;
+        if ((rc = dmalloc(d, (void**)&w.shared, 4 * sizeof(int), true))) return rc;
+        if ((rc = dmalloc(d, &w.call, sizeof(RollCall), true))) return rc;
+    }
+    if ((size_t)S > w.ukv_seqs) {
+        RGRG_HIP(hipStreamSynchronize(d->stream));
+        if (w.ukv) (void)hipFree(w.ukv);
+        w.ukv = nullptr; w.ukv_seqs = 0;
+        RGRG_HIP(hipMalloc((void**)&w.ukv, (size_t)S * d->ld_ukv * sizeof(float)));
+        w.ukv_seqs = S;
+    }
+    return RGRG_OK;
+}
+
+// feature_space_transformation_nn and the uk / uv GEMM of all S sequences (enqueue_prefill's, in passes of up to max_seqs rows
+// through its work space; S <= max_seqs is one pass, the GEMM calls of rgrg_decoder_generate for S rows) -> roll.ukv
+int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
+    const int D = d->D;
+    int rc;
+    for (int s0 = 0; s0 < S; s0 += d->max_seqs) {
+        const int M = std::min(d->max_seqs, S - s0);
+        RGRG_HIP(hipMemcpyAsync(d->feats, feats + (size_t)s0 * D, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
+        if ((rc = linear(d, d->fst0, d->feats, nullptr, d->h1, M, D, RGRG_ACT_RELU, false))) return rc;
+        if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, M, D, RGRG_ACT_NONE, false))) return rc;
+        if ((rc = linear(d, d->ukv, d->img, nullptr, d->roll.ukv + (size_t)s0 * d->ld_ukv, M, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
+    }
+    return RGRG_OK;
+}
+
+}  // namespace
+
+int enqueue_roll_end(rgrg_decoder* d, int R, int NT) {
+    hipLaunchKernelGGL(roll_argmax_kernel, dim3(R), dim3(256), 0, d->stream, d->cand_val, d->cand_idx, NT, d->roll.arg);
+    RGRG_LAUNCH_CHECK();
+    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
+    return launch_retire_refill(roll_rows(d), d->roll.arg, static_cast<const RollCall*>(d->roll.call), R, d->kv, d->kv_layer_stride,
+                                d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream);
+}
+
+}  // namespace rgrg
+
+using namespace rgrg;
+
+extern "C" int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats, int S, int R, int max_length, int64_t* ids_out,
+                                             int* lens_out, int* steps_out, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && feats && ids_out && lens_out && S > 0);
+    if (R < 1 || R > d->max_seqs) {
+        set_error("rgrg_decoder_generate_rolling: %d decoder rows, the cache of this decoder holds 1 .. %d", R, d->max_seqs);
+        return RGRG_EINVAL;
+    }
+    if (max_length < 2 || max_length > d->max_len) {
+        set_error("rgrg_decoder_generate_rolling: max_length %d, 2 .. %d (the cache) are possible", max_length, d->max_len);
+        return RGRG_EINVAL;
+    }
+    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
+    if (fmt == KV_E4M3) {
+        set_error("rgrg_decoder_generate_rolling: the e4m3 K/V cache has no per-row step: call rgrg_decoder_set_kv_format(d, 0) first");
+        return RGRG_EINVAL;
+    }
+    int rc;
+    if ((rc = decode_begin(d, stream))) return rc;
+    if ((rc = roll_reserve(d, S))) return rc;
+    if ((rc = enqueue_roll_prefill(d, feats, S))) return rc;
+    hipStream_t st = d->stream;
+    const RollRows rows = roll_rows(d);
+    const RollCall call{reinterpret_cast<long long*>(ids_out), lens_out, d->roll.ukv, max_length, S, max_length, d->ld_ukv};
+    RollCall* dcall = static_cast<RollCall*>(d->roll.call);
+    hipLaunchKernelGGL(roll_begin_kernel, dim3(64), dim3(256), 0, st, call, dcall, rows, R);
+    RGRG_LAUNCH_CHECK();
+    // every row is idle: this hands the first min(S, R) sequences to rows 0, 1, ... and fills their slot 0 (roll.arg is not read)
+    if ((rc = launch_retire_refill(rows, d->roll.arg, dcall, R, d->kv, d->kv_layer_stride, d->kv_kv_stride, d->H, d->T, d->n_layer, fmt,
+                                   d->f16(), st)))
+        return rc;
+
+    StepSpec step;
+    step.rows = R; step.tok = d->roll.tok; step.row_pos = d->roll.pos; step.row_step = d->roll.step; step.end = STEP_ROLL;
+    hipGraphExec_t exec = nullptr;
+    if (use_graph && (rc = step_graph(d, step, [&] { return enqueue_step(d, step, true); }, &exec))) return rc;
+    // A sequence takes at most max_length - 1 steps and a free row never waits while a sequence is pending (list scheduling): all S
+    // are done within ceil(S / R) (max_length - 1) steps of full rows plus one more sequence's worth.  The loop cannot run past that,
+    // whatever the device words say.
+    const long long bound = ((long long)(S + R - 1) / R + 1) * (max_length - 1);
+    // "nothing unfinished" is polled like the greedy loop polls its length word (run_decode_loop): every 16 steps, waiting for the copy
+    // queued 16 steps earlier; the up to 32 steps behind the last retirement run idle rows only
+    int polls = 0;
+    d->h_done[1] = d->h_done[2] = 1;
+    for (long long t = 0; t < bound; ++t) {
+        if (exec) RGRG_HIP(hipGraphLaunch(exec, st));
+        else if ((rc = enqueue_step(d, step, t == 0))) return rc;
+        if ((t & 15) == 15 && t + 1 < bound) {
+            if (polls > 0) {
+                const int prev = (polls - 1) & 1;
+                RGRG_HIP(hipEventSynchronize(d->ev_poll[prev]));
+                if (d->h_done[1 + prev] == 0) break;
+            }
+            const int cur = polls & 1;
+            RGRG_HIP(hipMemcpyAsync(d->h_done + 1 + cur, d->roll.shared + ROLL_UNFINISHED, sizeof(int), hipMemcpyDeviceToHost, st));
+            RGRG_HIP(hipEventRecord(d->ev_poll[cur], st));
+            ++polls;
+        }
+    }
+    RGRG_HIP(hipMemcpyAsync(d->h_done, d->roll.shared + ROLL_UNFINISHED, sizeof(int), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipMemcpyAsync(d->h_done + 1, d->roll.shared + ROLL_STEPS, sizeof(int), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    d->logits_stale_rows = 0;   // (logits_valid stays false: the last step's rows are idle ones)
+    if (d->h_done[0] != 0) {
+        set_error("rgrg_decoder_generate_rolling: %d of %d sequences unfinished after the bound of %lld steps on %d rows", d->h_done[0], S,
+                  bound, R);
+        return RGRG_EHIP;
+    }
+    if (steps_out) *steps_out = d->h_done[1];
+    return RGRG_OK;
+}
+
+// Test hook: ONE retire-and-refill step (roll_retire_kernel, roll_refill_kernel as the product launches them) on the caller's state.
+// Device int32: row_seq / row_len / row_tok / row_pos / row_step / arg [R], shared [4] = {next pending, unfinished, refills, steps};
+// ids int64 [S][ld_ids], lens [S].  ukv f32 [S][ld_ukv] and the cache kv [n_layer][2][R][H][T_slots][64] (fp32, or 16 bit with kv16 /
+// fp16; layer_stride / kv_stride in elements) may be NULL together: no refill launch.  Synchronises `stream`.
+extern "C" int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                                    int64_t* ids, int ld_ids, int* lens, int S, int R, int max_length, const float* ukv, int ld_ukv,
+                                    void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16,
+                                    void* stream) {
+    RGRG_CHECK_ARG(row_seq && row_len && row_tok && row_pos && row_step && shared && arg && ids && lens);
+    RGRG_CHECK_ARG(S > 0 && R > 0 && R < 65536 && max_length >= 2 && ld_ids >= max_length);
+    RGRG_CHECK_ARG((ukv == nullptr) == (kv == nullptr));
+    RGRG_CHECK_ARG(!kv || (H > 0 && T_slots >= 2 && n_layer > 0 && ld_ukv >= n_layer * 2 * H * 64 && kv_stride >= (size_t)R * H * T_slots * 64 &&
+                           layer_stride >= 2 * kv_stride));
+    hipStream_t st = as_stream(stream);
+    int* list = nullptr;
+    RollCall* dcall = nullptr;
+    RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
+    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("rgrg_debug_roll_step: hipMalloc failed"); return RGRG_EHIP; }
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S, max_length, ld_ukv};
+    hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
+    const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
+    int rc = RGRG_OK;
+    if (e == hipSuccess) {
+        if (kv) rc = launch_retire_refill(rows, arg, dcall, R, kv, layer_stride, kv_stride, H, T_slots, n_layer,
+                                          kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32, fp16 ? 1 : 0, st);
+        else { hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, st, rows, arg, dcall, R); e = hipGetLastError(); }
+    }
+    const hipError_t es = hipStreamSynchronize(st);   // the list and the call block are the call's own: they must outlive the launches
+    (void)hipFree(list);
+    (void)hipFree(dcall);
+    if (!rc && (e != hipSuccess || es != hipSuccess)) {
+        set_error("rgrg_debug_roll_step: %s", hipGetErrorString(e != hipSuccess ? e : es));
+        return RGRG_EHIP;
+    }
+    return rc;
+}

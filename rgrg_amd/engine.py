@@ -768,6 +768,42 @@ class HipEngine:
         return self._decode_call("rgrg_decoder_generate", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_generate(
             dec, f, S, limit, out, limit, n, 1 if use_graph else 0, self._s()), feats, S, S, limit, bf16, kv_fp8)
 
+    def rolling_rows_that_fit(self, max_length: int, budget_fraction: float = 0.5) -> int:
+        """The most decoder rows ``greedy_decode_rolling`` may use at ``max_length``: what the existing decoder holds, or what a
+        K/V cache of that many token slots may have within ``budget_fraction`` of the free device memory (the rule of
+        ``cache_tokens_that_fit``), in whole 32-row tiles below the 65536 rows the C ABI takes."""
+        cap_s, cap_l = self._decoder_caps
+        per_row = self.n_layer * 2 * 16 * (max(int(max_length), cap_l) + 1) * 64 * 4
+        free, _total = torch.cuda.mem_get_info(self.device)
+        free += max(0, torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device))
+        fit = min(int(free * budget_fraction) // per_row // 32 * 32, 65504)
+        return max(fit, cap_s if max_length <= cap_l else 0)
+
+    def greedy_decode_rolling(self, feats: Tensor, max_length: int, rows: Optional[int] = None, use_graph: bool = True, bf16=False,
+                              kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.generate_rolling (rgrg_decoder_generate_rolling): feats [S,1024] -> int64 [S, L'], the ids of
+        ``greedy_decode``, decoded on ``rows`` decoder rows that finished sequences hand to pending ones (None: min(S,
+        ``rolling_rows_that_fit``)).  The decoder - cache, step plan, precision - is the one of ``rows`` token rows.
+        ``last_rolling_steps``: the steps the call ran with at least one sequence in a row."""
+        _require_gpu(feats.device)
+        S, limit = feats.shape[0], int(max_length)
+        fit = self.rolling_rows_that_fit(limit)
+        R = min(S, fit) if rows is None else int(rows)
+        if R < 1 or R > fit:
+            raise _hip.RgrgHipError(f"rolling decode on {R} rows: a K/V cache of {limit} token slots holds 1 .. {fit} rows on this device")
+        lens = torch.zeros((S,), dtype=torch.int32, device=feats.device)
+        steps = C.c_int(0)
+
+        def call(dec, f, out, lp, n):
+            rc = self.lib.rgrg_decoder_generate_rolling(dec, f, S, R, limit, out, _hip.ptr(lens), C.byref(steps), 1 if use_graph else 0,
+                                                        self._s())
+            if rc == 0:
+                n._obj.value = int(lens.max())   # generate()'s width: the longest sequence
+            return rc
+        ids = self._decode_call("rgrg_decoder_generate_rolling", call, feats, R, S, limit, bf16, kv_fp8)
+        self.last_rolling_steps = steps.value
+        return ids
+
     def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
                                use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.greedy_search with a prompt (rgrg_decoder_generate_prompted): feats [S,1024], input_ids int64 [S,T],

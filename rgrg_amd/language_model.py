@@ -148,6 +148,18 @@ def check_beam_sample_args(max_length, num_beams, temperature, top_k, top_p, num
         raise ValueError("'num_return_sequences' has to be smaller or equal to 'num_beams'.")
 
 
+def check_rolling_args(max_length, rows) -> None:
+    """Argument errors of ``generate_rolling`` (LanguageModel, ReportGenerationModel): raised before any GPU work."""
+    if max_length is None:
+        raise ValueError("max_length has to be set for rolling-batch generation (it bounds every sequence and the K/V cache).")
+    if int(max_length) != max_length or max_length < 2:
+        raise ValueError(f"max_length has to be an integer >= 2 (BOS and one generated token), but is {max_length}")
+    if max_length > N_POS:
+        raise ValueError(f"max_length {max_length} exceeds the {N_POS} positions of the model")
+    if rows is not None and (int(rows) != rows or rows < 1):
+        raise ValueError(f"rows has to be a positive integer (the decoder rows the sequences flow through), but is {rows}")
+
+
 class LanguageModel(EngineOwner):
     _engine_prefix = "language_model."
 
@@ -328,6 +340,20 @@ class LanguageModel(EngineOwner):
         ids, logprobs = self.engine().sample_decode(image_hidden_states, max_length, temperature, int(top_k), top_p, int(seed),
                                                     int(num_return_sequences), **modes)
         return (ids, logprobs) if return_logprobs else ids
+
+    @torch.no_grad()
+    def generate_rolling(self, image_hidden_states: torch.FloatTensor, max_length: int, *, rows: Optional[int] = None) -> torch.LongTensor:
+        """Greedy search in its serving form: the S rows of ``image_hidden_states`` flow through ``rows`` decoder rows; a row whose
+        sentence has ended (EOS, or ``max_length`` tokens) takes the next pending one in the same step.  Same
+        return contract as ``generate(num_beams=1)`` - int64 [S, L'], input order, PAD after EOS, L' the longest sentence - and the
+        same tokens; the work follows the sum of the sentence lengths instead of S x the longest, and the K/V cache is sized by
+        ``rows``, so S may exceed what one ``generate`` call can hold.  ``rows=None`` takes min(S, the rows a cache of
+        ``max_length`` tokens can have on this device).  ValueError: ``max_length`` None or < 2, ``rows`` < 1; RgrgHipError: more
+        ``rows`` than that cache can have, and ``set_kv_cache_dtype("fp8_e4m3")`` where it would be used (the e4m3 attention kernel
+        has no per-row step).  torch.autocast opts into the 16-bit plans by ``rows``, exactly as ``generate`` does by S."""
+        check_rolling_args(max_length, rows)
+        modes = self._decode_modes(image_hidden_states.device)
+        return self.engine().greedy_decode_rolling(image_hidden_states, int(max_length), None if rows is None else int(rows), **modes)
 
     @torch.no_grad()
     def greedy_search(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int],

@@ -14,7 +14,7 @@ from torch import Tensor
 from . import _hip
 from ._owner import EngineOwner
 from .binary_classifier import BinaryClassifierRegionAbnormal, BinaryClassifierRegionSelection
-from .language_model import LanguageModel, check_beam_sample_args, check_group_beam_args, check_sample_args
+from .language_model import LanguageModel, check_beam_sample_args, check_group_beam_args, check_rolling_args, check_sample_args
 from .object_detector import ObjectDetector
 
 _LM = "language_model."
@@ -186,6 +186,24 @@ class ReportGenerationModel(EngineOwner):
             return -1
         output_ids = self.language_model.generate(selected_region_features, max_length, num_beams, num_beam_groups,
                                                   do_sample, num_return_sequences, early_stopping)
+        del selected_region_features
+        return output_ids, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def generate_rolling(self, images: torch.FloatTensor, max_length: int, *, rows: Optional[int] = None):
+        """``generate`` (greedy) with the sentences of the selected regions decoded by ``LanguageModel.generate_rolling``: the
+        regions flow through ``rows`` decoder rows instead of all being decoded in lock step.  The 4-tuple of ``generate``, with the
+        same output_ids, or ``-1`` when no region is selected.  Argument errors are ``generate_rolling``'s, raised before the
+        detector runs."""
+        check_rolling_args(max_length, rows)
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        output_ids = self.language_model.generate_rolling(selected_region_features, max_length, rows=rows)
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
 

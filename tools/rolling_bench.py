@@ -1,0 +1,97 @@
+"""The decoder alone on the bench's region rows, lock step against rolling batch (no detector in the timed part), like
+tools/decode_only.py: the feature rows the detector and the selection produce for the bench's 32 synthetic images, repeated
+``--repeat`` times as one stream of sequences, decoded under bf16 autocast at ``--max-length`` either by ``LanguageModel.generate``
+- one call per repeat, every call in lock step over all its rows (``--mode generate``, which also runs on a tree without
+``generate_rolling``) - or by ONE ``LanguageModel.generate_rolling`` call over the stream on ``--rows`` decoder rows (``--mode
+rolling``; several ``--rows`` values = several configurations in one process).
+Usage: python tools/rolling_bench.py --mode rolling --rows 128 256 464 928 [--repeat 4] [--weights bench|ragged] [--runs 3]
+Prints one JSON line per configuration: sequences, length histogram, steps executed, the longest sequence's steps, sum of the
+steps every sequence needs / rows, ms per call (median of --runs after one warm-up), ms per step, generated tokens per second."""
+import argparse
+import collections
+import contextlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rgrg_amd  # noqa: E402
+from rgrg_amd import synth  # noqa: E402
+
+EOS = 50256
+
+
+def lengths(ids):
+    """Tokens of every row, BOS and EOS included (PAD = EOS: the first EOS behind the BOS ends the row)."""
+    body = ids[:, 1:]
+    is_eos = body == EOS
+    first = torch.where(is_eos.any(dim=1), is_eos.float().argmax(dim=1) + 1, torch.full((ids.shape[0],), body.shape[1], device=ids.device))
+    return (first + 1).cpu()
+
+
+def timed(fn, runs):
+    fn()   # warm-up: decoder, graph capture, work space
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return out, statistics.median(ms), ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("generate", "rolling"), required=True)
+    ap.add_argument("--rows", type=int, nargs="*", default=[128, 256, 464, 928])
+    ap.add_argument("--repeat", type=int, default=4)
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--max-length", type=int, default=128)
+    ap.add_argument("--weights", choices=("bench", "ragged"), default="bench")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="bf16")
+    ap.add_argument("--runs", type=int, default=3)
+    args = ap.parse_args()
+    model = rgrg_amd.ReportGenerationModel(pretrain_without_lm_model=True)
+    model.load_state_dict(synth.make_state_dict(0, args.weights))
+    model.to("cuda:0").eval()
+    lm = model.language_model
+    images = synth.make_images(args.images, 1234).to("cuda:0")
+    ctx = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.dtype == "bf16" else contextlib.nullcontext
+    with torch.no_grad(), ctx():
+        _, _, top, cd = model.object_detector(images)
+        _, batch = model.binary_classifier_region_selection(top, cd, return_loss=False)
+    batch = batch.float().contiguous()
+    stream = batch.repeat(args.repeat, 1).contiguous()
+    L = args.max_length
+    base = {"mode": args.mode, "weights": args.weights, "dtype": args.dtype, "max_length": L, "sequences": int(stream.shape[0]),
+            "rows_per_image_batch": int(batch.shape[0]), "repeat": args.repeat, "data": "synthetic weights and images"}
+
+    def report(extra, lens, steps, ms, all_ms):
+        tokens = int((lens - 1).sum())
+        hist = collections.Counter(lens.tolist())
+        print(json.dumps(dict(base, **extra, length_histogram={str(k): hist[k] for k in sorted(hist)}, steps=steps,
+                              longest_steps=int(lens.max()) - 1, tokens=tokens, ms=round(ms, 3), ms_runs=[round(m, 3) for m in all_ms],
+                              ms_per_step=round(ms / max(steps, 1), 4), tokens_per_s=round(tokens / ms * 1e3, 1))), flush=True)
+
+    with torch.no_grad(), ctx():
+        if args.mode == "generate":
+            def run():
+                return [lm.generate(batch, max_length=L) for _ in range(args.repeat)]
+            outs, ms, all_ms = timed(run, args.runs)
+            lens = torch.cat([lengths(o) for o in outs])
+            report({"rows": int(batch.shape[0])}, lens, sum(int(o.shape[1]) - 1 for o in outs), ms, all_ms)
+        else:
+            for R in args.rows:
+                ids, ms, all_ms = timed(lambda: lm.generate_rolling(stream, L, rows=R), args.runs)
+                lens = lengths(ids)
+                steps = int(model.engine().last_rolling_steps)
+                report({"rows": R, "work_steps_per_row": round(int((lens - 1).sum()) / R, 2)}, lens, steps, ms, all_ms)
+
+
+if __name__ == "__main__":
+    main()
