@@ -819,7 +819,7 @@ int rgrg_balanced_sample(const int* matched, const int64_t* gt_labels, int G, co
  * then 4 deltas per anchor) from the sampler's outputs: anchors [A][4] shared by the images, gt [B][G][4]; labels and
  * regression targets (BoxCoder.encode, weights 1) of the sampled anchors are derived in the kernel from mask / matched.
  * out2[0] = loss_objectness (BCE over the sampled anchors, mean), out2[1] = loss_rpn_box_reg (smooth-L1 beta 1/9 over the
- * sampled positives / #sampled); nan when nothing is sampled. */
+ * sampled positives / #sampled); nan when nothing is sampled.  A must be a multiple of anchors_per_cell (RGRG_EINVAL). */
 int rgrg_rpn_loss_sampled_f32(const float* rpn_out, int ld, int anchors_per_cell, const int* matched, const float* gt, int G,
                               const float* anchors, const uint8_t* mask, const int* list, const int* count, int B, int A,
                               int batch, float* out2, void* stream);

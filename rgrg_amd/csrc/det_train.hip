@@ -503,7 +503,7 @@ extern "C" int rgrg_rpn_loss_sampled_f32(const float* rpn_out, int ld, int ancho
                                          int G, const float* anchors, const uint8_t* mask, const int* list, const int* count,
                                          int B, int A, int batch, float* out2, void* stream) {
     RGRG_CHECK_ARG(rpn_out && matched && gt && anchors && mask && list && count && out2 && B > 0 && A > 0 && G > 0 && batch > 0 &&
-                   anchors_per_cell > 0 && ld >= anchors_per_cell * 5);
+                   anchors_per_cell > 0 && ld >= anchors_per_cell * 5 && A % anchors_per_cell == 0);   // cell = (b A + i) / A_cell
     hipLaunchKernelGGL(rpn_loss_sampled_kernel, dim3(1), dim3(256), 0, as_stream(stream), rpn_out, ld, anchors_per_cell, matched, gt,
                        G, anchors, mask, list, count, B, A, batch, out2);
     RGRG_LAUNCH_CHECK();
