@@ -223,6 +223,26 @@ int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats, int S, in
 int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
                          int64_t* ids, int ld_ids, int* lens, int S, int R, int max_length, const float* ukv, int ld_ukv, void* kv,
                          size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, void* stream);
+/* Rolling-batch sampling: rgrg_decoder_generate_rolling with every arg-max replaced by the draw of "Sampling" below.  feats [S,1024];
+ * every feature row s has n hypotheses, sequences q = s * n + j (j < n), S * n sequences in all, which flow through the R rows in
+ * the order of q.  The n sequences of a feature row share its image key / value: the prefill runs over the S feature rows only.
+ * Sequence q draws the token of column c under the Philox counter (q, c - 1) - the counter of rgrg_decoder_sample for its row q at
+ * step c - 1; neither the decoder row that holds q nor the step of the call enters it, so the result does not depend on R beyond
+ * what the step plan of R rows does to the logits.  ids_out int64 / logprobs_out f32 (or NULL) [S*n][max_length] and lens_out int32
+ * [S*n] on the device: BOS, the tokens, PAD behind the last one; the log-prob of every drawn token, 0 in the BOS column and under
+ * PAD.  top_k = 1 gives the ids of rgrg_decoder_generate_rolling.  *steps_out, use_graph, `stream` and the refusals are those of
+ * rgrg_decoder_generate_rolling (the bound with S * n sequences), the parameter refusals those of rgrg_decoder_sample.  One captured
+ * step per (R, plan) serves every seed and parameter set. */
+int rgrg_decoder_sample_rolling(rgrg_decoder* d, const float* feats, int S, int n, int R, int max_length, float temperature, int top_k,
+                                float top_p, uint64_t seed, int64_t* ids_out, float* logprobs_out, int* lens_out, int* steps_out,
+                                int use_graph, void* stream);
+/* Test hook: the rolling sampler of rgrg_decoder_sample_rolling (the launch behind the logits of its step) on the caller's state, all
+ * on the device.  logits f32 [R][ld] (V <= 53248 of every row are the logits; 16-byte loads when ld % 4 == 0 and logits is 16-byte
+ * aligned); row_seq / row_len int32 [R]: the sequence a row holds (-1 = idle) and its tokens so far (>= 1).  An active row r draws
+ * under the counter (row_seq[r], row_len[r] - 1) and writes the token to arg[r] and - lp not NULL - the log-prob to
+ * lp[row_seq[r] * ld_lp + row_len[r]]; nothing else is written, nothing at all for an idle row.  Synchronises `stream`. */
+int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len, float temperature,
+                           int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp, void* stream);
 /* ---- Sampling.  The sampler is a pure function of one fp32 logits row x[0..V), temperature > 0, top_k >= 0 (0 = off),
  * 0 < top_p <= 1 (1 = off), a 64-bit seed, a row counter r and a step t:
  *   temperature  z_i = x_i * inv_T, inv_T = 1.0f / temperature computed once on the host in fp32.
@@ -238,6 +258,10 @@ int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, int* row_pos,
  *                the first-occurrence arg-max, exactly what greedy returns.
  *   log-prob     log q(token) under the distribution the token was drawn from (after temperature and filters), fp32.
  * Deterministic: the same inputs give the same bits (masses are accumulated as 64-bit fixed-point integers, sample.hip).
+ *
+ * Rolling counter rule (rgrg_decoder_sample_rolling): the row counter r is the SEQUENCE q, not the decoder row that happens to
+ * decode it, and t = c - 1 for the token of column c of that sequence, not the step of the call: which row decodes a sequence,
+ * and when, does not enter the draw.
  *
  * rgrg_decoder_sample: rgrg_decoder_generate with the arg-max replaced by that draw, row counter r = the row, t = the step
  * (0 for the first generated token).  Same prefill, same out_ids / *out_len semantics (PAD after a row's EOS); out_logprobs

@@ -66,6 +66,8 @@ SIGNATURES = {
     "rgrg_decoder_generate_prompted": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i, C.POINTER(_i), _i, _p]),
     "rgrg_decoder_generate_rolling": (_i, [_p, _p, _i, _i, _i, _p, _p, C.POINTER(_i), _i, _p]),
     "rgrg_debug_roll_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _i, _p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _i, _p]),
+    "rgrg_decoder_sample_rolling": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _p, _p, _p, C.POINTER(_i), _i, _p]),
+    "rgrg_debug_roll_sample": (_i, [_p, C.c_int64, _i, _i, _p, _p, _f, _i, _f, C.c_uint64, _p, _p, _i, _p]),
     "rgrg_decoder_sample": (_i, [_p, _p, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_sample_logits_f32": (_i, [_p, C.c_int64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p]),
     "rgrg_decoder_beam_search": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),

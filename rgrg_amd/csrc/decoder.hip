@@ -1579,7 +1579,9 @@ static int enqueue_step_tiled(rgrg_decoder* d, const StepSpec& s, bool count) {
 // One decode step: the fused plan up to its row limit (128 token rows; 64 under autocast), the tiled plan above
 int enqueue_step(rgrg_decoder* d, const StepSpec& s, bool count) {
     const int rc = s.rows <= decode_row_limit(d) ? enqueue_step_fused(d, s, count) : enqueue_step_tiled(d, s, count);
-    return (rc || s.end != STEP_SAMPLE) ? rc : enqueue_sampler(d, s.rows);
+    if (rc) return rc;
+    if (s.end == STEP_SAMPLE) return enqueue_sampler(d, s.rows);
+    return s.end == STEP_ROLL_SAMPLE ? enqueue_roll_sample_end(d, s.rows) : RGRG_OK;
 }
 
 StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad) {

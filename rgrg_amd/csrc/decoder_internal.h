@@ -1,5 +1,5 @@
 // What the decoder's translation units (decoder.hip: the decode step and the object; decoder_beam.hip: beam search;
-// decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch greedy decoding) share: the rgrg_decoder object, its constants and the few host
+// decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch decoding, greedy and sampled) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
 #include <functional>
@@ -128,7 +128,8 @@ enum StepEnd {
     STEP_SAMPLE,   // d->logits, then the sampler and its bookkeeping (enqueue_sampler)
     STEP_BEAM,     // d->logits, then the ranking of nb beams per item in G groups, which the caller enqueues behind the step (G = 0: plain)
     STEP_BEAM_SAMPLE,  // d->logits, then the beam-sampling ranking of nb beams per item (beam_sample.hip), enqueued by the caller likewise
-    STEP_ROLL          // arg-max into d->roll.arg, then the retire-and-refill kernels of rolling-batch decoding (decoder_roll.hip enqueue_roll_end)
+    STEP_ROLL,         // arg-max into d->roll.arg, then the retire-and-refill kernels of rolling-batch decoding (decoder_roll.hip enqueue_roll_end)
+    STEP_ROLL_SAMPLE   // d->logits, then the rolling sampler into d->roll.arg and the same two kernels (decoder_roll.hip enqueue_roll_sample_end)
 };
 struct StepSpec {
     int rows = 0;                      // sequences, or beam rows
@@ -144,6 +145,17 @@ struct StepSpec {
         return rows == o.rows && tok == o.tok && src == o.src && row_pos == o.row_pos && kv_first == o.kv_first && key_mask == o.key_mask &&
                row_step == o.row_step && end == o.end && nb == o.nb && G == o.G;
     }
+};
+
+// What changes from call to call of rolling-batch decoding (decoder_roll.hip): the kernels of a captured step read it from a device
+// block.  A call decodes S sequences, n per feature row: sequence q belongs to feature row q / n.
+struct RollCall {
+    long long* ids;       // [S][ld] the caller's output: column 0 BOS, PAD behind a sequence's last token
+    int* len;             // [S] tokens of every sequence, BOS included (0 until it has ended)
+    const float* ukv;     // [S / n][ld_ukv] image key / value rows of every layer (the ukv GEMM's output), one per FEATURE row
+    int ld, S, max_length, ld_ukv;
+    float* lp;            // [S][ld] log-probs of the drawn tokens (rolling sampling), or NULL
+    int n;                // sequences (hypotheses) per feature row
 };
 
 struct GraphEntry {
@@ -281,12 +293,12 @@ struct rgrg_decoder {
     hipEvent_t ev_fork = nullptr, ev_join[rgrg::MAX_CHAINS - 1] = {};
     int kv8 = 0;      // rgrg_decoder_set_kv_format: 1 = the many-sequence 16-bit step keeps its K/V cache as e4m3 bytes (attn_kv8.hip); survives
                       // precision changes and has no effect where the cache is fp32 (fp32 mode, the fused plans, forward_cached)
-    // rolling-batch greedy decoding (decoder_roll.hip).  Per decoder row [rows]: the sequence it holds (-1 = idle), that sequence's
+    // rolling-batch decoding, greedy and sampled (decoder_roll.hip).  Per decoder row [rows]: the sequence it holds (-1 = idle), that sequence's
     // length so far (BOS included), the token and the embedding position of its next step, its step (= the key count - 2), the arg-max
-    // of the step just run; list[2 k], list[2 k + 1] = row and sequence of the k-th refill of the step; shared[0] = the next pending
+    // - or the drawn token - of the step just run; list[2 k], list[2 k + 1] = row and sequence of the k-th refill of the step; shared[0] = the next pending
     // sequence, [1] = unfinished sequences, [2] = refills of the step, [3] = steps that had an active row.  call: the device block of
     // RollCall the captured kernels read what changes from call to call from; ukv [ukv_seqs][ld_ukv]: the image key / value rows of
-    // every sequence of the call (grown on demand, freed with the decoder)
+    // every feature row of the call (grown on demand, freed with the decoder)
     struct RollWork {
         int *seq = nullptr, *len = nullptr, *tok = nullptr, *pos = nullptr, *step = nullptr, *arg = nullptr, *list = nullptr, *shared = nullptr;
         void* call = nullptr;
@@ -371,6 +383,13 @@ int enqueue_sampler(rgrg_decoder* d, int S);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
 // decoder_roll.hip: the end of a STEP_ROLL step - the arg-max of R rows over their NT candidates, retire, refill
 int enqueue_roll_end(rgrg_decoder* d, int R, int NT);
+// ... and of a STEP_ROLL_SAMPLE step: the rolling sampler over the R logits rows, retire, refill
+int enqueue_roll_sample_end(rgrg_decoder* d, int R);
+// sample.hip: the rolling sampler - row r of logits [R][ld] holds sequence row_seq[r] (< 0: idle, nothing is written) at row_len[r]
+// tokens; an active row draws with the Philox counter (sequence, len - 1), the token -> arg[r], its log-prob ->
+// call->lp[sequence][len] (pitch call->ld; a NULL call->lp: no log-probs).  Parameters from the device block prm_dev.
+int launch_roll_sample(const float* logits, size_t ld, int R, int V, const void* prm_dev, const int* row_seq, const int* row_len,
+                       const RollCall* call, int* arg, hipStream_t st);
 int tf_reserve(rgrg_decoder* d, size_t rows);
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
                    int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr);

@@ -1,4 +1,4 @@
-// Rolling-batch greedy decoding (rgrg_decoder_generate_rolling): R decoder rows through which any number of sequences flow.  A row
+// Rolling-batch decoding - greedy (rgrg_decoder_generate_rolling) and sampled (rgrg_decoder_sample_rolling): R decoder rows through which any number of sequences flow.  A row
 // whose sequence has ended - EOS, or max_length tokens - takes the next pending sequence in the same step, so the work follows the
 // sum of the sequence lengths instead of sequences x the longest one, and the K/V cache is sized by R.
 //
@@ -10,18 +10,16 @@
 //   roll_refill_kernel   the image key / value of every sequence handed out -> slot 0 of its row's cache, all layers
 // What changes from call to call (output buffers, sequence count, max_length) is read from a device block, so one captured graph
 // per (R, plan) serves every call.
+//
+// Rolling sampling (STEP_ROLL_SAMPLE) is the same step with logits left and roll_sample_kernel (sample.hip) in
+// place of the arg-max: sequence q draws the token of column c under the Philox counter (q, c - 1), whichever row holds it.  A call
+// decodes n sequences per feature row; they share that row's image key / value (ukv row q / n).
 #include <algorithm>
 
 #include "decoder_internal.h"
 
 namespace rgrg {
 
-struct RollCall {
-    long long* ids;       // [S][ld] the caller's output: column 0 BOS, PAD behind a sequence's last token
-    int* len;             // [S] tokens of every sequence, BOS included (0 until it has ended)
-    const float* ukv;     // [S][ld_ukv] image key / value rows of every layer (the ukv GEMM's output)
-    int ld, S, max_length, ld_ukv;
-};
 struct RollRows {
     int *seq, *len, *tok, *pos, *step, *list, *shared;
 };
@@ -37,11 +35,14 @@ __global__ __launch_bounds__(256) void roll_argmax_kernel(const float* __restric
 }
 
 // The start of a call: the call block, every row idle, nothing handed out, and the output in its final form for a sequence that
-// never runs a step (BOS, then PAD).  One launch of roll_retire_kernel behind it hands out the first min(S, R) sequences.
+// never runs a step (BOS, then PAD; log-probs 0).  One launch of roll_retire_kernel behind it hands out the first min(S, R) sequences.
 __global__ __launch_bounds__(256) void roll_begin_kernel(const RollCall c, RollCall* __restrict__ call, const RollRows st, int R) {
     const size_t total = (size_t)c.S * c.max_length;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
         c.ids[(i / c.max_length) * c.ld + (i % c.max_length)] = (i % c.max_length) == 0 ? BOS_ID : PAD_ID;
+    if (c.lp)
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+            c.lp[(i / c.max_length) * c.ld + (i % c.max_length)] = 0.f;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < c.S; s += gridDim.x * blockDim.x) c.len[s] = 0;
     if (blockIdx.x == 0) {
         for (int r = threadIdx.x; r < R; r += 256) {
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
     }
 }
 
-// The image key / value of every sequence handed out in this step (the refill list) -> cache slot 0 of its row, every layer, with
+// The image key / value of every sequence handed out in this step (the refill list; ukv row sequence / n) -> cache slot 0 of its row, every layer, with
 // kv_slot0_kernel's rounding for the cache format (16 bit: to16_rt; fp32: the value).  Grid (layers * 2, ROLL_REFILL_ROWS): workgroup
 // (x, y) copies the D values of plane x for list entries y, y + gridDim.y, ...; a step without refills costs the empty launch.
 constexpr int ROLL_REFILL_ROWS = 32;
@@ -136,9 +137,9 @@ __global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict_
     const int n = shared[ROLL_REFILLS];
     const int l = blockIdx.x >> 1, kv = blockIdx.x & 1, D = H * 64;
     const float* ukv = call->ukv;
-    const int ld = call->ld_ukv;
+    const int ld = call->ld_ukv, per_row = call->n;
     for (int k = blockIdx.y; k < n; k += gridDim.y) {
-        const int r = list[2 * k], seq = list[2 * k + 1];
+        const int r = list[2 * k], seq = list[2 * k + 1] / per_row;
         for (int d = threadIdx.x; d < D; d += 256) {
             const int hd = d >> 6, e = d & 63;
             const float val = ukv[(size_t)seq * ld + ((size_t)l * 2 + kv) * D + d];
@@ -193,7 +194,7 @@ int roll_reserve(rgrg_decoder* d, int S) {
     return RGRG_OK;
 }
 
-// feature_space_transformation_nn and the uk / uv GEMM of all S sequences (enqueue_prefill's, in passes of up to max_seqs rows
+// feature_space_transformation_nn and the uk / uv GEMM of all S feature rows (enqueue_prefill's, in passes of up to max_seqs rows
 // through its work space; S <= max_seqs is one pass, the GEMM calls of rgrg_decoder_generate for S rows) -> roll.ukv
 int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
     const int D = d->D;
@@ -210,41 +211,37 @@ int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
 
 }  // namespace
 
-int enqueue_roll_end(rgrg_decoder* d, int R, int NT) {
-    hipLaunchKernelGGL(roll_argmax_kernel, dim3(R), dim3(256), 0, d->stream, d->cand_val, d->cand_idx, NT, d->roll.arg);
-    RGRG_LAUNCH_CHECK();
+static int roll_retire_refill(rgrg_decoder* d, int R) {
     const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
     return launch_retire_refill(roll_rows(d), d->roll.arg, static_cast<const RollCall*>(d->roll.call), R, d->kv, d->kv_layer_stride,
                                 d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream);
 }
 
-}  // namespace rgrg
+int enqueue_roll_end(rgrg_decoder* d, int R, int NT) {
+    hipLaunchKernelGGL(roll_argmax_kernel, dim3(R), dim3(256), 0, d->stream, d->cand_val, d->cand_idx, NT, d->roll.arg);
+    RGRG_LAUNCH_CHECK();
+    return roll_retire_refill(d, R);
+}
 
-using namespace rgrg;
+int enqueue_roll_sample_end(rgrg_decoder* d, int R) {
+    const int rc = launch_roll_sample(d->logits, (size_t)d->ld_logits, R, d->V, d->sample_prm, d->roll.seq, d->roll.len,
+                                      static_cast<const RollCall*>(d->roll.call), d->roll.arg, d->stream);
+    return rc ? rc : roll_retire_refill(d, R);
+}
 
-extern "C" int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats, int S, int R, int max_length, int64_t* ids_out,
-                                             int* lens_out, int* steps_out, int use_graph, void* stream) {
-    RGRG_CHECK_ARG(d && feats && ids_out && lens_out && S > 0);
-    if (R < 1 || R > d->max_seqs) {
-        set_error("rgrg_decoder_generate_rolling: %d decoder rows, the cache of this decoder holds 1 .. %d", R, d->max_seqs);
-        return RGRG_EINVAL;
-    }
-    if (max_length < 2 || max_length > d->max_len) {
-        set_error("rgrg_decoder_generate_rolling: max_length %d, 2 .. %d (the cache) are possible", max_length, d->max_len);
-        return RGRG_EINVAL;
-    }
-    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
-    if (fmt == KV_E4M3) {
-        set_error("rgrg_decoder_generate_rolling: the e4m3 K/V cache has no per-row step: call rgrg_decoder_set_kv_format(d, 0) first");
-        return RGRG_EINVAL;
-    }
+namespace {
+
+// What the two rolling entries share behind decode_begin: the S sequences - n per row of feats [S / n][1024] - through R rows with
+// steps that end in `end` (STEP_ROLL, or STEP_ROLL_SAMPLE with the parameter block already enqueued).
+int roll_run(rgrg_decoder* d, const char* who, const float* feats, int S, int n, int R, int max_length, StepEnd end, int64_t* ids_out,
+             float* lp_out, int* lens_out, int* steps_out, int use_graph) {
     int rc;
-    if ((rc = decode_begin(d, stream))) return rc;
-    if ((rc = roll_reserve(d, S))) return rc;
-    if ((rc = enqueue_roll_prefill(d, feats, S))) return rc;
+    if ((rc = roll_reserve(d, S / n))) return rc;
+    if ((rc = enqueue_roll_prefill(d, feats, S / n))) return rc;
     hipStream_t st = d->stream;
+    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
     const RollRows rows = roll_rows(d);
-    const RollCall call{reinterpret_cast<long long*>(ids_out), lens_out, d->roll.ukv, max_length, S, max_length, d->ld_ukv};
+    const RollCall call{reinterpret_cast<long long*>(ids_out), lens_out, d->roll.ukv, max_length, S, max_length, d->ld_ukv, lp_out, n};
     RollCall* dcall = static_cast<RollCall*>(d->roll.call);
     hipLaunchKernelGGL(roll_begin_kernel, dim3(64), dim3(256), 0, st, call, dcall, rows, R);
     RGRG_LAUNCH_CHECK();
@@ -254,7 +251,7 @@ extern "C" int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats
         return rc;
 
     StepSpec step;
-    step.rows = R; step.tok = d->roll.tok; step.row_pos = d->roll.pos; step.row_step = d->roll.step; step.end = STEP_ROLL;
+    step.rows = R; step.tok = d->roll.tok; step.row_pos = d->roll.pos; step.row_step = d->roll.step; step.end = end;
     hipGraphExec_t exec = nullptr;
     if (use_graph && (rc = step_graph(d, step, [&] { return enqueue_step(d, step, true); }, &exec))) return rc;
     // A sequence takes at most max_length - 1 steps and a free row never waits while a sequence is pending (list scheduling): all S
@@ -285,12 +282,58 @@ extern "C" int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats
     RGRG_HIP(hipStreamSynchronize(st));
     d->logits_stale_rows = 0;   // (logits_valid stays false: the last step's rows are idle ones)
     if (d->h_done[0] != 0) {
-        set_error("rgrg_decoder_generate_rolling: %d of %d sequences unfinished after the bound of %lld steps on %d rows", d->h_done[0], S,
-                  bound, R);
+        set_error("%s: %d of %d sequences unfinished after the bound of %lld steps on %d rows", who, d->h_done[0], S, bound, R);
         return RGRG_EHIP;
     }
     if (steps_out) *steps_out = d->h_done[1];
     return RGRG_OK;
+}
+
+// the refusals the two entries share, each with a message
+int roll_check(rgrg_decoder* d, const char* who, int R, int max_length) {
+    if (R < 1 || R > d->max_seqs) {
+        set_error("%s: %d decoder rows, the cache of this decoder holds 1 .. %d", who, R, d->max_seqs);
+        return RGRG_EINVAL;
+    }
+    if (max_length < 2 || max_length > d->max_len) {
+        set_error("%s: max_length %d, 2 .. %d (the cache) are possible", who, max_length, d->max_len);
+        return RGRG_EINVAL;
+    }
+    if ((KvFormat)rgrg_decoder_kv_format_in_use(d, R) == KV_E4M3) {
+        set_error("%s: the e4m3 K/V cache has no per-row step: call rgrg_decoder_set_kv_format(d, 0) first", who);
+        return RGRG_EINVAL;
+    }
+    return RGRG_OK;
+}
+
+}  // namespace
+
+}  // namespace rgrg
+
+using namespace rgrg;
+
+extern "C" int rgrg_decoder_generate_rolling(rgrg_decoder* d, const float* feats, int S, int R, int max_length, int64_t* ids_out,
+                                             int* lens_out, int* steps_out, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && feats && ids_out && lens_out && S > 0);
+    int rc;
+    if ((rc = roll_check(d, "rgrg_decoder_generate_rolling", R, max_length))) return rc;
+    if ((rc = decode_begin(d, stream))) return rc;
+    return roll_run(d, "rgrg_decoder_generate_rolling", feats, S, 1, R, max_length, STEP_ROLL, ids_out, nullptr, lens_out, steps_out,
+                    use_graph);
+}
+
+extern "C" int rgrg_decoder_sample_rolling(rgrg_decoder* d, const float* feats, int S, int n, int R, int max_length, float temperature,
+                                           int top_k, float top_p, uint64_t seed, int64_t* ids_out, float* logprobs_out, int* lens_out,
+                                           int* steps_out, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && feats && ids_out && lens_out && S > 0 && n > 0 && (long long)S * n < 0x7fffffffLL / 1024);
+    int rc;
+    if ((rc = roll_check(d, "rgrg_decoder_sample_rolling", R, max_length))) return rc;
+    if (!d->sample_prm && (rc = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return rc;
+    if ((rc = decode_begin(d, stream))) return rc;
+    // the parameter block lives in device memory: the captured step serves every seed and parameter set
+    if ((rc = enqueue_sample_params(d->sample_prm, temperature, top_k, top_p, seed, d->stream))) return rc;
+    return roll_run(d, "rgrg_decoder_sample_rolling", feats, S * n, n, R, max_length, STEP_ROLL_SAMPLE, ids_out, logprobs_out, lens_out,
+                    steps_out, use_graph);
 }
 
 // Test hook: ONE retire-and-refill step (roll_retire_kernel, roll_refill_kernel as the product launches them) on the caller's state.
@@ -311,7 +354,7 @@ extern "C" int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, in
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
     if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("rgrg_debug_roll_step: hipMalloc failed"); return RGRG_EHIP; }
-    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S, max_length, ld_ukv};
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S, max_length, ld_ukv, nullptr, 1};
     hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
     const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
     int rc = RGRG_OK;
@@ -325,6 +368,32 @@ extern "C" int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, in
     (void)hipFree(dcall);
     if (!rc && (e != hipSuccess || es != hipSuccess)) {
         set_error("rgrg_debug_roll_step: %s", hipGetErrorString(e != hipSuccess ? e : es));
+        return RGRG_EHIP;
+    }
+    return rc;
+}
+
+// Test hook: the rolling sampler (roll_sample_kernel as a STEP_ROLL_SAMPLE step launches it) on the caller's state.  Device: logits f32
+// [R][ld], row_seq / row_len / arg int32 [R], lp f32 [largest sequence + 1][ld_lp] or NULL.  Synchronises `stream`.
+extern "C" int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len,
+                                      float temperature, int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp,
+                                      void* stream) {
+    RGRG_CHECK_ARG(logits && row_seq && row_len && arg && R > 0 && R < 65536 && V > 0 && ld >= V && (!lp || ld_lp >= 2));
+    hipStream_t st = as_stream(stream);
+    void* prm = nullptr;
+    RollCall* dcall = nullptr;
+    RGRG_HIP(hipMalloc(&prm, sample_params_bytes()));
+    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(prm); set_error("rgrg_debug_roll_sample: hipMalloc failed"); return RGRG_EHIP; }
+    const RollCall call{nullptr, nullptr, nullptr, ld_lp, 0, 0, 0, lp, 1};
+    int rc = enqueue_sample_params(prm, temperature, top_k, top_p, seed, st);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
+    if (!rc && e == hipSuccess) rc = launch_roll_sample(logits, (size_t)ld, R, V, prm, row_seq, row_len, dcall, arg, st);
+    const hipError_t es = hipStreamSynchronize(st);   // the two blocks are the call's own: they must outlive the launches
+    (void)hipFree(prm);
+    (void)hipFree(dcall);
+    if (!rc && (e != hipSuccess || es != hipSuccess)) {
+        set_error("rgrg_debug_roll_sample: %s", hipGetErrorString(e != hipSuccess ? e : es));
         return RGRG_EHIP;
     }
     return rc;

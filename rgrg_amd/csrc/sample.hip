@@ -1,7 +1,8 @@
 // Token sampling on the device: temperature, top-k, top-p, one inverse-CDF draw and its log-probability per logits row, in
 // ONE launch (contract: include/rgrg_hip.h "Sampling").  One 1024-thread workgroup per row.  The row in registers,
 // the two filters and the fixed-point masses that make the result deterministic are in sample_device.h (shared with the
-// beam-sampling ranking, beam_sample.hip); here: the draw.  "Vocabulary order" is wave -> vector u -> lane -> element, so the
+// beam-sampling ranking, beam_sample.hip); here: the draw (sample_row), for the rows of a lock-step decode step or of caller-provided logits
+// (sample_kernel) and for the rows of rolling-batch sampling (roll_sample_kernel).  "Vocabulary order" is wave -> vector u -> lane -> element, so the
 // inverse-CDF scan needs one wave's prefix only.  The draw compares integers: running sum > floor(w24 x total / 2^24),
 // u = w24 2^-24.
 #include "decoder_internal.h"
@@ -9,23 +10,18 @@
 
 namespace rgrg {
 
-// logits [S][ld]; prm_dev (or, when null, prm_val) = the parameters; the Philox counter is (row0 + row, t) with t = *bk.step in
-// a decode step (bk.ids != null: the token and its log-prob go through record_step_token into ids / lp[row][t + 1]) and
-// t = step otherwise (out_tok / out_lp [S]).
+// The draw of one logits row x[0..V) by its workgroup of SM_THREADS threads, every thread of which calls this: filters, masses and
+// the inverse-CDF scan under the Philox counter (rr, t).  -> true in the ONE lane that holds the result (*tok, *logq); every other
+// thread returns false.  The body of sample_kernel and of roll_sample_kernel.
 template <bool VEC>
-__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, size_t ld, int V,
-                                                            const SampleParams* __restrict__ prm_dev, SampleParams prm_val, int step,
-                                                            int row0, int* __restrict__ out_tok, float* __restrict__ out_lp,
-                                                            StepBook bk, float* __restrict__ lp, int ld_lp) {
+__device__ __forceinline__ bool sample_row(const float* __restrict__ x, int V, const SampleParams& prm, unsigned rr, unsigned t,
+                                           int* tok_out, float* logq_out) {
     __shared__ u64 hist[256];
     __shared__ u64 sh_w[SM_WAVES];
     __shared__ unsigned sh_k[SM_WAVES];
     __shared__ u64 sh_a;
     __shared__ unsigned sh_prefix;
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SampleParams prm = prm_dev ? *prm_dev : prm_val;
-    const int t = bk.ids ? *bk.step : step;
-    const float* __restrict__ x = logits + (size_t)row * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     RowRegs r;
     r.base = wave * SM_SEG + lane * 4;
@@ -88,9 +84,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
 
     // the draw: first kept token, in vocabulary order, whose running mass exceeds u x total.  top_k == 1: the first kept token
     // (first-occurrence arg-max, what greedy returns)
-    const unsigned rr = (unsigned)(row0 + row);
-    const unsigned w24 = prm.top_k == 1 ? 0u
-                                        : philox4x32_10_first(rr, (unsigned)t, 0u, 0u, (unsigned)prm.seed, (unsigned)(prm.seed >> 32)) >> 8;
+    const unsigned w24 = prm.top_k == 1 ? 0u : philox4x32_10_first(rr, t, 0u, 0u, (unsigned)prm.seed, (unsigned)(prm.seed >> 32)) >> 8;
     const u64 T = (__umul64hi(total, (u64)w24) << 40) | ((total * (u64)w24) >> 24);   // floor(w24 total / 2^24) < total
     u64 run = 0;
     int wsel = 0;
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
         const bool before = run + sh_w[w] <= T;   // the crossing is behind wave w
         if (before && wsel == w) { run += sh_w[w]; wsel = w + 1; }
     }
-    if (wave != wsel) return;   // (wsel < SM_WAVES: the running mass reaches total > T)
+    if (wave != wsel) return false;   // (wsel < SM_WAVES: the running mass reaches total > T)
     u64 s[SM_NV];
 #pragma unroll
     for (int u = 0; u < SM_NV; ++u) {
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
     const u64 incl = run + wave_scan_u64(lane_s, lane);
     const u64 hit = __ballot(incl > T);
     const int L = __ffsll((long long)hit) - 1;
-    if (lane != L) return;
+    if (lane != L) return false;
     u64 c = incl - lane_s;
     unsigned kv[4];
 #pragma unroll
@@ -148,7 +142,25 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
     // (one lane, once per row: in double, so that the fp32 result carries one rounding and not those of z - z_max, of the
     // conversion of the total and of logf - together 2 ulp, measured against the float64 reference)
     const double logq_d = ((z == r.zmax) ? 0.0 : ((double)z - (double)r.zmax)) - (log((double)total) - 40.0 * 0.6931471805599453);
-    const float logq = (float)logq_d;
+    *tok_out = tok;
+    *logq_out = (float)logq_d;
+    return true;
+}
+
+// logits [S][ld]; prm_dev (or, when null, prm_val) = the parameters; the Philox counter is (row0 + row, t) with t = *bk.step in
+// a decode step (bk.ids != null: the token and its log-prob go through record_step_token into ids / lp[row][t + 1]) and
+// t = step otherwise (out_tok / out_lp [S]).
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, size_t ld, int V,
+                                                            const SampleParams* __restrict__ prm_dev, SampleParams prm_val, int step,
+                                                            int row0, int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                                            StepBook bk, float* __restrict__ lp, int ld_lp) {
+    const int row = blockIdx.x;
+    const SampleParams prm = prm_dev ? *prm_dev : prm_val;
+    const int t = bk.ids ? *bk.step : step;
+    int tok;
+    float logq;
+    if (!sample_row<VEC>(logits + (size_t)row * ld, V, prm, (unsigned)(row0 + row), (unsigned)t, &tok, &logq)) return;
     if (bk.ids) {
         bool was_finished;
         record_step_token(bk, row, t, tok, &was_finished);
@@ -157,6 +169,27 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
         out_tok[row] = tok;
         if (out_lp) out_lp[row] = logq;
     }
+}
+
+// The rolling sampler (rolling-batch sampling, decoder_roll.hip): row r holds sequence row_seq[r] at row_len[r] tokens and draws the
+// token of column len under the counter (sequence, len - 1) - the counter of sample_kernel for row = sequence at step len - 1, so
+// neither the decoder row nor the step of the call enters the draw.  The token goes to arg[r] (roll_retire_kernel appends it), the
+// log-prob to the sequence's own output row.  An idle row (sequence < 0) leaves as a whole workgroup before the first barrier.
+template <bool VEC>
+__global__ __launch_bounds__(SM_THREADS) void roll_sample_kernel(const float* __restrict__ logits, size_t ld, int V,
+                                                                 const SampleParams* __restrict__ prm_dev, const int* __restrict__ row_seq,
+                                                                 const int* __restrict__ row_len, const RollCall* __restrict__ call,
+                                                                 int* __restrict__ arg) {
+    const int row = blockIdx.x;
+    const int seq = row_seq[row];
+    if (seq < 0) return;
+    const int len = row_len[row];
+    int tok;
+    float logq;
+    if (!sample_row<VEC>(logits + (size_t)row * ld, V, *prm_dev, (unsigned)seq, (unsigned)(len - 1), &tok, &logq)) return;
+    arg[row] = tok;
+    float* lp = call->lp;
+    if (lp) lp[(size_t)seq * call->ld + len] = logq;
 }
 
 static int launch_sample(const float* logits, size_t ld, int S, int V, const SampleParams* prm_dev, SampleParams prm_val, int step,
@@ -169,6 +202,17 @@ static int launch_sample(const float* logits, size_t ld, int S, int V, const Sam
     else
         hipLaunchKernelGGL(sample_kernel<false>, dim3(S), dim3(SM_THREADS), 0, st, logits, ld, V, prm_dev, prm_val, step, row0, out_tok,
                            out_lp, bk, lp, ld_lp);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+int launch_roll_sample(const float* logits, size_t ld, int R, int V, const void* prm_dev, const int* row_seq, const int* row_len,
+                       const RollCall* call, int* arg, hipStream_t st) {
+    RGRG_CHECK_ARG(logits && R > 0 && V > 0 && V <= SM_WAVES * SM_SEG && ld >= (size_t)V && prm_dev && row_seq && row_len && call && arg);
+    const SampleParams* prm = static_cast<const SampleParams*>(prm_dev);
+    const bool vec = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(logits) % 16 == 0);
+    if (vec) hipLaunchKernelGGL(roll_sample_kernel<true>, dim3(R), dim3(SM_THREADS), 0, st, logits, ld, V, prm, row_seq, row_len, call, arg);
+    else hipLaunchKernelGGL(roll_sample_kernel<false>, dim3(R), dim3(SM_THREADS), 0, st, logits, ld, V, prm, row_seq, row_len, call, arg);
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
 }

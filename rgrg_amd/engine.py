@@ -804,6 +804,35 @@ class HipEngine:
         self.last_rolling_steps = steps.value
         return ids
 
+    def sample_decode_rolling(self, feats: Tensor, max_length: int, rows: Optional[int] = None, temperature: float = 1.0, top_k: int = 0,
+                              top_p: float = 1.0, seed: int = 0, num_return_sequences: int = 1, use_graph: bool = True, bf16=False,
+                              kv_fp8: bool = False) -> Tuple[Tensor, Tensor]:
+        """LanguageModel.sample_rolling (rgrg_decoder_sample_rolling): feats [S,1024] -> (ids int64 [S*n, L'], log-probs f32
+        [S*n, L']), the return of ``sample_decode``, with the S*n sequences (row s*n + j = hypothesis j of input row s) flowing through
+        ``rows`` decoder rows (None: min(S*n, ``rolling_rows_that_fit``)).  ``feats`` is passed unrepeated: the n hypotheses of a row
+        share its image key / value.  Sequence q draws the token of column c from the Philox counter (q, c - 1) under ``seed``,
+        whichever row decodes it.  ``last_rolling_steps`` as for ``greedy_decode_rolling``."""
+        _require_gpu(feats.device)
+        S, n, limit = feats.shape[0], int(num_return_sequences), int(max_length)
+        Q = S * n
+        fit = self.rolling_rows_that_fit(limit)
+        R = min(Q, fit) if rows is None else int(rows)
+        if R < 1 or R > fit:
+            raise _hip.RgrgHipError(f"rolling decode on {R} rows: a K/V cache of {limit} token slots holds 1 .. {fit} rows on this device")
+        lens = torch.zeros((Q,), dtype=torch.int32, device=feats.device)
+        steps = C.c_int(0)
+
+        def call(dec, f, out, lp, n_out):
+            rc = self.lib.rgrg_decoder_sample_rolling(dec, f, S, n, R, limit, float(temperature), int(top_k), float(top_p),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, out, lp, _hip.ptr(lens), C.byref(steps),
+                                                      1 if use_graph else 0, self._s())
+            if rc == 0:
+                n_out._obj.value = int(lens.max())   # sample()'s width: the longest sequence
+            return rc
+        ids, logprobs = self._decode_call("rgrg_decoder_sample_rolling", call, feats, R, Q, limit, bf16, kv_fp8, logprobs=True)
+        self.last_rolling_steps = steps.value
+        return ids, logprobs
+
     def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
                                use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
         """LanguageModel.greedy_search with a prompt (rgrg_decoder_generate_prompted): feats [S,1024], input_ids int64 [S,T],

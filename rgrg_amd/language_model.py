@@ -356,6 +356,29 @@ class LanguageModel(EngineOwner):
         return self.engine().greedy_decode_rolling(image_hidden_states, int(max_length), None if rows is None else int(rows), **modes)
 
     @torch.no_grad()
+    def sample_rolling(self, image_hidden_states: torch.FloatTensor, max_length: int, *, rows: Optional[int] = None,
+                       temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1,
+                       seed: Optional[int] = None, return_logprobs: bool = False):
+        """``sample`` in its serving form: the S*n sentences (n = num_return_sequences per row of ``image_hidden_states``) flow
+        through ``rows`` decoder rows as in ``generate_rolling``.  Same return contract as ``sample`` - int64
+        [S*n, L'], row s*n + j, BOS first, PAD after EOS, L' the longest sentence; with ``return_logprobs`` also fp32 [S*n, L'].
+        Sentence q draws the token of column c from the Philox counter (q, c - 1) under ``seed`` - ``sample``'s counter for its row
+        q - so which decoder row decodes a sentence, and when, does not enter the draw: on one step plan (fp32: up to 128 rows, or
+        above) the result is ``sample``'s, bit for bit, for every ``rows``.  Across step plans the logits differ by rounding and a
+        draw may differ with them.  ``top_k=1`` gives the ids of ``generate_rolling``.  The n hypotheses of a row share its image
+        key / value (one prefill row, not n); the K/V cache is sized by ``rows``, so S*n may exceed what one ``sample`` call
+        holds.  ``rows=None`` takes min(S*n, the rows a cache of ``max_length`` tokens can have on this device); ``seed=None``
+        draws the seed from torch's CPU generator.  Errors: those of ``sample`` and of ``generate_rolling``."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        check_rolling_args(max_length, rows)
+        modes = self._decode_modes(image_hidden_states.device)
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        ids, logprobs = self.engine().sample_decode_rolling(image_hidden_states, int(max_length), None if rows is None else int(rows),
+                                                            temperature, int(top_k), top_p, int(seed), int(num_return_sequences), **modes)
+        return (ids, logprobs) if return_logprobs else ids
+
+    @torch.no_grad()
     def greedy_search(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int],
                       **model_kwargs) -> torch.LongTensor:
         """language_model.py:609-652 with a prompt: continues ``input_ids`` [S,T] greedily and returns int64 [S, L'], the prompt in

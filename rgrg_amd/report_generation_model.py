@@ -208,6 +208,28 @@ class ReportGenerationModel(EngineOwner):
         return output_ids, selected_regions, detections, class_detected
 
     @torch.no_grad()
+    def sample_rolling(self, images: torch.FloatTensor, max_length: int, *, rows: Optional[int] = None, temperature: float = 1.0,
+                       top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed: Optional[int] = None,
+                       return_logprobs: bool = False):
+        """``sample`` with the sentences of the selected regions drawn by ``LanguageModel.sample_rolling``: the same 4-tuple
+        (``output_ids`` replaced by the sampler's return: ids, or (ids, logprobs) with ``return_logprobs``) or ``-1`` when no region
+        is selected.  Argument errors are ``sample``'s and ``generate_rolling``'s, raised before the detector runs."""
+        check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        check_rolling_args(max_length, rows)
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        output = self.language_model.sample_rolling(selected_region_features, max_length, rows=rows, temperature=temperature,
+                                                    top_k=top_k, top_p=top_p, num_return_sequences=num_return_sequences, seed=seed,
+                                                    return_logprobs=return_logprobs)
+        del selected_region_features
+        return output, selected_regions, detections, class_detected
+
+    @torch.no_grad()
     def generate_diverse(self, images: torch.FloatTensor, max_length: int, num_beams: int, num_beam_groups: int,
                          diversity_penalty: float, early_stopping: bool = False, num_return_sequences: int = 1):
         """``generate`` with the sentences of the selected regions decoded by ``LanguageModel.group_beam_search`` (diverse beam

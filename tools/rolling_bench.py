@@ -4,6 +4,11 @@ tools/decode_only.py: the feature rows the detector and the selection produce fo
 - one call per repeat, every call in lock step over all its rows (``--mode generate``, which also runs on a tree without
 ``generate_rolling``) - or by ONE ``LanguageModel.generate_rolling`` call over the stream on ``--rows`` decoder rows (``--mode
 rolling``; several ``--rows`` values = several configurations in one process).
+Sampling: ``--mode sample`` is ONE ``LanguageModel.sample`` call over the batch with ``--hypotheses`` n sequences per row (lock step over
+rows x n; runs on a tree without ``sample_rolling``), ``--mode sample-rolling`` ONE ``LanguageModel.sample_rolling`` call per
+``--rows`` value over the same rows and n, under ``--temperature / --top-k / --top-p / --seed``; ``--repeat`` is not used.  With
+``--prefill`` the rolling mode also times, at max_length 2 (one decode step per row hand-out), the call on the unrepeated rows
+against the call on the rows repeated n-fold with one hypothesis each: the difference is the prefill the shared image rows save.
 Usage: python tools/rolling_bench.py --mode rolling --rows 128 256 464 928 [--repeat 4] [--weights bench|ragged] [--runs 3]
 Prints one JSON line per configuration: sequences, length histogram, steps executed, the longest sequence's steps, sum of the
 steps every sequence needs / rows, ms per call (median of --runs after one warm-up), ms per step, generated tokens per second."""
@@ -47,7 +52,7 @@ def timed(fn, runs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("generate", "rolling"), required=True)
+    ap.add_argument("--mode", choices=("generate", "rolling", "sample", "sample-rolling"), required=True)
     ap.add_argument("--rows", type=int, nargs="*", default=[128, 256, 464, 928])
     ap.add_argument("--repeat", type=int, default=4)
     ap.add_argument("--images", type=int, default=32)
@@ -55,6 +60,12 @@ def main():
     ap.add_argument("--weights", choices=("bench", "ragged"), default="bench")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="bf16")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--hypotheses", type=int, default=4)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--prefill", action="store_true")
     args = ap.parse_args()
     model = rgrg_amd.ReportGenerationModel(pretrain_without_lm_model=True)
     model.load_state_dict(synth.make_state_dict(0, args.weights))
@@ -68,8 +79,14 @@ def main():
     batch = batch.float().contiguous()
     stream = batch.repeat(args.repeat, 1).contiguous()
     L = args.max_length
+    sampling = args.mode.startswith("sample")
+    draw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    if sampling:
+        stream = batch
     base = {"mode": args.mode, "weights": args.weights, "dtype": args.dtype, "max_length": L, "sequences": int(stream.shape[0]),
             "rows_per_image_batch": int(batch.shape[0]), "repeat": args.repeat, "data": "synthetic weights and images"}
+    if sampling:
+        base.update(draw, hypotheses=args.hypotheses, sequences=int(batch.shape[0]) * args.hypotheses, repeat=1)
 
     def report(extra, lens, steps, ms, all_ms):
         tokens = int((lens - 1).sum())
@@ -85,6 +102,22 @@ def main():
             outs, ms, all_ms = timed(run, args.runs)
             lens = torch.cat([lengths(o) for o in outs])
             report({"rows": int(batch.shape[0])}, lens, sum(int(o.shape[1]) - 1 for o in outs), ms, all_ms)
+        elif args.mode == "sample":
+            ids, ms, all_ms = timed(lambda: lm.sample(batch, L, num_return_sequences=args.hypotheses, **draw), args.runs)
+            report({"rows": int(ids.shape[0])}, lengths(ids), int(ids.shape[1]) - 1, ms, all_ms)
+        elif args.mode == "sample-rolling":
+            n = args.hypotheses
+            for R in args.rows:
+                ids, ms, all_ms = timed(lambda: lm.sample_rolling(batch, L, rows=R, num_return_sequences=n, **draw), args.runs)
+                lens = lengths(ids)
+                steps = int(model.engine().last_rolling_steps)
+                extra = {"rows": R, "work_steps_per_row": round(int((lens - 1).sum()) / R, 2)}
+                if args.prefill:
+                    rows_n = batch.repeat_interleave(n, 0).contiguous()
+                    _, shared, _ = timed(lambda: lm.sample_rolling(batch, 2, rows=R, num_return_sequences=n, **draw), 5)
+                    _, repeated, _ = timed(lambda: lm.sample_rolling(rows_n, 2, rows=R, num_return_sequences=1, **draw), 5)
+                    extra.update(ms_max_length_2_shared_rows=round(shared, 3), ms_max_length_2_rows_repeated=round(repeated, 3))
+                report(extra, lens, steps, ms, all_ms)
         else:
             for R in args.rows:
                 ids, ms, all_ms = timed(lambda: lm.generate_rolling(stream, L, rows=R), args.runs)
