@@ -243,6 +243,31 @@ int rgrg_decoder_sample_rolling(rgrg_decoder* d, const float* feats, int S, int 
  * lp[row_seq[r] * ld_lp + row_len[r]]; nothing else is written, nothing at all for an idle row.  Synchronises `stream`. */
 int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len, float temperature,
                            int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp, void* stream);
+/* Rolling-batch beam search: rgrg_decoder_beam_search over the S regions of feats [S,1024] with the regions flowing through
+ * G = min(R / num_beams, S) SLOTS of num_beams consecutive decoder rows (num_beams <= R <= max_seqs of the decoder; S is not bounded
+ * by it; rows behind G * num_beams are not used, and the step plan, precision and cache format are those of a step of G * num_beams
+ * rows).  Every slot has its own cur_len, heap and `done` flag.  A region leaves its slot when its scorer is done or when its cur_len
+ * reaches max_length; it is finalized then and the slot takes the next pending region in the same step - fresh rows at step 0 with
+ * beam scores 0, -1e9, ..., token BOS and the region's image key / value in slot 0 of the slot's first row; free slots take pending
+ * regions in ascending slot order, slots without a region idle.  The scorer is the one of rgrg_decoder_beam_search, on the host, with
+ * one synchronisation per step.  out_ids int64 [S * num_return_sequences][out_ld >= max_length] on the device and *out_len = L are
+ * what rgrg_decoder_beam_search returns for the same arguments: the same ids in the same order, the width L computed over all regions
+ * at the end.  *steps_out (host, optional): steps run, each with at least one occupied slot.  The prefill runs once over the S feature
+ * rows.  Synchronises `stream` before returning; use_graph = 0 launches the kernels eagerly.  More than 16 beams take the wide ranking
+ * kernels, as in lock step.
+ *   RGRG_EINVAL (with a message): R < num_beams or R > max_seqs; max_length outside 2 .. max_len; the e4m3 K/V cache in use for the rows.
+ *   RGRG_EHIP: regions unfinished after (ceil(S / G) + 1) * (max_length - 1) steps - the bound of any schedule; the loop stops there. */
+int rgrg_decoder_beam_search_rolling(rgrg_decoder* d, const float* feats, int S, int num_beams, int R, int max_length,
+                                     int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids, int out_ld,
+                                     int* out_len, int* steps_out, int use_graph, void* stream);
+/* Test hook: the turn kernel of rgrg_decoder_beam_search_rolling (beam_roll_turn_kernel: ancestor table and per-row step of the next
+ * step, one launch) on the caller's state, all int32 on the device.  src_old / src_new [R][T] are two buffers; parent [R]: the row of
+ * the row's slot (rows r / nb * nb .. + nb - 1) whose beam row r continues, -1 = fresh (the slot takes a new region), -2 = idle;
+ * step [R], updated in place, one value per slot among its continuing rows.  Continuing row r at step t: src_new[r][0..t] =
+ * src_old[parent][0..t], src_new[r][t + 1] = parent, step[r] = t + 1.  Fresh: src_new[r][0] = r / nb * nb, step[r] = 0.  Idle:
+ * step[r] = 0.  No other cell of src_new is written.  parent and step are read back and checked first (RGRG_EINVAL: a parent outside
+ * the slot, rows of a slot at different steps, a step outside 0 .. T - 2).  Synchronises `stream`. */
+int rgrg_debug_beam_roll_turn(const int* src_old, int* src_new, const int* parent, int* step, int T, int nb, int R, void* stream);
 /* ---- Sampling.  The sampler is a pure function of one fp32 logits row x[0..V), temperature > 0, top_k >= 0 (0 = off),
  * 0 < top_p <= 1 (1 = off), a 64-bit seed, a row counter r and a step t:
  *   temperature  z_i = x_i * inv_T, inv_T = 1.0f / temperature computed once on the host in fp32.
@@ -682,6 +707,16 @@ int rgrg_debug_attn_decode_first(const float* qkv, int ld_qkv, void* kcache, voi
 int rgrg_debug_attn_decode_rowstep(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* row_step, float* out,
                                    uint16_t* out16, int S, int H, int T_slots, int kv16, int fp16, int ni, int max_workgroups,
                                    void* stream);
+/* rgrg_debug_attn_decode_rowstep_src: the per-row-step variants WITH the ancestor table, attn_decode_kernel<true, ni, false, true>
+ * (kv16 = 0) and attn_decode_kv16_wave_kernel<true, fp16, false, false, true> (kv16 = 1) - the steps of
+ * rgrg_decoder_beam_search_rolling: row s reads slot j <= row_step[s] from cache row src[s][j] and stores its new k / v to slot
+ * row_step[s] + 1 of its own row.  A row at step t computes the bits rgrg_debug_attn_decode computes for it with the same src at
+ * *step_dev = t.  Everything else as rgrg_debug_attn_decode_rowstep.  row_step and src are read back and checked first (the call
+ * synchronises `stream`): RGRG_EINVAL for a step outside 0 .. T_slots - 2 and for a table entry of slots 0 .. row_step[s] + 1 outside
+ * 0 .. S - 1. */
+int rgrg_debug_attn_decode_rowstep_src(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* row_step, const int* src,
+                                       float* out, uint16_t* out16, int S, int H, int T_slots, int kv16, int fp16, int ni,
+                                       int max_workgroups, void* stream);
 /* rgrg_debug_attn_decode_beam_first: a beam step behind a left-padded prompt (rgrg_decoder_beam_search_prompted) - ancestor table
  * src [S][T_slots] AND first int32 [S] together (first is constant inside a beam group in the product; any values in [0, t] here).
  *   kv16 = 1: attn_decode_kv16_wave_kernel<true, fp16, false, true>, slots 1 .. first[s] left out of the softmax;

@@ -68,6 +68,8 @@ SIGNATURES = {
     "rgrg_debug_roll_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _i, _p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _i, _p]),
     "rgrg_decoder_sample_rolling": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _p, _p, _p, C.POINTER(_i), _i, _p]),
     "rgrg_debug_roll_sample": (_i, [_p, C.c_int64, _i, _i, _p, _p, _f, _i, _f, C.c_uint64, _p, _p, _i, _p]),
+    "rgrg_decoder_beam_search_rolling": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), C.POINTER(_i), _i, _p]),
+    "rgrg_debug_beam_roll_turn": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "rgrg_decoder_sample": (_i, [_p, _p, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_sample_logits_f32": (_i, [_p, C.c_int64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p]),
     "rgrg_decoder_beam_search": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), _p]),
@@ -122,6 +124,7 @@ SIGNATURES = {
     "rgrg_debug_attn_decode_qonly": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_first": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_rowstep": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_attn_decode_rowstep_src": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_beam_first": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p]),
     "rgrg_debug_attn_decode_kv8": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     "rgrg_debug_attn_prefill": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _i, _p]),

@@ -466,7 +466,8 @@ __device__ __forceinline__ void attn_chunk(const float* __restrict__ kc, const f
 // holds 0); the default instantiation carries none of it.
 // ROWSTEP (rolling-batch decoding, decoder_roll.hip): `step` is [S], the step of every sequence's OWN row - the workgroup of sequence s
 // reads step[s] where the others read the one word *step; everything behind t is the same code, so a row at its own step t gives the
-// bits the default instantiation gives at *step = t.
+// bits the default instantiation gives at *step = t.  With HAS_SRC (rolling beam search, decoder_beam_roll.hip) the two are orthogonal:
+// t, nkeys, slot and the chunk switch stay uniform over the workgroup (the wave, in the 16-bit kernel), the table is read per lane.
 template <bool HAS_SRC, int ATT_NI, bool HAS_MASK = false, bool ROWSTEP = false>  // HAS_SRC (beam search): per-slot ancestor table (one more dependent load per key, requested first)
 __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, int ld_qkv,
                                                           float* __restrict__ kc, float* __restrict__ vc,
@@ -1127,7 +1128,7 @@ struct AttnDecodeLaunch {
                                            // the kernel reads q only and stores nothing to the cache
     const int* first = nullptr;            // 16-bit cache: [S] padded prompt slots, cache slots 1 .. first[s] are left out (with src: not q_only)
     const int* row_step = nullptr;         // fp32 / 16-bit cache: [S] the step of every row on its own, instead of the one word *step (rolling-batch
-                                           // decoding); the plain form only - no table, no mask, no padded slots, not q_only
+                                           // decoding); plain or with src (rolling beam search) - no mask, no padded slots, not q_only
 };
 static int launch_attn_decode(const AttnDecodeLaunch& a) {
     if (a.kmask && a.fmt != KV_F32) {
@@ -1139,9 +1140,9 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
                   a.fmt == KV_E4M3 ? "e4m3 K/V cache" : "fp32 K/V cache: pass the additive mask");
         return RGRG_EINVAL;
     }
-    if (a.row_step && (a.src || a.kmask || a.first || a.q_only || a.fmt == KV_E4M3)) {
-        set_error("decode attention: the per-row step exists for the plain fp32 and 16-bit kernels (%s)",
-                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.src ? "ancestor table" : a.q_only ? "q-only" : "padding mask");
+    if (a.row_step && (a.kmask || a.first || a.q_only || a.fmt == KV_E4M3)) {
+        set_error("decode attention: the per-row step exists for the fp32 and 16-bit kernels, plain or with an ancestor table (%s)",
+                  a.fmt == KV_E4M3 ? "e4m3 K/V cache" : a.q_only ? "q-only" : a.first ? "padded prompt slots" : "padding mask");
         return RGRG_EINVAL;
     }
     const int* step = a.row_step ? a.row_step : a.step;   // the ROWSTEP instantiations take the rows' steps where the others take *step
@@ -1171,7 +1172,8 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
                                           a.S, a.H, a.T, a.src, a.f16, (int)wgrid.x, a.st);
 #define KV16_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kv16_wave_kernel<__VA_ARGS__>), wgrid, wblk, 0, a.st, a.qkv, a.ld_qkv, \
                                                   static_cast<u16*>(a.kc), static_cast<u16*>(a.vc), step, a.out, a.S, a.H, a.T, (a.first && !a.src) ? a.first : a.src, a.out16, a.first)
-        if (a.row_step) { if (a.f16) KV16_LAUNCH(false, true, false, false, true); else KV16_LAUNCH(false, false, false, false, true); }
+        if (a.row_step && a.src) { if (a.f16) KV16_LAUNCH(true, true, false, false, true); else KV16_LAUNCH(true, false, false, false, true); }   // rolling beams
+        else if (a.row_step) { if (a.f16) KV16_LAUNCH(false, true, false, false, true); else KV16_LAUNCH(false, false, false, false, true); }
         else if (a.first && a.src) {   // beam search behind a left-padded prompt
             if (a.f16) KV16_LAUNCH(true, true, false, true); else KV16_LAUNCH(true, false, false, true);
         } else if (a.first) {
@@ -1188,7 +1190,8 @@ static int launch_attn_decode(const AttnDecodeLaunch& a) {
         if (ni != 9 && ni != 2) { set_error("decode attention: %d keys per group, the kernel is built for 9 and 2", ni); return RGRG_EINVAL; }
 #define ATT_LAUNCH(...) hipLaunchKernelGGL((attn_decode_kernel<__VA_ARGS__>), grid, blk, 0, a.st, a.qkv, a.ld_qkv, static_cast<float*>(a.kc), \
                                                        static_cast<float*>(a.vc), step, a.out, a.S, a.H, a.T, a.src, a.frag_out, a.kmask)
-        if (a.row_step) { if (ni == 9) ATT_LAUNCH(false, 9, false, true); else ATT_LAUNCH(false, 2, false, true); }
+        if (a.row_step && a.src) { if (ni == 9) ATT_LAUNCH(true, 9, false, true); else ATT_LAUNCH(true, 2, false, true); }   // rolling beams
+        else if (a.row_step) { if (ni == 9) ATT_LAUNCH(false, 9, false, true); else ATT_LAUNCH(false, 2, false, true); }
         else if (a.kmask && a.src) {   // beam search behind a left-padded prompt (rgrg_decoder_beam_search_prompted)
             if (ni == 9) ATT_LAUNCH(true, 9, true); else ATT_LAUNCH(true, 2, true);
         } else if (a.kmask) {   // forward(use_cache=True) with a padded attention_mask (rgrg_decoder_forward_cached)
@@ -2066,6 +2069,42 @@ extern "C" int rgrg_debug_attn_decode_rowstep(const float* qkv, int ld_qkv, void
     AttnDecodeLaunch a{};
     a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
     a.row_step = row_step; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots;
+    a.fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.max_wgs = max_workgroups;
+    a.st = as_stream(stream);
+    return launch_attn_decode(a);
+}
+
+// Test hook: the per-row-step variants WITH an ancestor table (the steps of rgrg_decoder_beam_search_rolling) through the same launcher:
+// attn_decode_kernel<true, ni, false, true> / attn_decode_kv16_wave_kernel<true, fp16, false, false, true>.  row_step int32 [S] and
+// src int32 [S][T_slots] on the device; both are read back and checked first (one synchronisation): 0 <= row_step[s] <= T_slots - 2,
+// and every table entry a row can read - slots 0 .. row_step[s] + 1, the last one stale but requested - names a row 0 .. S - 1.
+extern "C" int rgrg_debug_attn_decode_rowstep_src(const float* qkv, int ld_qkv, void* kcache, void* vcache, const int* row_step,
+                                                  const int* src, float* out, uint16_t* out16, int S, int H, int T_slots, int kv16,
+                                                  int fp16, int ni, int max_workgroups, void* stream) {
+    RGRG_CHECK_ARG(qkv && kcache && vcache && row_step && src && S > 0 && H > 0 && T_slots >= 2 && ld_qkv >= 3 * H * 64);
+    RGRG_CHECK_ARG(out || (kv16 && out16));
+    RGRG_CHECK_ARG(kv16 || (!out16 && max_workgroups == 0));
+    RGRG_CHECK_ARG(!kv16 || ni == 0);
+    std::vector<int> host(S), tab((size_t)S * T_slots);
+    RGRG_HIP(hipStreamSynchronize(as_stream(stream)));
+    RGRG_HIP(hipMemcpy(host.data(), row_step, (size_t)S * sizeof(int), hipMemcpyDeviceToHost));
+    RGRG_HIP(hipMemcpy(tab.data(), src, tab.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int s = 0; s < S; ++s) {
+        if (host[s] < 0 || host[s] > T_slots - 2) {
+            set_error("rgrg_debug_attn_decode_rowstep_src: row_step[%d] = %d, a cache of %d slots takes 0 .. %d", s, host[s], T_slots, T_slots - 2);
+            return RGRG_EINVAL;
+        }
+        for (int j = 0; j <= host[s] + 1; ++j) {
+            const int r = tab[(size_t)s * T_slots + j];
+            if (r < 0 || r >= S) {
+                set_error("rgrg_debug_attn_decode_rowstep_src: src[%d][%d] = %d, the cache has rows 0 .. %d", s, j, r, S - 1);
+                return RGRG_EINVAL;
+            }
+        }
+    }
+    AttnDecodeLaunch a{};
+    a.qkv = qkv; a.ld_qkv = ld_qkv; a.kc = kcache; a.vc = vcache; a.plane_elems = (size_t)S * H * T_slots * 64;
+    a.row_step = row_step; a.src = src; a.out = out; a.out16 = out16; a.S = S; a.H = H; a.T = T_slots;
     a.fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32; a.f16 = fp16 ? 1 : 0; a.ni = ni; a.max_wgs = max_workgroups;
     a.st = as_stream(stream);
     return launch_attn_decode(a);

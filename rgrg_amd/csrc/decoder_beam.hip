@@ -350,9 +350,9 @@ __global__ __launch_bounds__(256) void beam_init_kernel(int* __restrict__ src, i
 // The two launches of a plain ranking, shared by beam_search_run and the test hooks (rgrg_debug_beam_row_topk / _merge), and the
 // one place that chooses the kernel.  More than 16 beams (K > BEAM_K): the K-round kernels on candidate rows K wide; up to 16: the
 // register lists, LIST >= K, on rows BEAM_K wide.  force_wide (the hooks only): the K-round kernels at any K.
-static bool beam_wide(int K, bool force_wide = false) { return force_wide || K > BEAM_K; }
+bool beam_wide(int K, bool force_wide) { return force_wide || K > BEAM_K; }
 // Row ranking of `rows` logits rows, K = 2 num_beams candidates each.
-static void launch_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum, float* top_val,
+void launch_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum, float* top_val,
                                  int* top_tok, bool force_wide, hipStream_t st) {
     if (beam_wide(K, force_wide)) {
         hipLaunchKernelGGL(beam_row_topk_wide_kernel, dim3(rows), dim3(BEAM_ROW_THREADS), 0, st, logits, ld, V, K, row_max, row_logsum,
@@ -366,7 +366,7 @@ static void launch_beam_row_topk(const float* logits, int ld, int V, int rows, i
 }
 // Item merge of S items with nb rows of K = 2 nb candidates (rows as launch_beam_row_topk left them); `score` [S][nb * K] is the
 // wide form's scratch.
-static void launch_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
+void launch_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok,
                               const float* beam_scores, int S, int nb, int V, float* score, float* out_score, int* out_tok, int* out_beam,
                               bool force_wide, hipStream_t st) {
     const int K = 2 * nb;
@@ -387,33 +387,117 @@ using namespace rgrg;
 // :597-605), restated on the host: hypothesis scores, worst_score and the is_done test are double arithmetic
 // (HF does them on Python floats obtained through .item()), beam scores stay float32.
 namespace rgrg {
-struct Hyp { double score; std::vector<long long> toks; };
-struct BeamHyps {
-    std::vector<Hyp> beams;
-    double worst = 1e9;
-    void add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp) {
-        const double score = sum_logprobs / std::pow((double)toks.size(), lp);
-        if ((int)beams.size() < nb || score > worst) {
-            beams.push_back({score, toks});
-            if ((int)beams.size() > nb) {
-                int i0 = 0;  // sorted([(score, idx)]): smallest (score, idx) is dropped, worst = the next one
-                for (int i = 1; i < (int)beams.size(); ++i)
-                    if (beams[i].score < beams[i0].score) i0 = i;
-                beams.erase(beams.begin() + i0);
-                double w = beams[0].score;
-                for (auto& h : beams) w = h.score < w ? h.score : w;
-                worst = w;
-            } else {
-                worst = score < worst ? score : worst;
-            }
+void BeamHyps::add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp) {
+    const double score = sum_logprobs / std::pow((double)toks.size(), lp);
+    if ((int)beams.size() < nb || score > worst) {
+        beams.push_back({score, toks});
+        if ((int)beams.size() > nb) {
+            int i0 = 0;  // sorted([(score, idx)]): smallest (score, idx) is dropped, worst = the next one
+            for (int i = 1; i < (int)beams.size(); ++i)
+                if (beams[i].score < beams[i0].score) i0 = i;
+            beams.erase(beams.begin() + i0);
+            double w = beams[0].score;
+            for (auto& h : beams) w = h.score < w ? h.score : w;
+            worst = w;
+        } else {
+            worst = score < worst ? score : worst;
         }
     }
-    bool is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const {
-        if ((int)beams.size() < nb) return false;
-        if (early) return true;
-        return worst >= best_sum_logprobs / std::pow((double)cur_len, lp);
+}
+bool BeamHyps::is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const {
+    if ((int)beams.size() < nb) return false;
+    if (early) return true;
+    return worst >= best_sum_logprobs / std::pow((double)cur_len, lp);
+}
+
+// BeamSearchScorer.process for ONE group of gs rows of one item (plain beam search: the item's one group of nb rows), shared by the
+// lock-step loop below and the rolling loop (decoder_beam_roll.hip).  sc / tok / beam: the group's 2 gs ranked candidates (beam = the
+// row within the item); item_row0: the item's first row in `ids`; nscore / ntok / nidx: the next score, token and parent row of the
+// group's gs rows.  The heap (capacity nb) and `done` belong to the ITEM: a finished item takes PAD.
+int beam_process_group(BeamHyps& hyps, char& done, const float* sc, const int* tok, const int* beam, int gs, int nb, int item_row0,
+                       const std::vector<std::vector<long long>>& ids, int cur_len, bool early, double lp, float* nscore, int* ntok,
+                       int* nidx) {
+    if (done) {
+        for (int j = 0; j < gs; ++j) { nscore[j] = 0.f; ntok[j] = PAD_ID; nidx[j] = 0; }
+        return RGRG_OK;
     }
-};
+    int beam_idx = 0;
+    for (int rank = 0; rank < 2 * gs; ++rank) {
+        const int row = item_row0 + beam[rank];
+        if (tok[rank] == EOS_ID) {
+            if (rank >= gs) continue;
+            hyps.add(ids[row], (double)sc[rank], nb, lp);
+        } else {
+            nscore[beam_idx] = sc[rank]; ntok[beam_idx] = tok[rank]; nidx[beam_idx] = row;
+            ++beam_idx;
+        }
+        if (beam_idx == gs) break;
+    }
+    if (beam_idx < gs) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
+    done = done || hyps.is_done((double)sc[0], cur_len, early, nb, lp);
+    return RGRG_OK;
+}
+
+// BeamSearchScorer.finalize for one item: an item that is not done adds its nb open beams (rows: ids / scores of its first row on)
+void beam_finalize_item(BeamHyps& hyps, bool done, const std::vector<long long>* rows, const float* scores, int nb, double lp) {
+    if (done) return;
+    for (int j = 0; j < nb; ++j) hyps.add(rows[j], (double)scores[j], nb, lp);
+}
+
+// ... and its output: the `keep` best hypotheses per item, padded to the width L over ALL items -> out_ids [S * keep][out_ld], *out_len = L
+int beam_write_best(const std::vector<BeamHyps>& hyps, int keep, int max_length, int64_t* out_ids, int out_ld, int* out_len, hipStream_t st) {
+    // num_beam_hyps_to_keep best hypotheses per item: sorted(beams, key=score) is stable and pop() takes the last, i.e.
+    // descending score and, among equal scores, the LATER-added hypothesis first
+    const int S = (int)hyps.size(), NR = S * keep;
+    std::vector<const std::vector<long long>*> best(NR);
+    int max_sent = 0;
+    for (int b = 0; b < S; ++b) {
+        const int nh = (int)hyps[b].beams.size();
+        if (nh < keep) { set_error("beam search: item %d has %d finished hypotheses, %d requested", b, nh, keep); return RGRG_ESTATE; }
+        std::vector<int> order(nh);
+        for (int j = 0; j < nh; ++j) order[j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hyps[b].beams[x].score < hyps[b].beams[y].score; });
+        for (int j = 0; j < keep; ++j) {
+            best[b * keep + j] = &hyps[b].beams[order[nh - 1 - j]].toks;
+            const int len = (int)best[b * keep + j]->size();
+            max_sent = len > max_sent ? len : max_sent;
+        }
+    }
+    const int L = (max_sent + 1 < max_length) ? max_sent + 1 : max_length;
+    std::vector<long long> dec((size_t)NR * L, PAD_ID);
+    for (int b = 0; b < NR; ++b) {
+        const int len = (int)best[b]->size();
+        for (int j = 0; j < len && j < L; ++j) dec[(size_t)b * L + j] = (*best[b])[j];
+        if (len < max_length) dec[(size_t)b * L + len] = EOS_ID;
+    }
+    RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), dec.data(), (size_t)L * sizeof(long long),
+                              (size_t)L * sizeof(long long), NR, hipMemcpyHostToDevice, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    *out_len = L;
+    return RGRG_OK;
+}
+
+// more than 16 beams: the K-wide candidate rows of the wide ranking kernels for R rows, grown on demand
+int beam_reserve_wide(rgrg_decoder* d, int R, int K) {
+    if (d->wide_cap >= (size_t)R * K) return RGRG_OK;
+    RGRG_HIP(hipStreamSynchronize(d->stream));
+    for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);   // (captured beam steps bake the buffers in)
+    d->graphs.clear();
+    for (void** q : {(void**)&d->wide_val, (void**)&d->wide_tok, (void**)&d->wide_score}) {   // grown: the smaller buffers go
+        if (!*q) continue;
+        auto it = std::find(d->allocs.begin(), d->allocs.end(), *q);
+        if (it != d->allocs.end()) d->allocs.erase(it);
+        (void)hipFree(*q);
+        *q = nullptr;
+    }
+    d->wide_cap = 0;
+    int r;
+    if ((r = dmalloc(d, (void**)&d->wide_val, (size_t)R * K * 4, true)) || (r = dmalloc(d, (void**)&d->wide_tok, (size_t)R * K * 4, true)) ||
+        (r = dmalloc(d, (void**)&d->wide_score, (size_t)R * K * 4, true)))
+        return r;
+    d->wide_cap = (size_t)R * K;
+    return RGRG_OK;
+}
 }  // namespace rgrg
 
 // prompt == NULL: the BOS start of rgrg_decoder_beam_search.  With a prompt (rgrg_decoder_beam_search_prompted, decoder_prompt.hip)
@@ -436,23 +520,9 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     RGRG_CHECK_ARG(R <= d->max_seqs && max_length >= 2 && max_length <= d->max_len && out_ld >= max_length);
     hipStream_t st = d->stream;
     const bool wide = beam_wide(K);   // more than 16 beams: the K-round ranking kernels on K-wide candidate rows
-    if (wide && d->wide_cap < (size_t)R * K) {
-        RGRG_HIP(hipStreamSynchronize(st));
-        for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);   // (captured beam steps bake the buffers in)
-        d->graphs.clear();
-        for (void** q : {(void**)&d->wide_val, (void**)&d->wide_tok, (void**)&d->wide_score}) {   // grown: the smaller buffers go
-            if (!*q) continue;
-            auto it = std::find(d->allocs.begin(), d->allocs.end(), *q);
-            if (it != d->allocs.end()) d->allocs.erase(it);
-            (void)hipFree(*q);
-            *q = nullptr;
-        }
-        d->wide_cap = 0;
-        int r;
-        if ((r = dmalloc(d, (void**)&d->wide_val, (size_t)R * K * 4, true)) || (r = dmalloc(d, (void**)&d->wide_tok, (size_t)R * K * 4, true)) ||
-            (r = dmalloc(d, (void**)&d->wide_score, (size_t)R * K * 4, true)))
-            return r;
-        d->wide_cap = (size_t)R * K;
+    if (wide) {
+        int r = beam_reserve_wide(d, R, K);
+        if (r) return r;
     }
     if (groups && !d->group_penalty) {
         int r = dmalloc(d, (void**)&d->group_penalty, sizeof(float), true);
@@ -549,26 +619,9 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
             for (int g = 0; g < G; ++g) {
                 const int r0 = b * nb + g * gs;            // the group's first row
                 const size_t c0 = (size_t)b * K + (size_t)g * 2 * gs;   // ... and first candidate slot
-                if (done[b]) {
-                    for (int j = 0; j < gs; ++j) { nscore[r0 + j] = 0.f; ntok[r0 + j] = PAD_ID; nidx[r0 + j] = 0; }
-                    continue;
-                }
-                int beam_idx = 0;
-                for (int rank = 0; rank < 2 * gs; ++rank) {
-                    const int tok = h_tok[c0 + rank];
-                    const float sc = h_score[c0 + rank];
-                    const int row = b * nb + h_beam[c0 + rank];
-                    if (tok == EOS_ID) {
-                        if (rank >= gs) continue;
-                        hyps[b].add(ids[row], (double)sc, nb, lp);
-                    } else {
-                        nscore[r0 + beam_idx] = sc; ntok[r0 + beam_idx] = tok; nidx[r0 + beam_idx] = row;
-                        ++beam_idx;
-                    }
-                    if (beam_idx == gs) break;
-                }
-                if (beam_idx < gs) { set_error("beam search: fewer than num_beams non-EOS candidates"); return RGRG_ESTATE; }
-                done[b] = done[b] || hyps[b].is_done((double)h_score[c0], cur_len, early_stopping != 0, nb, lp);
+                if ((rc = beam_process_group(hyps[b], done[b], h_score.data() + c0, h_tok.data() + c0, h_beam.data() + c0, gs, nb, b * nb, ids,
+                                             cur_len, early_stopping != 0, lp, nscore.data() + r0, ntok.data() + r0, nidx.data() + r0)))
+                    return rc;
             }
         }
         // input_ids = cat(input_ids[beam_idx], tokens); cache "re-order" = new ancestor table
@@ -595,39 +648,8 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         int* tmp = src_cur; src_cur = src_nxt; src_nxt = tmp;
     }
     // BeamSearchScorer.finalize (num_beam_hyps_to_keep = 1)
-    for (int b = 0; b < S; ++b) {
-        if (done[b]) continue;
-        for (int j = 0; j < nb; ++j) hyps[b].add(ids[b * nb + j], (double)beam_scores[b * nb + j], nb, lp);
-    }
-    // num_beam_hyps_to_keep best hypotheses per item: sorted(beams, key=score) is stable and pop() takes the last, i.e.
-    // descending score and, among equal scores, the LATER-added hypothesis first
-    const int keep = num_return_sequences, NR = S * keep;
-    std::vector<const std::vector<long long>*> best(NR);
-    int max_sent = 0, min_sent = 1 << 30;
-    for (int b = 0; b < S; ++b) {
-        const int nh = (int)hyps[b].beams.size();
-        if (nh < keep) { set_error("beam search: item %d has %d finished hypotheses, %d requested", b, nh, keep); return RGRG_ESTATE; }
-        std::vector<int> order(nh);
-        for (int j = 0; j < nh; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hyps[b].beams[x].score < hyps[b].beams[y].score; });
-        for (int j = 0; j < keep; ++j) {
-            best[b * keep + j] = &hyps[b].beams[order[nh - 1 - j]].toks;
-            const int len = (int)best[b * keep + j]->size();
-            max_sent = len > max_sent ? len : max_sent;
-            min_sent = len < min_sent ? len : min_sent;
-        }
-    }
-    const int L = (max_sent + 1 < max_length) ? max_sent + 1 : max_length;
-    std::vector<long long> dec((size_t)NR * L, PAD_ID);
-    for (int b = 0; b < NR; ++b) {
-        const int len = (int)best[b]->size();
-        for (int j = 0; j < len && j < L; ++j) dec[(size_t)b * L + j] = (*best[b])[j];
-        if (len < max_length) dec[(size_t)b * L + len] = EOS_ID;
-    }
-    RGRG_HIP(hipMemcpy2DAsync(out_ids, (size_t)out_ld * sizeof(int64_t), dec.data(), (size_t)L * sizeof(long long),
-                              (size_t)L * sizeof(long long), NR, hipMemcpyHostToDevice, st));
-    RGRG_HIP(hipStreamSynchronize(st));
-    *out_len = L;
+    for (int b = 0; b < S; ++b) beam_finalize_item(hyps[b], done[b] != 0, &ids[(size_t)b * nb], &beam_scores[(size_t)b * nb], nb, lp);
+    if ((rc = beam_write_best(hyps, num_return_sequences, max_length, out_ids, out_ld, out_len, st))) return rc;
     d->logits_valid = true;
     return RGRG_OK;
 }

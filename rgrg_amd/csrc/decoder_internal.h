@@ -1,5 +1,5 @@
 // What the decoder's translation units (decoder.hip: the decode step and the object; decoder_beam.hip: beam search;
-// decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch decoding, greedy and sampled) share: the rgrg_decoder object, its constants and the few host
+// decoder_beam_roll.hip: rolling-batch beam search; decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch decoding, greedy and sampled) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
 #include <functional>
@@ -158,6 +158,16 @@ struct RollCall {
     int n;                // sequences (hypotheses) per feature row
 };
 
+// BeamHypotheses of transformers 4.19.2 restated on the host (decoder_beam.hip): hypothesis scores, worst_score and the is_done test are
+// double arithmetic (HF does them on Python floats obtained through .item()), beam scores stay float32
+struct BeamHyp { double score; std::vector<long long> toks; };
+struct BeamHyps {
+    std::vector<BeamHyp> beams;
+    double worst = 1e9;
+    void add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp);
+    bool is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const;
+};
+
 struct GraphEntry {
     StepSpec spec;   // the step the graph was captured for
     hipGraphExec_t exec;
@@ -304,6 +314,7 @@ struct rgrg_decoder {
         void* call = nullptr;
         float* ukv = nullptr;
         size_t ukv_seqs = 0;
+        int host_refills = 0;   // enqueue_roll_refill_list: the host word the refill count is copied from
     } roll;
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
@@ -378,6 +389,20 @@ int launch_beam_sample_rank(const float* logits, size_t ld, int V, int S, int nb
                             const void* prm_val, const int* step_dev, int step, int row0, float* row_key, float* row_s, int* row_tok,
                             float* out_score, int* out_tok, int* out_beam, hipStream_t st);
 int check_beam_groups(const char* who, int num_beams, int num_beam_groups, float diversity_penalty, int num_return_sequences);
+// decoder_beam.hip, shared with the rolling loop (decoder_beam_roll.hip): the plain ranking's two launches and the one place that chooses
+// their kernel (K = 2 num_beams > BEAM_K: the K-round kernels on candidate rows K wide), the wide buffers for R rows, and the ONE
+// restatement of BeamSearchScorer - process (one item, one group's candidate list), finalize (one item), the padded output
+bool beam_wide(int K, bool force_wide = false);
+void launch_beam_row_topk(const float* logits, int ld, int V, int rows, int K, float* row_max, float* row_logsum, float* top_val,
+                          int* top_tok, bool force_wide, hipStream_t st);
+void launch_beam_merge(const float* row_max, const float* row_logsum, const float* top_val, const int* top_tok, const float* beam_scores,
+                       int S, int nb, int V, float* score, float* out_score, int* out_tok, int* out_beam, bool force_wide, hipStream_t st);
+int beam_reserve_wide(rgrg_decoder* d, int R, int K);
+int beam_process_group(BeamHyps& hyps, char& done, const float* sc, const int* tok, const int* beam, int gs, int nb, int item_row0,
+                       const std::vector<std::vector<long long>>& ids, int cur_len, bool early, double lp, float* nscore, int* ntok,
+                       int* nidx);
+void beam_finalize_item(BeamHyps& hyps, bool done, const std::vector<long long>* rows, const float* scores, int nb, double lp);
+int beam_write_best(const std::vector<BeamHyps>& hyps, int keep, int max_length, int64_t* out_ids, int out_ld, int* out_len, hipStream_t st);
 // decoder_sample.hip: the sampler behind the logits of S rows (the end of a STEP_SAMPLE step) and the start of every sampling entry
 int enqueue_sampler(rgrg_decoder* d, int S);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
@@ -385,6 +410,13 @@ int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top
 int enqueue_roll_end(rgrg_decoder* d, int R, int NT);
 // ... and of a STEP_ROLL_SAMPLE step: the rolling sampler over the R logits rows, retire, refill
 int enqueue_roll_sample_end(rgrg_decoder* d, int R);
+// ... and what rolling beam search (decoder_beam_roll.hip) shares with them: the work space for S feature rows, the refusals (R rows,
+// max_length, the e4m3 cache), feature_space_transformation_nn and the uk / uv GEMM of the S feature rows -> roll.ukv, and
+// roll_refill_kernel alone over a HOST-written refill list: n (row, feature row) pairs -> roll.list / roll.shared, then the launch
+int roll_reserve(rgrg_decoder* d, int S);
+int roll_check(rgrg_decoder* d, const char* who, int R, int max_length);
+int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S);
+int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R);
 // sample.hip: the rolling sampler - row r of logits [R][ld] holds sequence row_seq[r] (< 0: idle, nothing is written) at row_len[r]
 // tokens; an active row draws with the Philox counter (sequence, len - 1), the token -> arg[r], its log-prob ->
 // call->lp[sequence][len] (pitch call->ld; a NULL call->lp: no log-probs).  Parameters from the device block prm_dev.

@@ -172,6 +172,8 @@ RollRows roll_rows(const rgrg_decoder* d) {
     return RollRows{w.seq, w.len, w.tok, w.pos, w.step, w.list, w.shared};
 }
 
+}  // namespace
+
 int roll_reserve(rgrg_decoder* d, int S) {
     rgrg_decoder::RollWork& w = d->roll;
     int rc;
@@ -209,7 +211,27 @@ int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
     return RGRG_OK;
 }
 
-}  // namespace
+// roll_refill_kernel alone, for a scheduler that lives on the host (rolling beam search): the n (row, feature row) pairs of `pairs` -
+// host memory that stays valid until the stream has passed this point - go to roll.list, n to the refill count.  The device block
+// (roll.call) must hold the call's ukv / ld_ukv with n = 1.  n = 0 enqueues nothing.
+int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R) {
+    if (n <= 0) return RGRG_OK;
+    hipStream_t st = d->stream;
+    RGRG_HIP(hipMemcpyAsync(d->roll.list, pairs, 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    d->roll.host_refills = n;   // (outlives the call, like `pairs`)
+    RGRG_HIP(hipMemcpyAsync(d->roll.shared + ROLL_REFILLS, &d->roll.host_refills, sizeof(int), hipMemcpyHostToDevice, st));
+    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
+    const dim3 grid(d->n_layer * 2, std::min(n, ROLL_REFILL_ROWS));
+    const RollCall* call = static_cast<const RollCall*>(d->roll.call);
+    if (fmt == KV_F32)
+        hipLaunchKernelGGL(roll_refill_kernel<float>, grid, dim3(256), 0, st, d->roll.list, d->roll.shared, call, d->kv, d->kv_layer_stride,
+                           d->kv_kv_stride, d->H, d->T, 0);
+    else
+        hipLaunchKernelGGL(roll_refill_kernel<unsigned short>, grid, dim3(256), 0, st, d->roll.list, d->roll.shared, call,
+                           reinterpret_cast<unsigned short*>(d->kv), d->kv_layer_stride, d->kv_kv_stride, d->H, d->T, d->f16());
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 static int roll_retire_refill(rgrg_decoder* d, int R) {
     const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
@@ -289,7 +311,9 @@ int roll_run(rgrg_decoder* d, const char* who, const float* feats, int S, int n,
     return RGRG_OK;
 }
 
-// the refusals the two entries share, each with a message
+}  // namespace
+
+// the refusals the rolling entries share, each with a message
 int roll_check(rgrg_decoder* d, const char* who, int R, int max_length) {
     if (R < 1 || R > d->max_seqs) {
         set_error("%s: %d decoder rows, the cache of this decoder holds 1 .. %d", who, R, d->max_seqs);
@@ -305,8 +329,6 @@ int roll_check(rgrg_decoder* d, const char* who, int R, int max_length) {
     }
     return RGRG_OK;
 }
-
-}  // namespace
 
 }  // namespace rgrg
 

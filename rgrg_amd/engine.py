@@ -945,6 +945,27 @@ class HipEngine:
             dec, f, S, int(num_beams), limit, 1 if early_stopping else 0, float(length_penalty), int(num_return_sequences), out, limit, n,
             self._s()), feats, S * num_beams, S * int(num_return_sequences), limit, bf16, kv_fp8)
 
+    def beam_search_rolling(self, feats: Tensor, max_length: int, num_beams: int, rows: Optional[int] = None,
+                            early_stopping: bool = False, length_penalty: float = 1.0, num_return_sequences: int = 1,
+                            use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:
+        """LanguageModel.beam_search_rolling (rgrg_decoder_beam_search_rolling): feats [S,1024] -> int64 [S * num_return_sequences, L],
+        the return of ``beam_search``, with the S regions flowing through ``rows // num_beams`` slots of ``num_beams`` decoder rows
+        (None: min(S, ``rolling_rows_that_fit`` // num_beams) slots).  ``last_rolling_steps``: the steps the call ran, each with at
+        least one occupied slot."""
+        _require_gpu(feats.device)
+        S, nb, limit = feats.shape[0], int(num_beams), int(max_length)
+        fit = self.rolling_rows_that_fit(limit)
+        R = min(S, fit // nb) * nb if rows is None else int(rows)
+        if R < nb or R > fit:
+            raise _hip.RgrgHipError(f"rolling beam search on {R} rows: a K/V cache of {limit} token slots holds {nb} (one region of "
+                                    f"{nb} beams) .. {fit} rows on this device")
+        steps = C.c_int(0)
+        ids = self._decode_call("rgrg_decoder_beam_search_rolling", lambda dec, f, out, lp, n: self.lib.rgrg_decoder_beam_search_rolling(
+            dec, f, S, nb, R, limit, 1 if early_stopping else 0, float(length_penalty), int(num_return_sequences), out, limit, n,
+            C.byref(steps), 1 if use_graph else 0, self._s()), feats, R, S * int(num_return_sequences), limit, bf16, kv_fp8)
+        self.last_rolling_steps = steps.value
+        return ids
+
     def group_beam_search(self, feats: Tensor, max_length: int, num_beams: int, num_beam_groups: int, diversity_penalty: float,
                           early_stopping: bool = False, length_penalty: float = 1.0, bf16=False, num_return_sequences: int = 1,
                           kv_fp8: bool = False) -> Tensor:

@@ -160,6 +160,20 @@ def check_rolling_args(max_length, rows) -> None:
         raise ValueError(f"rows has to be a positive integer (the decoder rows the sequences flow through), but is {rows}")
 
 
+def check_rolling_beam_args(max_length, num_beams, rows, num_return_sequences) -> None:
+    """Argument errors of ``beam_search_rolling`` (LanguageModel) / ``generate_rolling_beam`` (ReportGenerationModel):
+    ``check_rolling_args`` plus the beam checks of ``generate``, raised before any GPU work."""
+    check_rolling_args(max_length, rows)
+    if int(num_beams) != num_beams or num_beams < 2:
+        raise ValueError(f"num_beams has to be an integer > 1 for beam search, but is {num_beams}")
+    if rows is not None and rows < num_beams:
+        raise ValueError(f"rows has to be at least num_beams (one region slot of {num_beams} decoder rows), but is {rows}")
+    if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+        raise ValueError(f"num_return_sequences has to be a positive integer, but is {num_return_sequences}")
+    if num_return_sequences > num_beams:
+        raise ValueError("'num_return_sequences' has to be smaller or equal to 'num_beams'.")
+
+
 class LanguageModel(EngineOwner):
     _engine_prefix = "language_model."
 
@@ -377,6 +391,24 @@ class LanguageModel(EngineOwner):
         ids, logprobs = self.engine().sample_decode_rolling(image_hidden_states, int(max_length), None if rows is None else int(rows),
                                                             temperature, int(top_k), top_p, int(seed), int(num_return_sequences), **modes)
         return (ids, logprobs) if return_logprobs else ids
+
+    @torch.no_grad()
+    def beam_search_rolling(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, *, rows: Optional[int] = None,
+                            early_stopping: bool = False, length_penalty: float = 1.0, num_return_sequences: int = 1) -> torch.LongTensor:
+        """Beam search in its serving form: the S regions of ``image_hidden_states`` flow through
+        ``G = rows // num_beams`` slots of ``num_beams`` consecutive decoder rows (``rows`` counts decoder rows); a region whose scorer
+        is done, or whose hypotheses have ``max_length`` tokens, leaves and its slot takes the next pending region in the same step.
+        The return of ``generate(num_beams=..)`` - int64 [S * num_return_sequences, L], the same ids, the same padded width L, the
+        same order - on one step plan (fp32: up to 128 rows, or above) bit for bit; the work follows the sum of the regions'
+        iterations instead of S x the slowest region, and the K/V cache is sized by ``rows``.  ``rows=None`` takes min(S, the rows
+        a cache of ``max_length`` tokens can have on this device // num_beams) slots.  ValueError: ``max_length`` None or < 2,
+        ``num_beams`` < 2, ``rows`` < ``num_beams``, ``num_return_sequences`` outside 1 .. ``num_beams``; RgrgHipError: more ``rows``
+        than that cache can have, and ``set_kv_cache_dtype("fp8_e4m3")`` where it would be used (the e4m3 attention kernel has no
+        per-row step).  torch.autocast opts into the 16-bit plans by the rows in use, as ``generate`` does by S * num_beams."""
+        check_rolling_beam_args(max_length, num_beams, rows, num_return_sequences)
+        modes = self._decode_modes(image_hidden_states.device)
+        return self.engine().beam_search_rolling(image_hidden_states, int(max_length), int(num_beams), None if rows is None else int(rows),
+                                                 bool(early_stopping), float(length_penalty), int(num_return_sequences), **modes)
 
     @torch.no_grad()
     def greedy_search(self, input_ids: torch.LongTensor, image_hidden_states: torch.FloatTensor, max_length: Optional[int],

@@ -14,7 +14,8 @@ from torch import Tensor
 from . import _hip
 from ._owner import EngineOwner
 from .binary_classifier import BinaryClassifierRegionAbnormal, BinaryClassifierRegionSelection
-from .language_model import LanguageModel, check_beam_sample_args, check_group_beam_args, check_rolling_args, check_sample_args
+from .language_model import (LanguageModel, check_beam_sample_args, check_group_beam_args, check_rolling_args, check_rolling_beam_args,
+                             check_sample_args)
 from .object_detector import ObjectDetector
 
 _LM = "language_model."
@@ -204,6 +205,27 @@ class ReportGenerationModel(EngineOwner):
         if selected_region_features.shape[0] == 0:
             return -1
         output_ids = self.language_model.generate_rolling(selected_region_features, max_length, rows=rows)
+        del selected_region_features
+        return output_ids, selected_regions, detections, class_detected
+
+    @torch.no_grad()
+    def generate_rolling_beam(self, images: torch.FloatTensor, max_length: int, num_beams: int, *, rows: Optional[int] = None,
+                              early_stopping: bool = False, length_penalty: float = 1.0, num_return_sequences: int = 1):
+        """``generate(num_beams=..)`` with the sentences of the selected regions decoded by ``LanguageModel.beam_search_rolling``: the
+        regions flow through ``rows // num_beams`` slots of beam rows instead of all being decoded in lock step.  The 4-tuple of
+        ``generate`` with the same output_ids, or ``-1`` when no region is selected.  Argument errors are
+        ``beam_search_rolling``'s, raised before the detector runs."""
+        check_rolling_beam_args(max_length, num_beams, rows, num_return_sequences)
+        _, detections, top_region_features, class_detected = self.object_detector(images)
+        del images
+        selected_regions, selected_region_features = self.binary_classifier_region_selection(
+            top_region_features, class_detected, return_loss=False)
+        del top_region_features
+        if selected_region_features.shape[0] == 0:
+            return -1
+        output_ids = self.language_model.beam_search_rolling(selected_region_features, max_length, num_beams, rows=rows,
+                                                             early_stopping=early_stopping, length_penalty=length_penalty,
+                                                             num_return_sequences=num_return_sequences)
         del selected_region_features
         return output_ids, selected_regions, detections, class_detected
 

@@ -6,7 +6,11 @@ tools/decode_only.py: the feature rows the detector and the selection produce fo
 rolling``; several ``--rows`` values = several configurations in one process).
 Sampling: ``--mode sample`` is ONE ``LanguageModel.sample`` call over the batch with ``--hypotheses`` n sequences per row (lock step over
 rows x n; runs on a tree without ``sample_rolling``), ``--mode sample-rolling`` ONE ``LanguageModel.sample_rolling`` call per
-``--rows`` value over the same rows and n, under ``--temperature / --top-k / --top-p / --seed``; ``--repeat`` is not used.  With
+``--rows`` value over the same rows and n, under ``--temperature / --top-k / --top-p / --seed``; ``--repeat`` is not used.
+Beam search: ``--beams N`` (N > 1, early stopping on) turns ``--mode generate`` into one ``LanguageModel.generate(num_beams=N)`` call per
+repeat (lock step over regions x N rows; runs on a tree without ``beam_search_rolling``) and ``--mode rolling`` into ONE
+``LanguageModel.beam_search_rolling`` call over the stream of regions per ``--rows`` value (decoder rows: rows // N slots); the JSON
+line then carries regions, regions per second and the K/V cache the decoder holds instead of the token figures.  With
 ``--prefill`` the rolling mode also times, at max_length 2 (one decode step per row hand-out), the call on the unrepeated rows
 against the call on the rows repeated n-fold with one hypothesis each: the difference is the prefill the shared image rows save.
 Usage: python tools/rolling_bench.py --mode rolling --rows 128 256 464 928 [--repeat 4] [--weights bench|ragged] [--runs 3]
@@ -66,6 +70,7 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--prefill", action="store_true")
+    ap.add_argument("--beams", type=int, default=0)
     args = ap.parse_args()
     model = rgrg_amd.ReportGenerationModel(pretrain_without_lm_model=True)
     model.load_state_dict(synth.make_state_dict(0, args.weights))
@@ -94,6 +99,31 @@ def main():
         print(json.dumps(dict(base, **extra, length_histogram={str(k): hist[k] for k in sorted(hist)}, steps=steps,
                               longest_steps=int(lens.max()) - 1, tokens=tokens, ms=round(ms, 3), ms_runs=[round(m, 3) for m in all_ms],
                               ms_per_step=round(ms / max(steps, 1), 4), tokens_per_s=round(tokens / ms * 1e3, 1))), flush=True)
+
+    def report_beams(extra, regions, steps, ms, all_ms):
+        cap_s, cap_l = model.engine()._decoder_caps
+        cache = model.engine().n_layer * 2 * cap_s * 16 * (cap_l + 1) * 64 * 4
+        print(json.dumps(dict(base, **extra, beams=args.beams, regions=regions, steps=steps, ms=round(ms, 3),
+                              ms_runs=[round(m, 3) for m in all_ms], ms_per_step=round(ms / max(steps, 1), 4),
+                              regions_per_s=round(regions / ms * 1e3, 1), kv_cache_rows=cap_s, kv_cache_mib=round(cache / 2 ** 20, 1))),
+              flush=True)
+
+    if args.beams > 1 and not sampling:
+        nb = args.beams
+        with torch.no_grad(), ctx():
+            if args.mode == "generate":
+                outs, ms, all_ms = timed(lambda: [lm.generate(batch, max_length=L, num_beams=nb, early_stopping=True)
+                                                  for _ in range(args.repeat)], args.runs)
+                # lock step runs until the slowest region is done: the output width is min(longest hypothesis + 1, max_length), so
+                # width - 1 counts the iterations exactly when a region ran to max_length and is a lower bound otherwise
+                report_beams({"rows": int(batch.shape[0]) * nb, "steps_are": "output width - 1 per call"}, int(stream.shape[0]),
+                             sum(int(o.shape[1]) - 1 for o in outs), ms, all_ms)
+            else:
+                for R in args.rows:
+                    _, ms, all_ms = timed(lambda: lm.beam_search_rolling(stream, L, nb, rows=R, early_stopping=True), args.runs)
+                    report_beams({"rows": R, "slots": min(R // nb, int(stream.shape[0]))}, int(stream.shape[0]),
+                                 int(model.engine().last_rolling_steps), ms, all_ms)
+        return
 
     with torch.no_grad(), ctx():
         if args.mode == "generate":
