@@ -243,6 +243,51 @@ int rgrg_decoder_sample_rolling(rgrg_decoder* d, const float* feats, int S, int 
  * lp[row_seq[r] * ld_lp + row_len[r]]; nothing else is written, nothing at all for an idle row.  Synchronises `stream`. */
 int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len, float temperature,
                            int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp, void* stream);
+/* ---- Rolling session: rolling-batch greedy decoding / sampling over an OPEN list.  One session per decoder; it owns the decoder's
+ * cache rows until it is closed.  Sequences are numbered q = 0, 1, 2, ... over the life of the session, n per submitted feature
+ * row (q / n is the feature row); the sampler's Philox counter stays (q, c - 1).  The session holds `capacity` feature rows, C =
+ * capacity * n sequences: output rows live in rings the decoder owns (ids / log-probs [C][max_length], lengths [C], row q % C; image
+ * key / value rows [capacity], row (q / n) % capacity).  The host keeps a watermark, the lowest sequence number not yet released.
+ * Every other decode entry on the decoder works as without a session and makes the session stale: its calls then fail with
+ * RGRG_EINVAL and a message containing "stale"; rgrg_decoder_roll_close still works.
+ *
+ * open: R rows, max_length, use_graph and the refusals of rgrg_decoder_generate_rolling (at open, the e4m3 cache included); sample != 0:
+ *   steps draw under (temperature, top_k, top_p, seed) as rgrg_decoder_sample_rolling, refusals of rgrg_decoder_sample.
+ *   RGRG_EINVAL: a session is open already; capacity < 1 or capacity * n >= 0x7fffffff / 1024.
+ * submit: m feature rows feats [m][1024] (device, `stream`'s) -> sequences *first_out .. *first_out + m * n - 1, in stream order behind the
+ *   steps already queued: the prefill GEMMs into the ukv ring, the new output rows (BOS, PAD, log-probs 0, length 0), S and the
+ *   unfinished count, one hand-out-only pass (idle rows take pending sequences in ascending row order; a row that holds a sequence is
+ *   not touched) and its refill.  RGRG_EINVAL before anything is enqueued, the session intact: the last new sequence at or beyond
+ *   watermark + C (the message names the capacity and the room left); sequence numbers at or beyond 0x7fffffff / 1024 (open a new
+ *   session).  Does not synchronise.
+ * advance: up to max_steps steps (< 0: until nothing is unfinished, bounded by (ceil(unfinished / R) + 1) * (max_length - 1), RGRG_EHIP
+ *   beyond), polled every 16 steps and 16 steps late as rgrg_decoder_generate_rolling; nothing is launched when the last poll said 0
+ *   and no submit has come since.  Synchronises.  *launched_out: steps launched; *unfinished_out: sequences pending or in a row;
+ *   *steps_out: the device's count of steps that had an active row, over the session.
+ * collect: sequences first .. first + count - 1 (watermark <= first, first + count <= submitted) -> ids_out int64 / logprobs_out f32
+ *   [count][max_length] on the device (either may be NULL) and lens_out int32 [count] on the HOST: the length of a finished sequence, 0
+ *   for one that has not finished as of the last advance.  Synchronises.
+ * release: the new watermark; RGRG_EINVAL when it moves backwards, beyond what was submitted, or past a sequence that has not
+ *   finished as of the last advance.
+ * close: synchronises, frees the rings.  No session open: RGRG_OK. */
+int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int n, int max_length, int sample, float temperature, int top_k,
+                           float top_p, uint64_t seed, int use_graph, void* stream);
+int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int m, long long* first_out, void* stream);
+int rgrg_decoder_roll_advance(rgrg_decoder* d, int max_steps, int* launched_out, int* unfinished_out, int* steps_out);
+int rgrg_decoder_roll_collect(rgrg_decoder* d, long long first, int count, int64_t* ids_out, float* logprobs_out, int* lens_out,
+                              void* stream);
+int rgrg_decoder_roll_release(rgrg_decoder* d, long long watermark);
+int rgrg_decoder_roll_close(rgrg_decoder* d);
+/* Test hook: what a session enqueues around one step, on the caller's state with a ring, all on the device.  Arrays as
+ * rgrg_debug_roll_step, but ids int64 / lp f32 (or NULL) [C][ld_ids], lens [C] and ukv [C / n][ld_ukv] are rings: sequence q uses row
+ * q % C and ukv row (q / n) % (C / n).  In this order: submit > 0: the new sequences S_before .. S_before + submit - 1 get their
+ * output rows (BOS, PAD, log-probs 0, length 0 - no other row is written), S and shared[1] grow by submit; handout != 0: the
+ * hand-out-only pass; retire != 0: a whole retire pass on arg.  Each pass is followed by its refill launch when ukv / kv are given.
+ * S_before is the sequence count before the submit.  Synchronises `stream`. */
+int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                                 int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before, int submit, int handout,
+                                 int retire, int R, int max_length, const float* ukv, int ld_ukv, void* kv, size_t layer_stride,
+                                 size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, void* stream);
 /* Rolling-batch beam search: rgrg_decoder_beam_search over the S regions of feats [S,1024] with the regions flowing through
  * G = min(R / num_beams, S) SLOTS of num_beams consecutive decoder rows (num_beams <= R <= max_seqs of the decoder; S is not bounded
  * by it; rows behind G * num_beams are not used, and the step plan, precision and cache format are those of a step of G * num_beams

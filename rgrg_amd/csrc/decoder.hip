@@ -1768,6 +1768,7 @@ extern "C" void rgrg_decoder_destroy(rgrg_decoder* d) {
     d->tr.free();
     if (d->tr.a16_scratch) (void)hipFree(d->tr.a16_scratch);
     if (d->roll.ukv) (void)hipFree(d->roll.ukv);
+    roll_session_free(d);
     if (d->h_done) (void)hipHostFree(d->h_done);
     for (hipEvent_t e : d->ev_poll)
         if (e) (void)hipEventDestroy(e);
@@ -1792,6 +1793,7 @@ int decode_begin(rgrg_decoder* d, void* stream) {
     RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(d->stream, d->ev_in, 0));
     d->logits_valid = false;   // until the call has completed (an early error return leaves no logits to copy)
+    ++d->epoch;                // an open rolling session is stale from here on
     return RGRG_OK;
 }
 int step_graph(rgrg_decoder* d, const StepSpec& s, const std::function<int()>& body, hipGraphExec_t* exec) {
@@ -1926,6 +1928,7 @@ extern "C" int rgrg_decoder_forward_cached(rgrg_decoder* d, const float* feats, 
         return RGRG_EINVAL;
     }
     hipStream_t caller = as_stream(stream), st = d->stream;
+    ++d->epoch;   // the cache rows are rewritten: an open rolling session is stale
     RGRG_HIP(hipEventRecord(d->ev_in, caller));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
     int rc;
@@ -1984,6 +1987,7 @@ extern "C" int rgrg_decoder_take_id_error(rgrg_decoder* d, int* pending) {
 extern "C" int rgrg_decoder_refresh_trainable(rgrg_decoder* d, void* stream) {
     RGRG_CHECK_ARG(d);
     hipStream_t caller = as_stream(stream), st = d->stream;
+    ++d->epoch;   // the cache rows are rewritten: an open rolling session is stale
     RGRG_HIP(hipEventRecord(d->ev_in, caller));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
     Lin* ls[] = {&d->fst0, &d->fst2, &d->ukv};
@@ -2266,6 +2270,7 @@ extern "C" int rgrg_decoder_set_precision(rgrg_decoder* d, int mode) {
     RGRG_CHECK_ARG(d && mode >= 0 && mode <= 2);
     if (mode == d->bf16_gemms) return RGRG_OK;
     const int prev = d->bf16_gemms;
+    ++d->epoch;   // an open rolling session is stale
     const int rc = set_precision_impl(d, mode);
     if (rc) {
         // a copy or an allocation failed half way: the decoder goes back to the mode it was in - whose copies may
@@ -2381,6 +2386,7 @@ extern "C" int rgrg_decoder_set_kv_format(rgrg_decoder* d, int fmt) {
     RGRG_HIP(hipStreamSynchronize(d->stream));
     d->kv8 = fmt;
     d->logits_valid = false;
+    ++d->epoch;   // an open rolling session is stale
     // captured graphs bake the attention kernel and the cache addresses in: drop them
     for (auto& g : d->graphs) (void)hipGraphExecDestroy(g.exec);
     d->graphs.clear();
@@ -2446,6 +2452,7 @@ extern "C" int rgrg_decoder_attention_only(rgrg_decoder* d, int S, int nkeys, in
 extern "C" int rgrg_decoder_trace_step(rgrg_decoder* d, int S, int nkeys, int iters, float* recs, int max_recs, int* n_out) {
     RGRG_CHECK_ARG(d && S > decode_row_limit(d) && S <= d->rows && nkeys >= 2 && nkeys <= d->T && recs && n_out && iters >= 0);
     d->logits_valid = false;
+    ++d->epoch;   // an open rolling session is stale
     std::vector<rgrg_decoder::TraceMark> marks;
     hipEvent_t base;
     RGRG_HIP(hipEventCreate(&base));
@@ -2481,6 +2488,7 @@ extern "C" int rgrg_decoder_time_step_parts(rgrg_decoder* d, int S, int nkeys, i
     // one_range: every launch covers all S rows (the kernels alone on the GPU at the step's full size), whatever the step's own
     // row-range split is; 0: as the step launches them (concurrent row ranges on forked streams where it does that)
     d->logits_valid = false;   // the replays below overwrite x / xn16 / the logits work space
+    ++d->epoch;   // an open rolling session is stale
     const int keep_chains = d->chains;
     if (one_range) d->chains = 1;
     struct Restore { rgrg_decoder* d; int c; ~Restore() { d->chains = c; } } restore{d, keep_chains};

@@ -533,6 +533,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
         if (!d->sample_prm && (r = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return r;
         if (!d->bsample_s && (r = dmalloc(d, (void**)&d->bsample_s, (size_t)d->rows * BEAM_K * sizeof(float), true))) return r;
     }
+    ++d->epoch;   // the cache rows are rewritten: an open rolling session is stale
     RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));
     RGRG_HIP(hipStreamWaitEvent(st, d->ev_in, 0));
     // ... and the sampling step its seed and parameters from this block: the graph of a spec serves every seed and parameter set

@@ -97,7 +97,7 @@ extern "C" int rgrg_decoder_beam_search_rolling(rgrg_decoder* d, const float* fe
     hipStream_t st = d->stream;
     // the prefill runs once over the S feature rows, not over S * num_beams: roll.ukv [S][ld_ukv]
     if ((rc = enqueue_roll_prefill(d, feats, S))) return rc;
-    const RollCall call{nullptr, nullptr, d->roll.ukv, 0, S, max_length, d->ld_ukv, nullptr, 1};   // what roll_refill_kernel reads: ukv, ld_ukv, n
+    const RollCall call{nullptr, nullptr, d->roll.ukv, 0, S, max_length, d->ld_ukv, nullptr, 1, S, S};   // what roll_refill_kernel reads: ukv, ld_ukv, n, Cf
     RGRG_HIP(hipMemcpyAsync(d->roll.call, &call, sizeof(call), hipMemcpyHostToDevice, st));
     RGRG_HIP(hipStreamSynchronize(st));   // `call` is this frame's
     hipLaunchKernelGGL(beam_roll_begin_kernel, dim3(64), dim3(256), 0, st, d->src_a, d->src_b, d->roll.step, d->T, nb, Ru);

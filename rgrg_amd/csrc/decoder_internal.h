@@ -156,6 +156,9 @@ struct RollCall {
     int ld, S, max_length, ld_ukv;
     float* lp;            // [S][ld] log-probs of the drawn tokens (rolling sampling), or NULL
     int n;                // sequences (hypotheses) per feature row
+    // Only the STORAGE is a ring (a rolling session): sequence q writes row q % C of ids / lp / len and reads row
+    // (q / n) % Cf of ukv.  A one-shot call passes C = S and Cf = S / n: q % C == q, the caller's buffers as they are.
+    int C, Cf;
 };
 
 // BeamHypotheses of transformers 4.19.2 restated on the host (decoder_beam.hip): hypothesis scores, worst_score and the is_done test are
@@ -316,6 +319,27 @@ struct rgrg_decoder {
         size_t ukv_seqs = 0;
         int host_refills = 0;   // enqueue_roll_refill_list: the host word the refill count is copied from
     } roll;
+    // Every decode entry that rewrites the cache rows, the step plan or the rolling state bumps the epoch (decode_begin and the
+    // entries that wait for the caller's stream themselves); an open rolling session remembers the one it was opened in.
+    unsigned long long epoch = 0;
+    // The rolling session (decoder_roll.hip): one per decoder.  ids / lp / len are the output rings the decoder owns
+    // ([C][max_length], [C]); h_len (pinned) mirrors len as of the last synchronisation, with 0 for every sequence submitted since.
+    struct RollSession {
+        bool open = false;
+        unsigned long long epoch = 0;
+        rgrg::RollCall call{};          // the host's copy of the device block (S = sequences submitted so far)
+        int R = 0, use_graph = 0;
+        rgrg::StepEnd end = rgrg::STEP_ROLL;
+        long long watermark = 0;        // the lowest sequence number not yet released
+        long long unfinished = 0;       // as of the last synchronisation, plus what was submitted since
+        bool drained = true;            // the last poll said 0 and no submit has come since: advance launches nothing
+        bool counted = false;           // the first eager step has been counted into the GEMM statistics
+        int steps = 0;                  // the device's count of steps that had an active row, as of the last synchronisation
+        long long* ids = nullptr;
+        float* lp = nullptr;
+        int* len = nullptr;
+        int* h_len = nullptr;
+    } sess;
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
                       // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log
@@ -415,7 +439,8 @@ int enqueue_roll_sample_end(rgrg_decoder* d, int R);
 // roll_refill_kernel alone over a HOST-written refill list: n (row, feature row) pairs -> roll.list / roll.shared, then the launch
 int roll_reserve(rgrg_decoder* d, int S);
 int roll_check(rgrg_decoder* d, const char* who, int R, int max_length);
-int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S);
+int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S, size_t ukv_row0 = 0);   // -> roll.ukv rows ukv_row0 .. + S - 1
+void roll_session_free(rgrg_decoder* d);   // the session's rings (rgrg_decoder_destroy, close)
 int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R);
 // sample.hip: the rolling sampler - row r of logits [R][ld] holds sequence row_seq[r] (< 0: idle, nothing is written) at row_len[r]
 // tokens; an active row draws with the Philox counter (sequence, len - 1), the token -> arg[r], its log-prob ->

@@ -61,9 +61,11 @@ __global__ __launch_bounds__(256) void roll_begin_kernel(const RollCall c, RollC
 //   FREE rows - just retired, or idle - take the pending sequences next, next + 1, ... in ascending row order as long as there
 //   are any: BOS, position 0, step 0, and (row, sequence) goes to the refill list.  A free row without a sequence is idle: it
 //   keeps the BOS state, runs along and writes nothing.
-// `next` advances by the sequences handed out, not by the free rows.
+// `next` advances by the sequences handed out, not by the free rows.  Sequence q writes ring row q % C of the output.
+// handout_only (the first hand-out of a call, a submit of a session): a row that holds a sequence is not touched - no append, no
+// retire, arg is not read - and the pass is not a step; idle rows take pending sequences as above.
 __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, const int* __restrict__ arg, const RollCall* __restrict__ call,
-                                                          int R) {
+                                                          int R, int handout_only) {
     __shared__ int wave_free[4];
     const RollCall c = *call;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -76,14 +78,15 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
         if (r < R) {
             const int seq = st.seq[r];
             is_free = seq < 0;
-            if (seq >= 0) {
+            if (seq >= 0 && !handout_only) {
                 ++active_in;
                 const int tok = arg[r];
                 int len = st.len[r];
-                c.ids[(size_t)seq * c.ld + len] = tok;
+                const int slot = seq % c.C;
+                c.ids[(size_t)slot * c.ld + len] = tok;
                 ++len;
                 if (tok == EOS_ID || len >= c.max_length) {
-                    c.len[seq] = len;
+                    c.len[slot] = len;
                     is_free = true;
                 } else {
                     st.len[r] = len; st.tok[r] = tok; st.pos[r] = len - 1; st.step[r] = len - 1;
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
     }
 }
 
-// The image key / value of every sequence handed out in this step (the refill list; ukv row sequence / n) -> cache slot 0 of its row, every layer, with
+// The image key / value of every sequence handed out in this step (the refill list; ukv ring row (sequence / n) % Cf) -> cache slot 0 of its row, every layer, with
 // kv_slot0_kernel's rounding for the cache format (16 bit: to16_rt; fp32: the value).  Grid (layers * 2, ROLL_REFILL_ROWS): workgroup
 // (x, y) copies the D values of plane x for list entries y, y + gridDim.y, ...; a step without refills costs the empty launch.
 constexpr int ROLL_REFILL_ROWS = 32;
@@ -137,9 +140,9 @@ __global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict_
     const int n = shared[ROLL_REFILLS];
     const int l = blockIdx.x >> 1, kv = blockIdx.x & 1, D = H * 64;
     const float* ukv = call->ukv;
-    const int ld = call->ld_ukv, per_row = call->n;
+    const int ld = call->ld_ukv, per_row = call->n, Cf = call->Cf;
     for (int k = blockIdx.y; k < n; k += gridDim.y) {
-        const int r = list[2 * k], seq = list[2 * k + 1] / per_row;
+        const int r = list[2 * k], seq = list[2 * k + 1] / per_row % Cf;
         for (int d = threadIdx.x; d < D; d += 256) {
             const int hd = d >> 6, e = d & 63;
             const float val = ukv[(size_t)seq * ld + ((size_t)l * 2 + kv) * D + d];
@@ -153,8 +156,8 @@ __global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict_
 namespace {
 
 int launch_retire_refill(const RollRows& st, const int* arg, const RollCall* call, int R, void* kv, size_t layer_stride, size_t kv_stride,
-                         int H, int T, int n_layer, KvFormat fmt, int f16, hipStream_t s) {
-    hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, s, st, arg, call, R);
+                         int H, int T, int n_layer, KvFormat fmt, int f16, hipStream_t s, int handout_only = 0) {
+    hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, s, st, arg, call, R, handout_only);
     RGRG_LAUNCH_CHECK();
     const dim3 grid(n_layer * 2, std::min(R, ROLL_REFILL_ROWS));
     if (fmt == KV_F32)
@@ -198,7 +201,7 @@ int roll_reserve(rgrg_decoder* d, int S) {
 
 // feature_space_transformation_nn and the uk / uv GEMM of all S feature rows (enqueue_prefill's, in passes of up to max_seqs rows
 // through its work space; S <= max_seqs is one pass, the GEMM calls of rgrg_decoder_generate for S rows) -> roll.ukv
-int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
+int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S, size_t ukv_row0) {
     const int D = d->D;
     int rc;
     for (int s0 = 0; s0 < S; s0 += d->max_seqs) {
@@ -206,7 +209,7 @@ int enqueue_roll_prefill(rgrg_decoder* d, const float* feats, int S) {
         RGRG_HIP(hipMemcpyAsync(d->feats, feats + (size_t)s0 * D, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
         if ((rc = linear(d, d->fst0, d->feats, nullptr, d->h1, M, D, RGRG_ACT_RELU, false))) return rc;
         if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, M, D, RGRG_ACT_NONE, false))) return rc;
-        if ((rc = linear(d, d->ukv, d->img, nullptr, d->roll.ukv + (size_t)s0 * d->ld_ukv, M, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
+        if ((rc = linear(d, d->ukv, d->img, nullptr, d->roll.ukv + (ukv_row0 + s0) * d->ld_ukv, M, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
     }
     return RGRG_OK;
 }
@@ -233,10 +236,10 @@ int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R) {
     return RGRG_OK;
 }
 
-static int roll_retire_refill(rgrg_decoder* d, int R) {
+static int roll_retire_refill(rgrg_decoder* d, int R, int handout_only = 0) {
     const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
     return launch_retire_refill(roll_rows(d), d->roll.arg, static_cast<const RollCall*>(d->roll.call), R, d->kv, d->kv_layer_stride,
-                                d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream);
+                                d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream, handout_only);
 }
 
 int enqueue_roll_end(rgrg_decoder* d, int R, int NT) {
@@ -263,13 +266,13 @@ int roll_run(rgrg_decoder* d, const char* who, const float* feats, int S, int n,
     hipStream_t st = d->stream;
     const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
     const RollRows rows = roll_rows(d);
-    const RollCall call{reinterpret_cast<long long*>(ids_out), lens_out, d->roll.ukv, max_length, S, max_length, d->ld_ukv, lp_out, n};
+    const RollCall call{reinterpret_cast<long long*>(ids_out), lens_out, d->roll.ukv, max_length, S, max_length, d->ld_ukv, lp_out, n, S, S / n};
     RollCall* dcall = static_cast<RollCall*>(d->roll.call);
     hipLaunchKernelGGL(roll_begin_kernel, dim3(64), dim3(256), 0, st, call, dcall, rows, R);
     RGRG_LAUNCH_CHECK();
-    // every row is idle: this hands the first min(S, R) sequences to rows 0, 1, ... and fills their slot 0 (roll.arg is not read)
+    // every row is idle: the hand-out-only pass gives the first min(S, R) sequences to rows 0, 1, ... and fills their slot 0
     if ((rc = launch_retire_refill(rows, d->roll.arg, dcall, R, d->kv, d->kv_layer_stride, d->kv_kv_stride, d->H, d->T, d->n_layer, fmt,
-                                   d->f16(), st)))
+                                   d->f16(), st, 1)))
         return rc;
 
     StepSpec step;
@@ -376,20 +379,303 @@ extern "C" int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, in
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
     if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("rgrg_debug_roll_step: hipMalloc failed"); return RGRG_EHIP; }
-    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S, max_length, ld_ukv, nullptr, 1};
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S, max_length, ld_ukv, nullptr, 1, S, S};
     hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
     const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
     int rc = RGRG_OK;
     if (e == hipSuccess) {
         if (kv) rc = launch_retire_refill(rows, arg, dcall, R, kv, layer_stride, kv_stride, H, T_slots, n_layer,
                                           kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32, fp16 ? 1 : 0, st);
-        else { hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, st, rows, arg, dcall, R); e = hipGetLastError(); }
+        else { hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, st, rows, arg, dcall, R, 0); e = hipGetLastError(); }
     }
     const hipError_t es = hipStreamSynchronize(st);   // the list and the call block are the call's own: they must outlive the launches
     (void)hipFree(list);
     (void)hipFree(dcall);
     if (!rc && (e != hipSuccess || es != hipSuccess)) {
         set_error("rgrg_debug_roll_step: %s", hipGetErrorString(e != hipSuccess ? e : es));
+        return RGRG_EHIP;
+    }
+    return rc;
+}
+
+// ---- The rolling session: the call above with an open list.  S grows by submits between steps, the output and the
+// ukv rows live in rings the decoder owns, finished sequences are collected and released in order while others run.
+namespace rgrg {
+
+// A submit of `count` sequences q0 .. q0 + count - 1 (c: the host's block, S = q0 still): their ring rows in the state
+// roll_begin_kernel gives a sequence that never ran - BOS then PAD, log-probs 0, len 0 - and nothing else; then S and the
+// unfinished word grow by count.  The kernels behind it in the stream see the new S.
+__global__ __launch_bounds__(256) void roll_submit_kernel(const RollCall c, RollCall* __restrict__ call, int* __restrict__ shared, int q0,
+                                                          int count) {
+    const size_t total = (size_t)count * c.max_length;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t o = (size_t)((q0 + (int)(i / c.max_length)) % c.C) * c.ld + (i % c.max_length);
+        c.ids[o] = (i % c.max_length) == 0 ? BOS_ID : PAD_ID;
+        if (c.lp) c.lp[o] = 0.f;
+    }
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x) c.len[(q0 + s) % c.C] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        call->S = q0 + count;
+        shared[ROLL_UNFINISHED] += count;
+    }
+}
+
+static int launch_roll_submit(const RollCall& c, RollCall* dcall, int* shared, int q0, int count, hipStream_t st) {
+    const int blocks = (int)std::min<size_t>(64, ((size_t)count * c.max_length + 255) / 256);
+    hipLaunchKernelGGL(roll_submit_kernel, dim3(std::max(blocks, 1)), dim3(256), 0, st, c, dcall, shared, q0, count);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
+void roll_session_free(rgrg_decoder* d) {
+    rgrg_decoder::RollSession& s = d->sess;
+    if (s.ids) (void)hipFree(s.ids);
+    if (s.lp) (void)hipFree(s.lp);
+    if (s.len) (void)hipFree(s.len);
+    if (s.h_len) (void)hipHostFree(s.h_len);
+    s = rgrg_decoder::RollSession{};
+}
+
+// the session every call but open and close needs: open, and no other decode entry has run on the decoder since
+static int roll_session_live(rgrg_decoder* d, const char* who) {
+    if (!d->sess.open) { set_error("%s: no rolling session is open on this decoder", who); return RGRG_EINVAL; }
+    if (d->sess.epoch != d->epoch) {
+        set_error("%s: the rolling session is stale: another decode call has used the decoder's cache rows since it was opened (close it and open a new one)", who);
+        return RGRG_EINVAL;
+    }
+    return RGRG_OK;
+}
+
+}  // namespace rgrg
+
+extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int n, int max_length, int sample, float temperature, int top_k,
+                                      float top_p, uint64_t seed, int use_graph, void* stream) {
+    RGRG_CHECK_ARG(d && n > 0);
+    const char* who = "rgrg_decoder_roll_open";
+    if (d->sess.open) { set_error("%s: a rolling session is already open on this decoder (one per decoder: close it first)", who); return RGRG_EINVAL; }
+    if (capacity < 1 || (long long)capacity * n >= 0x7fffffffLL / 1024) {
+        set_error("%s: a ring of %d feature rows x %d sequences, 1 .. %lld sequences are possible", who, capacity, n, 0x7fffffffLL / 1024 - 1);
+        return RGRG_EINVAL;
+    }
+    int rc;
+    if ((rc = roll_check(d, who, R, max_length))) return rc;
+    if ((rc = roll_reserve(d, capacity))) return rc;
+    if (sample && !d->sample_prm && (rc = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return rc;
+    rgrg_decoder::RollSession& s = d->sess;
+    const size_t C = (size_t)capacity * n;
+    if (hipMalloc((void**)&s.ids, C * max_length * sizeof(long long)) != hipSuccess || hipMalloc((void**)&s.len, C * sizeof(int)) != hipSuccess ||
+        (sample && hipMalloc((void**)&s.lp, C * max_length * sizeof(float)) != hipSuccess) ||
+        hipHostMalloc((void**)&s.h_len, C * sizeof(int)) != hipSuccess) {
+        roll_session_free(d);
+        set_error("%s: no memory for a ring of %zu sequences of %d tokens", who, C, max_length);
+        return RGRG_EHIP;
+    }
+    std::fill(s.h_len, s.h_len + C, 0);
+    if ((rc = decode_begin(d, stream)) || (sample && (rc = enqueue_sample_params(d->sample_prm, temperature, top_k, top_p, seed, d->stream)))) {
+        roll_session_free(d);
+        return rc;
+    }
+    s.call = RollCall{s.ids, s.len, d->roll.ukv, max_length, 0, max_length, d->ld_ukv, s.lp, n, (int)C, capacity};
+    s.R = R; s.use_graph = use_graph; s.end = sample ? STEP_ROLL_SAMPLE : STEP_ROLL;
+    // the device block, every row idle, nothing pending (S = 0: roll_begin_kernel writes no output row)
+    hipLaunchKernelGGL(roll_begin_kernel, dim3(1), dim3(256), 0, d->stream, s.call, static_cast<RollCall*>(d->roll.call), roll_rows(d), R);
+    if (hipGetLastError() != hipSuccess) { roll_session_free(d); set_error("%s: the launch of roll_begin_kernel failed", who); return RGRG_EHIP; }
+    s.epoch = d->epoch;
+    s.open = true;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int m, long long* first_out, void* stream) {
+    RGRG_CHECK_ARG(d && feats && m > 0);
+    const char* who = "rgrg_decoder_roll_submit";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    rgrg_decoder::RollSession& s = d->sess;
+    const int n = s.call.n, C = s.call.C, Cf = s.call.Cf;
+    const long long q0 = s.call.S, count = (long long)m * n;
+    if (q0 + count >= 0x7fffffffLL / 1024) {
+        set_error("%s: sequence numbers of a session stay below %lld (%lld submitted so far): open a new session", who, 0x7fffffffLL / 1024, q0);
+        return RGRG_EINVAL;
+    }
+    if (q0 + count > s.watermark + C) {
+        set_error("%s: %d feature rows (%lld sequences) do not fit the ring: capacity %d feature rows (%d sequences), room for %lld "
+                  "feature rows until finished sequences are collected and released", who, m, count, Cf, C, (s.watermark + C - q0) / n);
+        return RGRG_EINVAL;
+    }
+    RGRG_HIP(hipEventRecord(d->ev_in, as_stream(stream)));   // the feature rows are the caller's stream's
+    RGRG_HIP(hipStreamWaitEvent(d->stream, d->ev_in, 0));
+    // 1. the three GEMMs of the m rows into their ukv ring rows, split where the ring wraps
+    const int f0 = (int)((q0 / n) % Cf), head = std::min(m, Cf - f0);
+    if ((rc = enqueue_roll_prefill(d, feats, head, (size_t)f0))) return rc;
+    if (m > head && (rc = enqueue_roll_prefill(d, feats + (size_t)head * d->D, m - head, 0))) return rc;
+    // 2. + 3. the new output rows, S and the unfinished word; 4. idle rows take what is pending, their slot 0 is filled
+    if ((rc = launch_roll_submit(s.call, static_cast<RollCall*>(d->roll.call), d->roll.shared, (int)q0, (int)count, d->stream))) return rc;
+    for (long long q = q0; q < q0 + count; ++q) s.h_len[q % C] = 0;
+    s.call.S = (int)(q0 + count);
+    s.unfinished += count;
+    s.drained = false;
+    if ((rc = roll_retire_refill(d, s.R, 1))) return rc;
+    if (first_out) *first_out = q0;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_advance(rgrg_decoder* d, int max_steps, int* launched_out, int* unfinished_out, int* steps_out) {
+    RGRG_CHECK_ARG(d);
+    const char* who = "rgrg_decoder_roll_advance";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    rgrg_decoder::RollSession& s = d->sess;
+    hipStream_t st = d->stream;
+    const int R = s.R, L = s.call.max_length;
+    // until drained (max_steps < 0): the bound of roll_run over what is unfinished now
+    const long long bound = ((s.unfinished + R - 1) / R + 1) * (L - 1);
+    const long long limit = max_steps < 0 ? bound : max_steps;
+    long long launched = 0;
+    if (!s.drained && limit > 0) {
+        StepSpec step;
+        step.rows = R; step.tok = d->roll.tok; step.row_pos = d->roll.pos; step.row_step = d->roll.step; step.end = s.end;
+        hipGraphExec_t exec = nullptr;
+        if (s.use_graph && (rc = step_graph(d, step, [&] { return enqueue_step(d, step, true); }, &exec))) return rc;
+        // polled as roll_run polls: every 16 steps, waiting for the copy queued 16 steps earlier
+        int polls = 0;
+        d->h_done[1] = d->h_done[2] = 1;
+        for (long long t = 0; t < limit; ++t) {
+            if (exec) RGRG_HIP(hipGraphLaunch(exec, st));
+            else if ((rc = enqueue_step(d, step, !s.counted))) return rc;
+            s.counted = true;
+            ++launched;
+            if ((t & 15) == 15 && t + 1 < limit) {
+                if (polls > 0) {
+                    const int prev = (polls - 1) & 1;
+                    RGRG_HIP(hipEventSynchronize(d->ev_poll[prev]));
+                    if (d->h_done[1 + prev] == 0) break;
+                }
+                const int cur = polls & 1;
+                RGRG_HIP(hipMemcpyAsync(d->h_done + 1 + cur, d->roll.shared + ROLL_UNFINISHED, sizeof(int), hipMemcpyDeviceToHost, st));
+                RGRG_HIP(hipEventRecord(d->ev_poll[cur], st));
+                ++polls;
+            }
+        }
+    }
+    // (also when nothing was launched: a submit's hand-out pass may be queued, and the caller gets the device's counts)
+    if (launched > 0 || !s.drained) {
+        RGRG_HIP(hipMemcpyAsync(d->h_done, d->roll.shared + ROLL_UNFINISHED, sizeof(int), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipMemcpyAsync(d->h_done + 1, d->roll.shared + ROLL_STEPS, sizeof(int), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipMemcpyAsync(s.h_len, s.len, (size_t)s.call.C * sizeof(int), hipMemcpyDeviceToHost, st));
+        RGRG_HIP(hipStreamSynchronize(st));
+        d->logits_stale_rows = 0;
+        s.unfinished = d->h_done[0];
+        s.drained = s.unfinished == 0;
+        s.steps = d->h_done[1];
+    }
+    if (launched_out) *launched_out = (int)launched;
+    if (unfinished_out) *unfinished_out = (int)s.unfinished;
+    if (steps_out) *steps_out = s.steps;
+    if (max_steps < 0 && s.unfinished != 0) {
+        set_error("%s: %lld sequences unfinished after the bound of %lld steps on %d rows", who, s.unfinished, bound, R);
+        return RGRG_EHIP;
+    }
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_collect(rgrg_decoder* d, long long first, int count, int64_t* ids_out, float* logprobs_out, int* lens_out,
+                                         void* stream) {
+    RGRG_CHECK_ARG(d && count > 0 && lens_out);
+    const char* who = "rgrg_decoder_roll_collect";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    rgrg_decoder::RollSession& s = d->sess;
+    const int C = s.call.C, L = s.call.max_length;
+    if (first < s.watermark || first + count > s.call.S) {
+        set_error("%s: sequences %lld .. %lld, the ring holds %lld .. %d", who, first, first + count - 1, s.watermark, s.call.S - 1);
+        return RGRG_EINVAL;
+    }
+    if (logprobs_out && !s.lp) { set_error("%s: a greedy session keeps no log-probs", who); return RGRG_EINVAL; }
+    for (int i = 0; i < count; ++i) lens_out[i] = s.h_len[(first + i) % C];
+    if (ids_out) {
+        hipStream_t st = d->stream;
+        for (int i = 0; i < count;) {   // whole runs of ring rows
+            const int slot = (int)((first + i) % C), run = std::min(count - i, C - slot);
+            RGRG_HIP(hipMemcpyAsync(ids_out + (size_t)i * L, s.ids + (size_t)slot * L, (size_t)run * L * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+            if (logprobs_out)
+                RGRG_HIP(hipMemcpyAsync(logprobs_out + (size_t)i * L, s.lp + (size_t)slot * L, (size_t)run * L * sizeof(float), hipMemcpyDeviceToDevice, st));
+            i += run;
+        }
+        RGRG_HIP(hipStreamSynchronize(st));
+    }
+    (void)stream;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_release(rgrg_decoder* d, long long watermark) {
+    RGRG_CHECK_ARG(d);
+    const char* who = "rgrg_decoder_roll_release";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    rgrg_decoder::RollSession& s = d->sess;
+    if (watermark < s.watermark || watermark > s.call.S) {
+        set_error("%s: watermark %lld, %lld .. %d are possible", who, watermark, s.watermark, s.call.S);
+        return RGRG_EINVAL;
+    }
+    for (long long q = s.watermark; q < watermark; ++q)
+        if (s.h_len[q % s.call.C] == 0) {
+            set_error("%s: sequence %lld below the new watermark %lld has not finished", who, q, watermark);
+            return RGRG_EINVAL;
+        }
+    s.watermark = watermark;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_close(rgrg_decoder* d) {
+    RGRG_CHECK_ARG(d);
+    if (!d->sess.open) return RGRG_OK;
+    const hipError_t e = hipStreamSynchronize(d->stream);   // queued steps read the rings
+    roll_session_free(d);
+    if (e != hipSuccess) { set_error("rgrg_decoder_roll_close: %s", hipGetErrorString(e)); return RGRG_EHIP; }
+    return RGRG_OK;
+}
+
+// Test hook: what a session enqueues around one step, on the caller's state with a ring - submit-init of `submit` new sequences
+// (S_before .. S_before + submit - 1; 0: none), the hand-out-only pass (handout), a whole retire pass (retire), each pass with its
+// refill launch when ukv / kv are given.  Arrays as rgrg_debug_roll_step, but ids / lp [C][ld_ids], lens [C], ukv [C / n][ld_ukv].
+extern "C" int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared,
+                                            const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before,
+                                            int submit, int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv,
+                                            void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16,
+                                            int fp16, void* stream) {
+    RGRG_CHECK_ARG(row_seq && row_len && row_tok && row_pos && row_step && shared && arg && ids && lens);
+    RGRG_CHECK_ARG(C > 0 && n > 0 && C % n == 0 && S_before >= 0 && submit >= 0 && submit % n == 0 && submit <= C &&
+                   (long long)S_before + submit < 0x7fffffffLL / 1024);
+    RGRG_CHECK_ARG(R > 0 && R < 65536 && max_length >= 2 && ld_ids >= max_length);
+    RGRG_CHECK_ARG((ukv == nullptr) == (kv == nullptr));
+    RGRG_CHECK_ARG(!kv || (H > 0 && T_slots >= 2 && n_layer > 0 && ld_ukv >= n_layer * 2 * H * 64 && kv_stride >= (size_t)R * H * T_slots * 64 &&
+                           layer_stride >= 2 * kv_stride));
+    hipStream_t st = as_stream(stream);
+    int* list = nullptr;
+    RollCall* dcall = nullptr;
+    RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
+    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("rgrg_debug_roll_session_step: hipMalloc failed"); return RGRG_EHIP; }
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S_before, max_length, ld_ukv, lp, n, C, C / n};
+    hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
+    const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
+    const KvFormat fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32;
+    int rc = RGRG_OK;
+    auto pass = [&](int handout_only) {
+        if (kv) return launch_retire_refill(rows, arg, dcall, R, kv, layer_stride, kv_stride, H, T_slots, n_layer, fmt, fp16 ? 1 : 0, st, handout_only);
+        hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, st, rows, arg, dcall, R, handout_only);
+        RGRG_LAUNCH_CHECK();
+        return (int)RGRG_OK;
+    };
+    if (e == hipSuccess) {
+        if (submit > 0) rc = launch_roll_submit(call, dcall, shared, S_before, submit, st);
+        if (!rc && handout) rc = pass(1);
+        if (!rc && retire) rc = pass(0);
+    }
+    const hipError_t es = hipStreamSynchronize(st);   // the list and the call block are the call's own: they must outlive the launches
+    (void)hipFree(list);
+    (void)hipFree(dcall);
+    if (!rc && (e != hipSuccess || es != hipSuccess)) {
+        set_error("rgrg_debug_roll_session_step: %s", hipGetErrorString(e != hipSuccess ? e : es));
         return RGRG_EHIP;
     }
     return rc;
@@ -406,7 +692,7 @@ extern "C" int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, in
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc(&prm, sample_params_bytes()));
     if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(prm); set_error("rgrg_debug_roll_sample: hipMalloc failed"); return RGRG_EHIP; }
-    const RollCall call{nullptr, nullptr, nullptr, ld_lp, 0, 0, 0, lp, 1};
+    const RollCall call{nullptr, nullptr, nullptr, ld_lp, 0, 0, 0, lp, 1, 0x7fffffff, 0x7fffffff};   // no ring: the row is the sequence
     int rc = enqueue_sample_params(prm, temperature, top_k, top_p, seed, st);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);

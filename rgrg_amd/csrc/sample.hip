@@ -189,7 +189,7 @@ __global__ __launch_bounds__(SM_THREADS) void roll_sample_kernel(const float* __
     if (!sample_row<VEC>(logits + (size_t)row * ld, V, *prm_dev, (unsigned)seq, (unsigned)(len - 1), &tok, &logq)) return;
     arg[row] = tok;
     float* lp = call->lp;
-    if (lp) lp[(size_t)seq * call->ld + len] = logq;
+    if (lp) lp[(size_t)(seq % call->C) * call->ld + len] = logq;   // the sequence's ring row (a one-shot call: C = S, the row itself)
 }
 
 static int launch_sample(const float* logits, size_t ld, int S, int V, const SampleParams* prm_dev, SampleParams prm_val, int step,

@@ -113,6 +113,7 @@ class HipEngine:
         self._decoder = None
         self._kv = None        # the decoder's K/V cache: a torch tensor (caller-owned memory of rgrg_decoder_create_with_cache)
         self._cached = None
+        self._session = None   # the open rolling session (open_rolling): one per decoder
         self._init(state_dict)
 
     def _init(self, state_dict: Dict[str, Tensor]) -> None:
@@ -832,6 +833,42 @@ class HipEngine:
         ids, logprobs = self._decode_call("rgrg_decoder_sample_rolling", call, feats, R, Q, limit, bf16, kv_fp8, logprobs=True)
         self.last_rolling_steps = steps.value
         return ids, logprobs
+
+    def open_rolling(self, max_length: int, rows: int, capacity: Optional[int] = None, *, sample: Optional[dict] = None,
+                     use_graph: bool = True, bf16=False, kv_fp8: bool = False):
+        """A rolling session (rgrg_decoder_roll_open) on ``rows`` decoder rows: feature rows are submitted at any
+        time, steps advanced as far as the caller likes, finished sentences collected as they end -> ``RollingSession``.
+        ``capacity``: the feature rows the session holds at a time (None: 4 * rows sequences); ``sample``: None = greedy, or
+        ``dict(temperature, top_k, top_p, seed, num_return_sequences)``.  The decoder - cache, step plan, precision - is the one of
+        ``rows`` token rows in the modes given HERE; later submits use them.  One session per engine: ValueError while another is
+        open.  Any other decode call on the engine makes the session stale."""
+        from .rolling_session import RollingSession
+        _require_gpu(self.device)
+        R, limit = int(rows), int(max_length)
+        n = int(sample.get("num_return_sequences", 1)) if sample else 1
+        cap = -(-4 * R // n) if capacity is None else int(capacity)
+        if limit < 2 or R < 1 or n < 1:
+            raise ValueError(f"open_rolling: max_length {limit} (>= 2), rows {R} (>= 1) and {n} sequences per feature row (>= 1)")
+        if cap < 1:
+            raise ValueError(f"open_rolling: capacity has to be at least 1 feature row, but is {cap}")
+        old = getattr(self, "_session", None)
+        if old is not None and not old.closed:
+            if not old._known_stale and self._decoder is old._dec:
+                raise ValueError("a rolling session is already open on this engine (one per decoder): close it first")
+            old.close()
+        fit = self.rolling_rows_that_fit(limit)
+        if R > fit:
+            raise _hip.RgrgHipError(f"rolling decode on {R} rows: a K/V cache of {limit} token slots holds 1 .. {fit} rows on this device")
+        dec = self._get_decoder(R, limit)
+        self._cached = None
+        self._set_modes(dec, bf16, kv_fp8)
+        sp = sample or {}
+        _hip.check(self.lib.rgrg_decoder_roll_open(dec, R, cap, n, limit, 1 if sample else 0, float(sp.get("temperature", 1.0)),
+                                                   int(sp.get("top_k", 0)), float(sp.get("top_p", 1.0)),
+                                                   int(sp.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, 1 if use_graph else 0, self._s()),
+                   "rgrg_decoder_roll_open")
+        self._session = RollingSession(self, dec, R, cap, n, limit, bool(sample))
+        return self._session
 
     def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],
                                use_graph: bool = True, bf16=False, kv_fp8: bool = False) -> Tensor:

@@ -392,6 +392,36 @@ class LanguageModel(EngineOwner):
                                                             temperature, int(top_k), top_p, int(seed), int(num_return_sequences), **modes)
         return (ids, logprobs) if return_logprobs else ids
 
+    def open_rolling(self, max_length: int, *, rows: int, capacity: Optional[int] = None, do_sample: bool = False,
+                     temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1,
+                     seed: Optional[int] = None):
+        """``generate_rolling`` / ``sample_rolling`` (``do_sample``) over an OPEN list: a ``RollingSession`` on
+        ``rows`` decoder rows.  ``submit(feats)`` -> the range of sentence numbers q (n = num_return_sequences per feature row, in
+        submit order), at any time between steps; ``advance(steps=None)`` runs steps (None: until nothing is unfinished);
+        ``collect()`` -> ``(q, ids[, logprobs])`` of every sentence that has ended since, trimmed to its length; ``close()``, or use
+        it as a context manager.  Sentence q gets the tokens ``generate`` (the draws ``sample_rolling``: counter (q, c - 1)) gives
+        it.  ``capacity``: the feature rows held at a time (None: 4 * rows sentences); a submit beyond it raises RgrgHipError
+        until sentences in front have been collected.  Precision and step plan are those of ``rows`` under the autocast state of
+        THIS call.  Argument errors (ValueError, before any device work) are those of ``generate_rolling`` / ``sample_rolling``,
+        ``rows`` is required; any other decode call on the model makes the session stale (RgrgHipError "stale")."""
+        if do_sample:
+            check_sample_args(temperature, top_k, top_p, num_return_sequences)
+        elif num_return_sequences != 1:
+            raise ValueError("num_return_sequences has to be 1 without do_sample (greedy search has one hypothesis per row)")
+        check_rolling_args(max_length, rows)
+        if rows is None:
+            raise ValueError("rows has to be given for a rolling session (the decoder rows the sentences flow through)")
+        if capacity is not None and (int(capacity) != capacity or capacity < 1):
+            raise ValueError(f"capacity has to be a positive integer (the feature rows the session holds at a time), but is {capacity}")
+        modes = self._decode_modes(next(self.parameters()).device)
+        sample = None
+        if do_sample:
+            if seed is None:
+                seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            sample = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed),
+                          num_return_sequences=int(num_return_sequences))
+        return self.engine().open_rolling(int(max_length), int(rows), None if capacity is None else int(capacity), sample=sample, **modes)
+
     @torch.no_grad()
     def beam_search_rolling(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, *, rows: Optional[int] = None,
                             early_stopping: bool = False, length_penalty: float = 1.0, num_return_sequences: int = 1) -> torch.LongTensor:

@@ -1,0 +1,197 @@
+"""Rolling sessions: rolling-batch greedy decoding and sampling over an open list.  ``RollingSession`` is what
+``HipEngine.open_rolling`` / ``LanguageModel.open_rolling`` return - feature rows in, numbered sequences out -,
+``ReportRollingSession`` what ``ReportGenerationModel.open_rolling`` returns - images in, one ``generate_rolling`` result per
+submit out.  Every FLOP runs in ``librgrg_hip.so`` (rgrg_decoder_roll_*)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional
+
+import torch
+
+from . import _hip
+from .constants import PAD_TOKEN_ID
+
+
+class RollingSession:
+    """R decoder rows through which the sequences of any number of ``submit`` calls flow.  Sequences are numbered q = 0, 1, ... in
+    submit order, n per feature row.  The session holds ``capacity`` feature rows at a time: a submit that does not fit until
+    finished sequences have been collected raises ``RgrgHipError`` and leaves the session as it was.  Any other decode call on the
+    engine makes the session stale: its next call raises ``RgrgHipError`` ("stale"), ``close`` still works."""
+
+    def __init__(self, engine, dec, rows: int, capacity: int, n: int, max_length: int, sample: bool):
+        self._eng, self._dec = engine, dec
+        self.rows, self.capacity, self.n, self.max_length, self.sampled = rows, capacity, n, max_length, sample
+        self.submitted = 0          # sequences numbered so far
+        self.watermark = 0          # the lowest sequence number not yet released
+        self.unfinished = 0         # sequences pending or in a row, as of the last advance plus what was submitted since
+        self.steps = 0              # the device's count of steps that had a sequence in a row
+        self._collected = set()     # delivered sequences at or above the watermark
+        self._known_stale = False
+        self._hold = []
+
+    # ------------------------------------------------------------------ helpers
+    def _check(self, rc: int, name: str) -> None:
+        try:
+            _hip.check(rc, name)
+        except _hip.RgrgHipError as e:
+            if "stale" in str(e):
+                self._known_stale = True
+            raise
+
+    def _live(self):
+        if self._dec is None:
+            raise _hip.RgrgHipError("the rolling session is closed")
+        if self._eng._decoder is not self._dec:   # the engine has replaced its decoder (a larger call): the rows are gone
+            self._known_stale = True
+            raise _hip.RgrgHipError("the rolling session is stale: the engine's decoder has been replaced since it was opened")
+        return self._eng.lib, self._dec
+
+    @property
+    def closed(self) -> bool:
+        return self._dec is None
+
+    # ------------------------------------------------------------------ the calls
+    def submit(self, feats: torch.Tensor) -> range:
+        """feats [m, 1024] on the engine's device -> the sequence numbers of its m * n sentences.  Enqueued behind the steps already
+        launched; an idle row starts a new sentence in the very next step.  Does not wait for the device."""
+        lib, dec = self._live()
+        if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] != 1024:
+            raise ValueError(f"submit takes feature rows [m >= 1, 1024], got {tuple(feats.shape)}")
+        with torch.cuda.device(self._eng.device):
+            f = feats.to(device=self._eng.device, dtype=torch.float32).contiguous()
+            first = C.c_longlong(0)
+            self._check(lib.rgrg_decoder_roll_submit(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), "rgrg_decoder_roll_submit")
+            self._hold.append(f)   # the GEMMs read it on the decoder's stream: kept until an advance has synchronised
+        count = f.shape[0] * self.n
+        self.submitted = first.value + count
+        self.unfinished += count
+        return range(first.value, first.value + count)
+
+    def advance(self, steps: Optional[int] = None) -> int:
+        """Runs up to ``steps`` decode steps (None: until nothing is unfinished) and waits for them -> the steps launched; 0 at once
+        when nothing is unfinished."""
+        lib, dec = self._live()
+        if steps is not None and (int(steps) != steps or steps < 0):
+            raise ValueError(f"steps has to be None or a non-negative integer, but is {steps}")
+        launched, unfinished, dsteps = C.c_int(0), C.c_int(0), C.c_int(0)
+        with torch.cuda.device(self._eng.device):
+            self._check(lib.rgrg_decoder_roll_advance(dec, -1 if steps is None else int(steps), C.byref(launched), C.byref(unfinished),
+                                                      C.byref(dsteps)), "rgrg_decoder_roll_advance")
+        self.unfinished, self.steps = unfinished.value, dsteps.value
+        self._hold = []
+        return launched.value
+
+    def collect(self) -> List[tuple]:
+        """Every finished sequence not delivered yet, in ascending q: ``(q, ids)`` - int64 [len], BOS first, the EOS included - and for
+        a sampling session ``(q, ids, logprobs)``.  Sequences finish out of order and are delivered so; the ring is released over
+        the delivered PREFIX only, so one long sentence in front keeps the room of those behind it."""
+        lib, dec = self._live()
+        first, count = self.watermark, self.submitted - self.watermark
+        if count == 0:
+            return []
+        lens = (C.c_int * count)()
+        with torch.cuda.device(self._eng.device):
+            self._check(lib.rgrg_decoder_roll_collect(dec, first, count, None, None, lens, self._eng._s()), "rgrg_decoder_roll_collect")
+            new = [i for i in range(count) if lens[i] > 0 and first + i not in self._collected]
+            if not new:
+                return []
+            lo, span = new[0], new[-1] - new[0] + 1
+            ids = torch.empty((span, self.max_length), dtype=torch.int64, device=self._eng.device)
+            lp = torch.empty((span, self.max_length), dtype=torch.float32, device=self._eng.device) if self.sampled else None
+            lens2 = (C.c_int * span)()
+            self._check(lib.rgrg_decoder_roll_collect(dec, first + lo, span, _hip.ptr(ids), _hip.ptr(lp), lens2, self._eng._s()),
+                        "rgrg_decoder_roll_collect")
+            out = []
+            for i in new:
+                row = (first + i, ids[i - lo, :lens[i]])   # (views of this call's own copy of the ring rows)
+                out.append(row + (lp[i - lo, :lens[i]],) if self.sampled else row)
+                self._collected.add(first + i)
+            wm = self.watermark
+            while wm in self._collected:
+                self._collected.discard(wm)
+                wm += 1
+            if wm != self.watermark:
+                self._check(lib.rgrg_decoder_roll_release(dec, wm), "rgrg_decoder_roll_release")
+                self.watermark = wm
+        return out
+
+    def close(self) -> None:
+        """Ends the session (also a stale one); the engine can open another."""
+        if self._dec is None:
+            return
+        dec, self._dec = self._dec, None
+        if self._eng._session is self:
+            self._eng._session = None
+        if self._eng._decoder is dec:   # otherwise the decoder went away, and the session's rings with it
+            with torch.cuda.device(self._eng.device):
+                _hip.check(self._eng.lib.rgrg_decoder_roll_close(dec), "rgrg_decoder_roll_close")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class ReportRollingSession:
+    """``ReportGenerationModel.open_rolling``: every ``submit(images)`` is a ticket; ``collect`` returns ``(ticket, result)`` for the
+    tickets whose sentences have all ended, ``result`` being what ``generate_rolling(images)`` returns for that submit (``-1`` when
+    no region was selected - such a ticket completes at once)."""
+
+    def __init__(self, model, session: RollingSession):
+        self._model, self.session = model, session
+        self._tickets = {}      # ticket -> [range of sequences, rest of the 4-tuple, {q: ids}]
+        self._done = []         # (ticket, -1) of submits without a selected region
+        self._next = 0
+
+    @torch.no_grad()
+    def submit(self, images: torch.Tensor) -> int:
+        m = self._model
+        if self.session.closed:
+            raise _hip.RgrgHipError("the rolling session is closed")
+        _, detections, top_region_features, class_detected = m.object_detector(images)
+        selected_regions, feats = m.binary_classifier_region_selection(top_region_features, class_detected, return_loss=False)
+        ticket, self._next = self._next, self._next + 1
+        if feats.shape[0] == 0:
+            self._done.append((ticket, -1))
+        else:
+            self._tickets[ticket] = [self.session.submit(feats), (selected_regions, detections, class_detected), {}]
+        return ticket
+
+    def advance(self, steps: Optional[int] = None) -> int:
+        return self.session.advance(steps)
+
+    @property
+    def unfinished(self) -> int:
+        return self.session.unfinished
+
+    def collect(self) -> List[tuple]:
+        out, self._done = self._done, []
+        if self._tickets:
+            for item in self.session.collect():
+                for rng, _, got in self._tickets.values():
+                    if item[0] in rng:
+                        got[item[0]] = item[1]
+                        break
+        for ticket in sorted(self._tickets):
+            rng, rest, got = self._tickets[ticket]
+            if len(got) == len(rng):
+                width = max(v.shape[0] for v in got.values())
+                ids = torch.full((len(rng), width), PAD_TOKEN_ID, dtype=torch.int64, device=got[rng[0]].device)
+                for i, q in enumerate(rng):
+                    ids[i, :got[q].shape[0]] = got[q]
+                out.append((ticket, (ids,) + rest))
+                del self._tickets[ticket]
+        return sorted(out, key=lambda t: t[0])
+
+    def close(self) -> None:
+        self.session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -13,6 +13,13 @@ repeat (lock step over regions x N rows; runs on a tree without ``beam_search_ro
 line then carries regions, regions per second and the K/V cache the decoder holds instead of the token figures.  With
 ``--prefill`` the rolling mode also times, at max_length 2 (one decode step per row hand-out), the call on the unrepeated rows
 against the call on the rows repeated n-fold with one hypothesis each: the difference is the prefill the shared image rows save.
+Sessions (``--session``): ``--session all`` is ONE rolling session per ``--rows`` value with the whole stream submitted
+before the first step (set it against ``--mode rolling`` on the same arguments: the same schedule); ``--session arrivals`` splits the
+unrepeated rows into ``--submits`` submits that arrive ``--gap`` steps apart into one session on ``--rows`` rows (timed with
+``advance(gap)`` between them; a second pass with ``advance(1)`` gives, per submit, the steps from its arrival to its last sentence);
+``--session arrivals-generate`` / ``arrivals-rolling`` are what a tree without sessions offers for the same arrivals - one
+``generate()`` / one ``generate_rolling`` per arrival, a call starting when the one before it has returned (they use nothing newer
+than ``generate_rolling``, so this file also runs them on such a tree).
 Usage: python tools/rolling_bench.py --mode rolling --rows 128 256 464 928 [--repeat 4] [--weights bench|ragged] [--runs 3]
 Prints one JSON line per configuration: sequences, length histogram, steps executed, the longest sequence's steps, sum of the
 steps every sequence needs / rows, ms per call (median of --runs after one warm-up), ms per step, generated tokens per second."""
@@ -54,9 +61,89 @@ def timed(fn, runs):
     return out, statistics.median(ms), ms
 
 
+def run_session(args, model, lm, batch, stream, L, report):
+    def table(items, total):
+        out = torch.full((total, L), EOS, dtype=torch.int64)
+        for q, ids in items:
+            out[q, :ids.shape[0]] = ids.cpu()
+        return out
+
+    if args.session == "all":
+        for R in args.rows:
+            S = int(stream.shape[0])
+            state = {}
+
+            def run():
+                with lm.open_rolling(L, rows=R, capacity=S) as ses:   # (open and close are part of the call: the rings are allocated)
+                    ses.submit(stream)
+                    ses.advance()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    items = ses.collect()
+                    state.update(steps=ses.steps, items=items, collect_ms=(time.perf_counter() - t0) * 1e3)
+            _, ms, all_ms = timed(run, args.runs)
+            lens = lengths(table(state["items"], S))
+            report({"rows": R, "work_steps_per_row": round(int((lens - 1).sum()) / R, 2), "collect_ms_included": round(state["collect_ms"], 3)},
+                   lens, int(state["steps"]), ms, all_ms)
+        return
+    chunks = [c.contiguous() for c in torch.chunk(batch, args.submits)]
+    total, gap = int(batch.shape[0]), args.gap
+    first = [sum(int(c.shape[0]) for c in chunks[:i]) for i in range(len(chunks))]
+    for R in (args.rows if args.session != "arrivals-generate" else [0]):
+        if args.session == "arrivals":
+            def run(step=gap, latency=None):
+                items, clock = [], 0
+                with lm.open_rolling(L, rows=R, capacity=total) as ses:
+                    def tick(k):
+                        nonlocal clock
+                        for _ in range(0, k, step):
+                            clock += ses.advance(min(step, k))
+                            got = ses.collect()
+                            items.extend(got)
+                            if latency is not None:
+                                for q, _ids in got:
+                                    i = max(j for j in range(len(first)) if first[j] <= q)
+                                    latency[i] = max(latency[i], clock - i * gap)
+                    for c in chunks:
+                        ses.submit(c)
+                        tick(gap)
+                    while ses.unfinished:
+                        tick(gap if latency is None else 1)
+                    return items, ses.steps
+            (items, steps), ms, all_ms = timed(run, args.runs)
+            lat = [0] * len(chunks)
+            run(step=1, latency=lat)
+            report({"rows": R, "sequences": total, "repeat": 1, "submits": len(chunks), "gap_steps": gap,
+                    "steps_from_arrival_to_last_sentence": lat},
+                   lengths(table(items, total)), int(steps), ms, all_ms)
+        else:
+            def run():
+                outs, steps = [], []
+                for c in chunks:
+                    if args.session == "arrivals-generate":
+                        outs.append(lm.generate(c, max_length=L))
+                        steps.append(int(outs[-1].shape[1]) - 1)
+                    else:
+                        outs.append(lm.generate_rolling(c, L, rows=min(R, int(c.shape[0]))))
+                        steps.append(int(model.engine().last_rolling_steps))
+                return outs, steps
+            (outs, steps), ms, all_ms = timed(run, args.runs)
+            lat, end = [], 0
+            for i, k in enumerate(steps):   # a call starts when its rows have arrived and the call before it has returned
+                end = max(i * gap, end) + k
+                lat.append(end - i * gap)
+            report({"rows": R or "the arrival's rows", "sequences": total, "repeat": 1, "submits": len(chunks), "gap_steps": gap,
+                    "steps_from_arrival_to_last_sentence": lat,
+                    "steps_are": "steps of calls on different row counts: not of one duration"},
+                   torch.cat([lengths(o) for o in outs]), sum(steps), ms, all_ms)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("generate", "rolling", "sample", "sample-rolling"), required=True)
+    ap.add_argument("--mode", choices=("generate", "rolling", "sample", "sample-rolling"))
+    ap.add_argument("--session", choices=("all", "arrivals", "arrivals-generate", "arrivals-rolling"))
+    ap.add_argument("--submits", type=int, default=8)
+    ap.add_argument("--gap", type=int, default=8)
     ap.add_argument("--rows", type=int, nargs="*", default=[128, 256, 464, 928])
     ap.add_argument("--repeat", type=int, default=4)
     ap.add_argument("--images", type=int, default=32)
@@ -72,6 +159,10 @@ def main():
     ap.add_argument("--prefill", action="store_true")
     ap.add_argument("--beams", type=int, default=0)
     args = ap.parse_args()
+    if (args.mode is None) == (args.session is None):
+        ap.error("give either --mode or --session")
+    if args.session:
+        args.mode = "session-" + args.session
     model = rgrg_amd.ReportGenerationModel(pretrain_without_lm_model=True)
     model.load_state_dict(synth.make_state_dict(0, args.weights))
     model.to("cuda:0").eval()
@@ -107,6 +198,11 @@ def main():
                               ms_runs=[round(m, 3) for m in all_ms], ms_per_step=round(ms / max(steps, 1), 4),
                               regions_per_s=round(regions / ms * 1e3, 1), kv_cache_rows=cap_s, kv_cache_mib=round(cache / 2 ** 20, 1))),
               flush=True)
+
+    if args.session:
+        with torch.no_grad(), ctx():
+            run_session(args, model, lm, batch, stream, L, report)
+        return
 
     if args.beams > 1 and not sampling:
         nb = args.beams
