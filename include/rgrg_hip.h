@@ -305,6 +305,43 @@ int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* 
 int rgrg_decoder_beam_search_rolling(rgrg_decoder* d, const float* feats, int S, int num_beams, int R, int max_length,
                                      int early_stopping, float length_penalty, int num_return_sequences, int64_t* out_ids, int out_ld,
                                      int* out_len, int* steps_out, int use_graph, void* stream);
+/* ---- Rolling beam session: rgrg_decoder_beam_search_rolling over an OPEN list.  One session per decoder, and never next to a
+ * rgrg_decoder_roll_* session: opening either kind while the other is open fails with RGRG_EINVAL and a message.  G = R / num_beams
+ * slots, fixed for the life of the session; every step runs on G * num_beams rows (step plan, precision and cache format are those
+ * of that many rows in the modes in force at open), idle slots included.  Regions are numbered q = 0, 1, 2, ... over the life of the
+ * session, one per submitted feature row.  The session holds `capacity` regions: image key / value rows live in a ring [capacity] the
+ * decoder owns, row q % capacity; heaps and finished hypotheses live on the host for regions watermark .. submitted - 1.  Every other
+ * decode entry on the decoder works as without a session and makes the session stale: its calls then fail with RGRG_EINVAL and a
+ * message containing "stale"; rgrg_decoder_beam_roll_close still works.
+ *
+ * open: the arguments of rgrg_decoder_beam_search_rolling.  Refused, in this order and before any device work: num_beams and
+ *   num_return_sequences as there; R < num_beams; the refusals of rgrg_decoder_generate_rolling for G * num_beams rows (the e4m3 cache
+ *   included); capacity < 1; a session of either kind open on this decoder.  Every slot starts idle.
+ * submit: m feature rows feats [m][1024] (device, `stream`'s) -> regions *first_out .. *first_out + m - 1, pending: the prefill GEMMs
+ *   into the ring rows, in two passes where the ring wraps, in stream order behind the steps already run.  RGRG_EINVAL before anything
+ *   is enqueued, the session intact: the last new region at or beyond watermark + capacity (the message names the capacity and the
+ *   room left).  Does not synchronise: feats must stay valid until the next advance has synchronised.
+ * advance: up to max_steps steps (< 0: until nothing is unfinished, bounded by (ceil(unfinished / G) + 1) * (max_length - 1), RGRG_EHIP
+ *   beyond).  In front of every step free slots take the pending regions in ascending slot order - a slot is seated only in front of
+ *   a step that is launched -, then the step of rgrg_decoder_beam_search_rolling with its one synchronisation; a region that is done,
+ *   or has reached max_length, is finalized and frees its slot.  Nothing is launched when no slot is occupied and nothing is pending.
+ *   A region left mid-flight is continued by the next advance.  *launched_out: steps launched; *unfinished_out: regions pending or
+ *   seated; *steps_out: steps run over the session, each with an occupied slot.
+ * collect: regions first .. first + count - 1 (watermark <= first, first + count <= submitted).  finished_out int32 [count] on the HOST
+ *   (or NULL): 1 for a region finalized as of the last advance.  out_ids == NULL: only this query.  Otherwise every region of the range
+ *   must be finished (RGRG_EINVAL), and out_ids int64 [count * num_return_sequences][out_ld >= max_length] on the device and *out_len
+ *   are what rgrg_decoder_beam_search_rolling returns for a call over exactly these regions (the width over the range).  Synchronises.
+ * release: the new watermark; the heaps below it are dropped.  RGRG_EINVAL when it moves backwards, beyond what was submitted, or
+ *   past a region that has not finished as of the last advance.
+ * close: synchronises, drops the session.  No session open: RGRG_OK. */
+int rgrg_decoder_beam_roll_open(rgrg_decoder* d, int R, int num_beams, int capacity, int max_length, int early_stopping,
+                                float length_penalty, int num_return_sequences, int use_graph, void* stream);
+int rgrg_decoder_beam_roll_submit(rgrg_decoder* d, const float* feats, int m, long long* first_out, void* stream);
+int rgrg_decoder_beam_roll_advance(rgrg_decoder* d, int max_steps, int* launched_out, int* unfinished_out, int* steps_out);
+int rgrg_decoder_beam_roll_collect(rgrg_decoder* d, long long first, int count, int64_t* out_ids, int out_ld, int* out_len,
+                                   int* finished_out, void* stream);
+int rgrg_decoder_beam_roll_release(rgrg_decoder* d, long long watermark);
+int rgrg_decoder_beam_roll_close(rgrg_decoder* d);
 /* Test hook: the turn kernel of rgrg_decoder_beam_search_rolling (beam_roll_turn_kernel: ancestor table and per-row step of the next
  * step, one launch) on the caller's state, all int32 on the device.  src_old / src_new [R][T] are two buffers; parent [R]: the row of
  * the row's slot (rows r / nb * nb .. + nb - 1) whose beam row r continues, -1 = fresh (the slot takes a new region), -2 = idle;

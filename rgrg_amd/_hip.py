@@ -77,6 +77,12 @@ SIGNATURES = {
     "rgrg_debug_roll_session_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, C.c_size_t,
                                           C.c_size_t, _i, _i, _i, _i, _i, _p]),
     "rgrg_decoder_beam_search_rolling": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), C.POINTER(_i), _i, _p]),
+    "rgrg_decoder_beam_roll_open": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "rgrg_decoder_beam_roll_submit": (_i, [_p, _p, _i, C.POINTER(C.c_longlong), _p]),
+    "rgrg_decoder_beam_roll_advance": (_i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "rgrg_decoder_beam_roll_collect": (_i, [_p, C.c_longlong, _i, _p, _i, C.POINTER(_i), C.POINTER(_i), _p]),
+    "rgrg_decoder_beam_roll_release": (_i, [_p, C.c_longlong]),
+    "rgrg_decoder_beam_roll_close": (_i, [_p]),
     "rgrg_debug_beam_roll_turn": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "rgrg_decoder_sample": (_i, [_p, _p, _i, _i, _f, _i, _f, C.c_uint64, _p, _i, _p, C.POINTER(_i), _i, _p]),
     "rgrg_sample_logits_f32": (_i, [_p, C.c_int64, _i, _i, _f, _i, _f, C.c_uint64, _i, _i, _p, _p, _p]),

@@ -2,6 +2,7 @@
 // decoder_beam_roll.hip: rolling-batch beam search; decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch decoding, greedy and sampled) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
+#include <deque>
 #include <functional>
 #include <vector>
 
@@ -169,6 +170,22 @@ struct BeamHyps {
     double worst = 1e9;
     void add(const std::vector<long long>& toks, double sum_logprobs, int nb, double lp);
     bool is_done(double best_sum_logprobs, int cur_len, bool early, int nb, double lp) const;
+};
+
+// The host state of the rolling beam loop (decoder_beam_roll.hip), which the one-shot call keeps for a call and the session
+//  between its calls.  Per row of the Ru = G * nb rows: the hypothesis so far, and what the next step is fed - token,
+// beam score, turn (the parent row, TURN_FRESH or TURN_IDLE).  Per slot: the region it holds (-1 = idle), that region's cur_len and
+// `done` flag.  refill: the (first row, region) pairs of the slots seated for the next step.  src_cur / src_nxt: the ancestor tables.
+struct BeamRollState {
+    int nb = 0, G = 0, Ru = 0, max_length = 0, early = 0, use_graph = 0, nrefill = 0, occupied = 0;
+    bool wide = false;
+    double lp = 1.0;
+    std::vector<std::vector<long long>> ids, nids;
+    std::vector<float> beam_scores, nscore, h_score;
+    std::vector<int> beam_tok, turn, ntok, nidx, h_tok, h_beam, refill, cur_len;
+    std::vector<long long> region;
+    std::vector<char> done;
+    int *src_cur = nullptr, *src_nxt = nullptr;
 };
 
 struct GraphEntry {
@@ -340,6 +357,19 @@ struct rgrg_decoder {
         int* len = nullptr;
         int* h_len = nullptr;
     } sess;
+    // The rolling beam session (decoder_beam_roll.hip): one per decoder, and never next to `sess`.  Regions are numbered
+    // over the life of the session; `next` is the lowest one not yet seated (pending: next .. submitted - 1), hyps / finalized hold
+    // regions watermark .. submitted - 1.  The image key / value ring is roll.ukv [capacity][ld_ukv], row q % capacity.
+    struct BeamRollSession {
+        bool open = false;
+        unsigned long long epoch = 0;
+        rgrg::RollCall call{};          // what the device block holds: ukv, ld_ukv, n = 1, Cf = capacity
+        rgrg::BeamRollState st;
+        int capacity = 0, keep = 0, steps = 0;
+        long long submitted = 0, watermark = 0, next = 0;
+        std::deque<rgrg::BeamHyps> hyps;
+        std::deque<char> finalized;
+    } bsess;
     int chains = 4;   // round 5 (LDS-DMA kernel everywhere): 1 -> 81.6, 2 -> 82.8, 3 -> 85.4, 4 -> 85.1 images/s at BASELINE configs[2]
                       // (profiles/r05_decode_row_ranges_ab.log); round 6, attn_proj / mlp_proj on the K-parity kernel: ms per decode step
                       // 2.89 (3 ranges, round-5 kernels), 2.83 (3), 2.785 (4) - profiles/r06_step_trace_v3.log

@@ -453,6 +453,7 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
     RGRG_CHECK_ARG(d && n > 0);
     const char* who = "rgrg_decoder_roll_open";
     if (d->sess.open) { set_error("%s: a rolling session is already open on this decoder (one per decoder: close it first)", who); return RGRG_EINVAL; }
+    if (d->bsess.open) { set_error("%s: a rolling beam session is already open on this decoder (one per decoder: close it first)", who); return RGRG_EINVAL; }
     if (capacity < 1 || (long long)capacity * n >= 0x7fffffffLL / 1024) {
         set_error("%s: a ring of %d feature rows x %d sequences, 1 .. %lld sequences are possible", who, capacity, n, 0x7fffffffLL / 1024 - 1);
         return RGRG_EINVAL;

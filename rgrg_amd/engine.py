@@ -835,18 +835,26 @@ class HipEngine:
         return ids, logprobs
 
     def open_rolling(self, max_length: int, rows: int, capacity: Optional[int] = None, *, sample: Optional[dict] = None,
-                     use_graph: bool = True, bf16=False, kv_fp8: bool = False):
+                     beam: Optional[dict] = None, use_graph: bool = True, bf16=False, kv_fp8: bool = False):
         """A rolling session (rgrg_decoder_roll_open) on ``rows`` decoder rows: feature rows are submitted at any
         time, steps advanced as far as the caller likes, finished sentences collected as they end -> ``RollingSession``.
         ``capacity``: the feature rows the session holds at a time (None: 4 * rows sequences); ``sample``: None = greedy, or
         ``dict(temperature, top_k, top_p, seed, num_return_sequences)``.  The decoder - cache, step plan, precision - is the one of
         ``rows`` token rows in the modes given HERE; later submits use them.  One session per engine: ValueError while another is
-        open.  Any other decode call on the engine makes the session stale."""
-        from .rolling_session import RollingSession
+        open.  Any other decode call on the engine makes the session stale.
+        ``beam``: ``dict(num_beams, early_stopping, length_penalty, num_return_sequences)`` opens a ``RollingBeamSession``
+        (rgrg_decoder_beam_roll_open, DESIGN.md 7.17) on ``rows // num_beams`` slots instead; ``capacity`` then counts regions (None:
+        4 * slots).  Not together with ``sample``."""
+        from .rolling_session import RollingBeamSession, RollingSession
         _require_gpu(self.device)
         R, limit = int(rows), int(max_length)
+        if beam and sample:
+            raise ValueError("open_rolling: beam and sample exclude each other (beam-sampling has no session)")
+        nb = int(beam["num_beams"]) if beam else 1
+        if beam and (nb < 2 or R < nb):
+            raise ValueError(f"open_rolling: num_beams {nb} (>= 2) on rows {R} (>= num_beams: one region slot)")
         n = int(sample.get("num_return_sequences", 1)) if sample else 1
-        cap = -(-4 * R // n) if capacity is None else int(capacity)
+        cap = (4 * (R // nb) if beam else -(-4 * R // n)) if capacity is None else int(capacity)
         if limit < 2 or R < 1 or n < 1:
             raise ValueError(f"open_rolling: max_length {limit} (>= 2), rows {R} (>= 1) and {n} sequences per feature row (>= 1)")
         if cap < 1:
@@ -862,6 +870,13 @@ class HipEngine:
         dec = self._get_decoder(R, limit)
         self._cached = None
         self._set_modes(dec, bf16, kv_fp8)
+        if beam:
+            keep = int(beam.get("num_return_sequences", 1))
+            _hip.check(self.lib.rgrg_decoder_beam_roll_open(dec, R, nb, cap, limit, 1 if beam.get("early_stopping", False) else 0,
+                                                            float(beam.get("length_penalty", 1.0)), keep, 1 if use_graph else 0, self._s()),
+                       "rgrg_decoder_beam_roll_open")
+            self._session = RollingBeamSession(self, dec, R, cap, limit, nb, keep)
+            return self._session
         sp = sample or {}
         _hip.check(self.lib.rgrg_decoder_roll_open(dec, R, cap, n, limit, 1 if sample else 0, float(sp.get("temperature", 1.0)),
                                                    int(sp.get("top_k", 0)), float(sp.get("top_p", 1.0)),

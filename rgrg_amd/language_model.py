@@ -394,7 +394,7 @@ class LanguageModel(EngineOwner):
 
     def open_rolling(self, max_length: int, *, rows: int, capacity: Optional[int] = None, do_sample: bool = False,
                      temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1,
-                     seed: Optional[int] = None):
+                     seed: Optional[int] = None, num_beams: int = 1, early_stopping: bool = False, length_penalty: float = 1.0):
         """``generate_rolling`` / ``sample_rolling`` (``do_sample``) over an OPEN list: a ``RollingSession`` on
         ``rows`` decoder rows.  ``submit(feats)`` -> the range of sentence numbers q (n = num_return_sequences per feature row, in
         submit order), at any time between steps; ``advance(steps=None)`` runs steps (None: until nothing is unfinished);
@@ -403,7 +403,24 @@ class LanguageModel(EngineOwner):
         it.  ``capacity``: the feature rows held at a time (None: 4 * rows sentences); a submit beyond it raises RgrgHipError
         until sentences in front have been collected.  Precision and step plan are those of ``rows`` under the autocast state of
         THIS call.  Argument errors (ValueError, before any device work) are those of ``generate_rolling`` / ``sample_rolling``,
-        ``rows`` is required; any other decode call on the model makes the session stale (RgrgHipError "stale")."""
+        ``rows`` is required; any other decode call on the model makes the session stale (RgrgHipError "stale").
+        ``num_beams > 1``: ``beam_search_rolling`` over an open list -> a ``RollingBeamSession`` on
+        ``rows // num_beams`` slots.  ``submit(feats)`` -> the range of REGION numbers, one per feature row; ``collect()`` ->
+        ``(q, ids)`` with ids int64 [num_return_sequences, L_q], the rows ``generate(num_beams=..)`` gives the region.  ``capacity``
+        counts regions (None: 4 * (rows // num_beams)).  Argument errors are those of ``beam_search_rolling``; ``do_sample``
+        with beams raises ValueError (beam-sampling has no session)."""
+        if num_beams != 1:
+            if do_sample:
+                raise ValueError("do_sample has to be False with num_beams > 1: beam-sampling has no rolling session")
+            check_rolling_beam_args(max_length, num_beams, rows, num_return_sequences)
+            if rows is None:
+                raise ValueError("rows has to be given for a rolling session (the decoder rows the regions flow through)")
+            if capacity is not None and (int(capacity) != capacity or capacity < 1):
+                raise ValueError(f"capacity has to be a positive integer (the regions the session holds at a time), but is {capacity}")
+            modes = self._decode_modes(next(self.parameters()).device)
+            beam = dict(num_beams=int(num_beams), early_stopping=bool(early_stopping), length_penalty=float(length_penalty),
+                        num_return_sequences=int(num_return_sequences))
+            return self.engine().open_rolling(int(max_length), int(rows), None if capacity is None else int(capacity), beam=beam, **modes)
         if do_sample:
             check_sample_args(temperature, top_k, top_p, num_return_sequences)
         elif num_return_sequences != 1:

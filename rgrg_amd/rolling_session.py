@@ -30,7 +30,12 @@ class RollingSession:
         self._known_stale = False
         self._hold = []
 
+    _abi = "rgrg_decoder_roll_"   # the C entries behind submit / advance / close (RollingBeamSession: rgrg_decoder_beam_roll_)
+
     # ------------------------------------------------------------------ helpers
+    def _fn(self, name: str):
+        return getattr(self._eng.lib, self._abi + name)
+
     def _check(self, rc: int, name: str) -> None:
         try:
             _hip.check(rc, name)
@@ -61,7 +66,7 @@ class RollingSession:
         with torch.cuda.device(self._eng.device):
             f = feats.to(device=self._eng.device, dtype=torch.float32).contiguous()
             first = C.c_longlong(0)
-            self._check(lib.rgrg_decoder_roll_submit(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), "rgrg_decoder_roll_submit")
+            self._check(self._fn("submit")(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), self._abi + "submit")
             self._hold.append(f)   # the GEMMs read it on the decoder's stream: kept until an advance has synchronised
         count = f.shape[0] * self.n
         self.submitted = first.value + count
@@ -76,8 +81,8 @@ class RollingSession:
             raise ValueError(f"steps has to be None or a non-negative integer, but is {steps}")
         launched, unfinished, dsteps = C.c_int(0), C.c_int(0), C.c_int(0)
         with torch.cuda.device(self._eng.device):
-            self._check(lib.rgrg_decoder_roll_advance(dec, -1 if steps is None else int(steps), C.byref(launched), C.byref(unfinished),
-                                                      C.byref(dsteps)), "rgrg_decoder_roll_advance")
+            self._check(self._fn("advance")(dec, -1 if steps is None else int(steps), C.byref(launched), C.byref(unfinished),
+                                            C.byref(dsteps)), self._abi + "advance")
         self.unfinished, self.steps = unfinished.value, dsteps.value
         self._hold = []
         return launched.value
@@ -125,7 +130,7 @@ class RollingSession:
             self._eng._session = None
         if self._eng._decoder is dec:   # otherwise the decoder went away, and the session's rings with it
             with torch.cuda.device(self._eng.device):
-                _hip.check(self._eng.lib.rgrg_decoder_roll_close(dec), "rgrg_decoder_roll_close")
+                _hip.check(self._fn("close")(dec), self._abi + "close")
 
     def __enter__(self):
         return self
@@ -135,10 +140,54 @@ class RollingSession:
         return False
 
 
+class RollingBeamSession(RollingSession):
+    """Rolling beam search over an open list (DESIGN.md 7.17, rgrg_decoder_beam_roll_*): ``rows // num_beams`` slots of ``num_beams``
+    decoder rows through which the regions of any number of ``submit`` calls flow.  The surface of ``RollingSession`` with regions
+    in place of sentences: one region per feature row, numbered q = 0, 1, ... in submit order; ``capacity`` counts regions."""
+
+    _abi = "rgrg_decoder_beam_roll_"
+
+    def __init__(self, engine, dec, rows: int, capacity: int, max_length: int, num_beams: int, num_return_sequences: int):
+        super().__init__(engine, dec, rows, capacity, 1, max_length, False)
+        self.num_beams, self.num_return_sequences, self.slots = num_beams, num_return_sequences, rows // num_beams
+
+    def collect(self) -> List[tuple]:
+        """Every finished region not delivered yet, in ascending q: ``(q, ids)`` with ids int64 [num_return_sequences, L_q] - the rows
+        ``generate(num_beams=..)`` returns for the region, at the padded width L_q of that region alone.  Regions finish out of
+        order and are delivered so; the delivered PREFIX is released."""
+        lib, dec = self._live()
+        first, count = self.watermark, self.submitted - self.watermark
+        if count == 0:
+            return []
+        fin = (C.c_int * count)()
+        out = []
+        with torch.cuda.device(self._eng.device):
+            self._check(lib.rgrg_decoder_beam_roll_collect(dec, first, count, None, 0, None, fin, self._eng._s()), "rgrg_decoder_beam_roll_collect")
+            for i in range(count):
+                q = first + i
+                if not fin[i] or q in self._collected:
+                    continue
+                ids = torch.empty((self.num_return_sequences, self.max_length), dtype=torch.int64, device=self._eng.device)
+                width = C.c_int(0)
+                self._check(lib.rgrg_decoder_beam_roll_collect(dec, q, 1, _hip.ptr(ids), self.max_length, C.byref(width), None, self._eng._s()),
+                            "rgrg_decoder_beam_roll_collect")
+                out.append((q, ids[:, :width.value].contiguous()))
+                self._collected.add(q)
+            wm = self.watermark
+            while wm in self._collected:
+                self._collected.discard(wm)
+                wm += 1
+            if wm != self.watermark:
+                self._check(lib.rgrg_decoder_beam_roll_release(dec, wm), "rgrg_decoder_beam_roll_release")
+                self.watermark = wm
+        return out
+
+
 class ReportRollingSession:
     """``ReportGenerationModel.open_rolling``: every ``submit(images)`` is a ticket; ``collect`` returns ``(ticket, result)`` for the
     tickets whose sentences have all ended, ``result`` being what ``generate_rolling(images)`` returns for that submit (``-1`` when
-    no region was selected - such a ticket completes at once)."""
+    no region was selected - such a ticket completes at once).  Over a ``RollingBeamSession`` a region delivers its
+    num_return_sequences hypotheses and ``result`` is what ``generate(images, num_beams=..)`` returns."""
 
     def __init__(self, model, session: RollingSession):
         self._model, self.session = model, session
@@ -178,10 +227,14 @@ class ReportRollingSession:
         for ticket in sorted(self._tickets):
             rng, rest, got = self._tickets[ticket]
             if len(got) == len(rng):
-                width = max(v.shape[0] for v in got.values())
-                ids = torch.full((len(rng), width), PAD_TOKEN_ID, dtype=torch.int64, device=got[rng[0]].device)
-                for i, q in enumerate(rng):
-                    ids[i, :got[q].shape[0]] = got[q]
+                # a sentence [len] or a region's hypotheses [n, L_q], PAD up to the widest of the ticket: the width generate() computes
+                rows = [got[q].reshape(-1, got[q].shape[-1]) for q in rng]
+                width = max(r.shape[1] for r in rows)
+                ids = torch.full((sum(r.shape[0] for r in rows), width), PAD_TOKEN_ID, dtype=torch.int64, device=rows[0].device)
+                at = 0
+                for r in rows:
+                    ids[at:at + r.shape[0], :r.shape[1]] = r
+                    at += r.shape[0]
                 out.append((ticket, (ids,) + rest))
                 del self._tickets[ticket]
         return sorted(out, key=lambda t: t[0])
