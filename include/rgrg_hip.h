@@ -278,6 +278,31 @@ int rgrg_decoder_roll_collect(rgrg_decoder* d, long long first, int count, int64
                               void* stream);
 int rgrg_decoder_roll_release(rgrg_decoder* d, long long watermark);
 int rgrg_decoder_roll_close(rgrg_decoder* d);
+/* ---- Requests of a rolling session: every submit may carry its own decoding parameters, and a submitted sequence can be cancelled.
+ * Request ring: the decoder keeps one 40-byte entry per ring row (entry q % C for sequence q), written at submit and read by the
+ * retire pass and the sampler of every step for the sequence a row holds.  Layout (little endian, what the two _req hooks take):
+ *   0 uint64 seed | 8 float 1 / temperature | 12 int32 top_k | 16 float top_p | 20 int32 max_length | 24 int32 q0 |
+ *   28 uint16 stop[4] (65535 = unused) | 36 uint32 flags (bit 0: cancelled)
+ * rgrg_decoder_roll_submit writes the session's own values with q0 = 0 - its results are those of a session without requests.
+ *
+ * submit_req: rgrg_decoder_roll_submit with a request for all m * n new sequences.  max_length 0: the session's, else 2 .. the
+ *   session's: the sequence retires when its max_length-th token is written (the ring rows keep the session's width).  temperature 0,
+ *   top_k < 0, top_p 0, has_seed 0: the session's value; anything else is accepted in a sampling session only and validated as
+ *   rgrg_decoder_sample does.  top_k = 1 is a greedy request inside a sampling session.  Counter rule: without a seed sequence q draws
+ *   column c under the session's seed and the Philox counter (q, c - 1); with has_seed under `seed` and (q - q0, c - 1), q0 being the
+ *   first sequence of the submit - what rgrg_decoder_sample_rolling gives for these feature rows alone under that seed.  stop_ids
+ *   (host, n_stop <= 4 token ids < 65535): tokens that end a sequence as EOS does - appended, the last token.  RGRG_EINVAL before
+ *   anything is enqueued, the session intact: the refusals of submit, a value out of range, a sampling value in a greedy session.
+ * cancel: sets the cancel flag of sequences first .. first + count - 1 (watermark <= first, first + count <= submitted; RGRG_EINVAL
+ *   otherwise) on the decoder's stream, without synchronising.  Cancel rule: the retire pass of the next step launched after the call
+ *   CUTS a flagged sequence that holds a row: the token of that step is not appended, the row is free in the same pass and takes the
+ *   next pending sequence.  A flagged sequence still pending takes a row as usual and is cut in that row's first retire pass: BOS
+ *   alone, one row-step.  A sequence that has ended is not touched.
+ * Length word: lens_out of rgrg_decoder_roll_collect is > 0 for a sequence that has ended (its tokens), < 0 for one that was cut
+ *   (minus its tokens, BOS included; no EOS is added) and 0 for one that has not finished.  release accepts both non-zero kinds. */
+int rgrg_decoder_roll_submit_req(rgrg_decoder* d, const float* feats, int m, int max_length, float temperature, int top_k, float top_p,
+                                 int has_seed, uint64_t seed, const int* stop_ids, int n_stop, long long* first_out, void* stream);
+int rgrg_decoder_roll_cancel(rgrg_decoder* d, long long first, int count);
 /* Test hook: what a session enqueues around one step, on the caller's state with a ring, all on the device.  Arrays as
  * rgrg_debug_roll_step, but ids int64 / lp f32 (or NULL) [C][ld_ids], lens [C] and ukv [C / n][ld_ukv] are rings: sequence q uses row
  * q % C and ukv row (q / n) % (C / n).  In this order: submit > 0: the new sequences S_before .. S_before + submit - 1 get their
@@ -288,6 +313,21 @@ int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* 
                                  int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before, int submit, int handout,
                                  int retire, int R, int max_length, const float* ukv, int ld_ukv, void* kv, size_t layer_stride,
                                  size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, void* stream);
+/* Test hook: rgrg_debug_roll_session_step with the caller's request ring req [C] on the device ("Request ring" above; NULL: exactly
+ * that hook).  The retire pass takes the limit, the stop ids and the cancel flag of a row's sequence from entry row_seq[r] % C; a cut
+ * writes lens[row_seq[r] % C] = -row_len[r].  The submit-init does not write the ring.  RGRG_EINVAL: an entry whose max_length is not
+ * 2 .. max_length or whose sampling values rgrg_decoder_sample would refuse (the ring is read back and checked first). */
+int rgrg_debug_roll_session_step_req(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                                     int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before, int submit, int handout,
+                                     int retire, int R, int max_length, const float* ukv, int ld_ukv, void* kv, size_t layer_stride,
+                                     size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, const void* req, void* stream);
+/* Test hook: rgrg_debug_roll_sample with the caller's request ring req [C] on the device (NULL: exactly that hook, C unused).  An
+ * active row draws with the values of entry row_seq[r] % C under the counter (row_seq[r] - q0, row_len[r] - 1); lp is [C][ld_lp], the
+ * log-prob goes to lp[(row_seq[r] % C) * ld_lp + row_len[r]].  (temperature, top_k, top_p, seed) fill the step's parameter block, which
+ * is not read then.  RGRG_EINVAL: C < 1, an entry rgrg_decoder_sample would refuse, q0 < 0. */
+int rgrg_debug_roll_sample_req(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len, float temperature,
+                               int top_k, float top_p, uint64_t seed, const void* req, int C, int* arg, float* lp, int ld_lp,
+                               void* stream);
 /* Rolling-batch beam search: rgrg_decoder_beam_search over the S regions of feats [S,1024] with the regions flowing through
  * G = min(R / num_beams, S) SLOTS of num_beams consecutive decoder rows (num_beams <= R <= max_seqs of the decoder; S is not bounded
  * by it; rows behind G * num_beams are not used, and the step plan, precision and cache format are those of a step of G * num_beams

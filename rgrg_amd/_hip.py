@@ -70,12 +70,17 @@ SIGNATURES = {
     "rgrg_debug_roll_sample": (_i, [_p, C.c_int64, _i, _i, _p, _p, _f, _i, _f, C.c_uint64, _p, _p, _i, _p]),
     "rgrg_decoder_roll_open": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _p]),
     "rgrg_decoder_roll_submit": (_i, [_p, _p, _i, C.POINTER(C.c_longlong), _p]),
+    "rgrg_decoder_roll_submit_req": (_i, [_p, _p, _i, _i, _f, _i, _f, _i, C.c_uint64, C.POINTER(_i), _i, C.POINTER(C.c_longlong), _p]),
+    "rgrg_decoder_roll_cancel": (_i, [_p, C.c_longlong, _i]),
     "rgrg_decoder_roll_advance": (_i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "rgrg_decoder_roll_collect": (_i, [_p, C.c_longlong, _i, _p, _p, C.POINTER(_i), _p]),
     "rgrg_decoder_roll_release": (_i, [_p, C.c_longlong]),
     "rgrg_decoder_roll_close": (_i, [_p]),
     "rgrg_debug_roll_session_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, C.c_size_t,
                                           C.c_size_t, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_roll_session_step_req": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p,
+                                              C.c_size_t, C.c_size_t, _i, _i, _i, _i, _i, _p, _p]),
+    "rgrg_debug_roll_sample_req": (_i, [_p, C.c_int64, _i, _i, _p, _p, _f, _i, _f, C.c_uint64, _p, _i, _p, _p, _i, _p]),
     "rgrg_decoder_beam_search_rolling": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, C.POINTER(_i), C.POINTER(_i), _i, _p]),
     "rgrg_decoder_beam_roll_open": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "rgrg_decoder_beam_roll_submit": (_i, [_p, _p, _i, C.POINTER(C.c_longlong), _p]),

@@ -150,6 +150,7 @@ struct StepSpec {
 
 // What changes from call to call of rolling-batch decoding (decoder_roll.hip): the kernels of a captured step read it from a device
 // block.  A call decodes S sequences, n per feature row: sequence q belongs to feature row q / n.
+struct RollReq;
 struct RollCall {
     long long* ids;       // [S][ld] the caller's output: column 0 BOS, PAD behind a sequence's last token
     int* len;             // [S] tokens of every sequence, BOS included (0 until it has ended)
@@ -160,7 +161,28 @@ struct RollCall {
     // Only the STORAGE is a ring (a rolling session): sequence q writes row q % C of ids / lp / len and reads row
     // (q / n) % Cf of ukv.  A one-shot call passes C = S and Cf = S / n: q % C == q, the caller's buffers as they are.
     int C, Cf;
+    // The request ring of a rolling session: entry q % C holds what sequence q asked for.  NULL - the one-shot calls,
+    // rolling beam search, the test hooks without a ring - is the call's max_length, EOS alone and the parameter block of the step.
+    const RollReq* req;
 };
+
+// What one sequence of a rolling session asked for (include/rgrg_hip.h "Request ring" states the layout for the test hooks): 40 bytes,
+// written by roll_submit_kernel for every new sequence, read by roll_retire_kernel and roll_sample_kernel for the sequence a row holds.
+// A greedy session uses max_length, stop and flags only.
+constexpr unsigned ROLL_REQ_CANCEL = 1u;      // flags: rgrg_decoder_roll_cancel has reached the sequence
+constexpr unsigned short ROLL_NO_STOP = 0xffffu;
+constexpr int ROLL_MAX_STOPS = 4;
+struct RollReq {
+    unsigned long long seed;    // the Philox key of the sequence's draws
+    float inv_T;                // 1 / temperature
+    int top_k;
+    float top_p;
+    int max_length;             // the sequence's own limit, 2 .. the session's
+    int q0;                     // the counter row of the draws is q - q0 (0: the session's numbering)
+    unsigned short stop[ROLL_MAX_STOPS];   // token ids that end the sequence as EOS does; ROLL_NO_STOP = unused
+    unsigned flags;
+};
+static_assert(sizeof(RollReq) == 40, "RollReq is 40 bytes (include/rgrg_hip.h)");
 
 // BeamHypotheses of transformers 4.19.2 restated on the host (decoder_beam.hip): hypothesis scores, worst_score and the is_done test are
 // double arithmetic (HF does them on Python floats obtained through .item()), beam scores stay float32
@@ -356,6 +378,9 @@ struct rgrg_decoder {
         float* lp = nullptr;
         int* len = nullptr;
         int* h_len = nullptr;
+        // the request ring [C] and what a submit without a request writes into it: the session's own parameters
+        rgrg::RollReq* req = nullptr;
+        rgrg::RollReq defaults{};
     } sess;
     // The rolling beam session (decoder_beam_roll.hip): one per decoder, and never next to `sess`.  Regions are numbered
     // over the life of the session; `next` is the lowest one not yet seated (pending: next .. submitted - 1), hyps / finalized hold
@@ -474,7 +499,8 @@ void roll_session_free(rgrg_decoder* d);   // the session's rings (rgrg_decoder_
 int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R);
 // sample.hip: the rolling sampler - row r of logits [R][ld] holds sequence row_seq[r] (< 0: idle, nothing is written) at row_len[r]
 // tokens; an active row draws with the Philox counter (sequence, len - 1), the token -> arg[r], its log-prob ->
-// call->lp[sequence][len] (pitch call->ld; a NULL call->lp: no log-probs).  Parameters from the device block prm_dev.
+// call->lp[sequence][len] (pitch call->ld; a NULL call->lp: no log-probs).  Parameters from the device block prm_dev - or, with a request ring (call->req), from
+// the sequence's entry, the counter then being (sequence - q0, len - 1).
 int launch_roll_sample(const float* logits, size_t ld, int R, int V, const void* prm_dev, const int* row_seq, const int* row_len,
                        const RollCall* call, int* arg, hipStream_t st);
 int tf_reserve(rgrg_decoder* d, size_t rows);

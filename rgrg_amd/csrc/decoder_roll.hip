@@ -15,6 +15,7 @@
 // place of the arg-max: sequence q draws the token of column c under the Philox counter (q, c - 1), whichever row holds it.  A call
 // decodes n sequences per feature row; they share that row's image key / value (ukv row q / n).
 #include <algorithm>
+#include <vector>
 
 #include "decoder_internal.h"
 
@@ -64,6 +65,10 @@ __global__ __launch_bounds__(256) void roll_begin_kernel(const RollCall c, RollC
 // `next` advances by the sequences handed out, not by the free rows.  Sequence q writes ring row q % C of the output.
 // handout_only (the first hand-out of a call, a submit of a session): a row that holds a sequence is not touched - no append, no
 // retire, arg is not read - and the pass is not a step; idle rows take pending sequences as above.
+// With a request ring (call->req; tests/rolling_request_reference.py is the model) the limit is the sequence's own, its
+// stop tokens end it like EOS (appended, the last token), and a sequence whose cancel flag is set is CUT: nothing is appended, its
+// length is recorded NEGATIVE (-len, len >= 1 tokens kept) and the row is free like a retired one.  The flag is looked at for rows that
+// hold a sequence on entry only: a pending sequence takes a row as usual and is cut in that row's next pass, as BOS alone.
 __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, const int* __restrict__ arg, const RollCall* __restrict__ call,
                                                           int R, int handout_only) {
     __shared__ int wave_free[4];
@@ -83,13 +88,27 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
                 const int tok = arg[r];
                 int len = st.len[r];
                 const int slot = seq % c.C;
-                c.ids[(size_t)slot * c.ld + len] = tok;
-                ++len;
-                if (tok == EOS_ID || len >= c.max_length) {
-                    c.len[slot] = len;
+                int limit = c.max_length;
+                bool stop = tok == EOS_ID, cut = false;
+                if (c.req) {   // the sequence's own request (a session): its limit, its stop tokens, the cancel flag
+                    const RollReq q = c.req[slot];
+                    limit = min(q.max_length, c.max_length);   // (never beyond the row's width, whatever the entry says)
+                    cut = (q.flags & ROLL_REQ_CANCEL) != 0u;
+#pragma unroll
+                    for (int i = 0; i < ROLL_MAX_STOPS; ++i) stop |= q.stop[i] != ROLL_NO_STOP && tok == (int)q.stop[i];
+                }
+                if (cut) {   // cancelled: the token of this step is not appended; the negative length tells the cut from an end
+                    c.len[slot] = -len;
                     is_free = true;
                 } else {
-                    st.len[r] = len; st.tok[r] = tok; st.pos[r] = len - 1; st.step[r] = len - 1;
+                    c.ids[(size_t)slot * c.ld + len] = tok;
+                    ++len;
+                    if (stop || len >= limit) {
+                        c.len[slot] = len;
+                        is_free = true;
+                    } else {
+                        st.len[r] = len; st.tok[r] = tok; st.pos[r] = len - 1; st.step[r] = len - 1;
+                    }
                 }
             }
         }
@@ -405,26 +424,37 @@ namespace rgrg {
 // A submit of `count` sequences q0 .. q0 + count - 1 (c: the host's block, S = q0 still): their ring rows in the state
 // roll_begin_kernel gives a sequence that never ran - BOS then PAD, log-probs 0, len 0 - and nothing else; then S and the
 // unfinished word grow by count.  The kernels behind it in the stream see the new S.
+// ring (or NULL: no request ring, or a test hook whose caller has written it): entry q % C of every new sequence becomes `req`.
 __global__ __launch_bounds__(256) void roll_submit_kernel(const RollCall c, RollCall* __restrict__ call, int* __restrict__ shared, int q0,
-                                                          int count) {
+                                                          int count, RollReq* __restrict__ ring, const RollReq req) {
     const size_t total = (size_t)count * c.max_length;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t o = (size_t)((q0 + (int)(i / c.max_length)) % c.C) * c.ld + (i % c.max_length);
         c.ids[o] = (i % c.max_length) == 0 ? BOS_ID : PAD_ID;
         if (c.lp) c.lp[o] = 0.f;
     }
-    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x) c.len[(q0 + s) % c.C] = 0;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x) {
+        c.len[(q0 + s) % c.C] = 0;
+        if (ring) ring[(q0 + s) % c.C] = req;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         call->S = q0 + count;
         shared[ROLL_UNFINISHED] += count;
     }
 }
 
-static int launch_roll_submit(const RollCall& c, RollCall* dcall, int* shared, int q0, int count, hipStream_t st) {
+static int launch_roll_submit(const RollCall& c, RollCall* dcall, int* shared, int q0, int count, hipStream_t st, RollReq* ring = nullptr,
+                              const RollReq& req = RollReq{}) {
     const int blocks = (int)std::min<size_t>(64, ((size_t)count * c.max_length + 255) / 256);
-    hipLaunchKernelGGL(roll_submit_kernel, dim3(std::max(blocks, 1)), dim3(256), 0, st, c, dcall, shared, q0, count);
+    hipLaunchKernelGGL(roll_submit_kernel, dim3(std::max(blocks, 1)), dim3(256), 0, st, c, dcall, shared, q0, count, ring, req);
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
+}
+
+// rgrg_decoder_roll_cancel: the cancel flag of sequences first .. first + count - 1, outside the captured step.  The retire pass of the
+// next step sees it (stream order); nothing else of the entry changes, so a sequence that has ended keeps its length word.
+__global__ __launch_bounds__(256) void roll_cancel_kernel(RollReq* __restrict__ ring, int C, int first, int count) {
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x) ring[(first + s) % C].flags |= ROLL_REQ_CANCEL;
 }
 
 void roll_session_free(rgrg_decoder* d) {
@@ -432,6 +462,7 @@ void roll_session_free(rgrg_decoder* d) {
     if (s.ids) (void)hipFree(s.ids);
     if (s.lp) (void)hipFree(s.lp);
     if (s.len) (void)hipFree(s.len);
+    if (s.req) (void)hipFree(s.req);
     if (s.h_len) (void)hipHostFree(s.h_len);
     s = rgrg_decoder::RollSession{};
 }
@@ -466,7 +497,7 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
     const size_t C = (size_t)capacity * n;
     if (hipMalloc((void**)&s.ids, C * max_length * sizeof(long long)) != hipSuccess || hipMalloc((void**)&s.len, C * sizeof(int)) != hipSuccess ||
         (sample && hipMalloc((void**)&s.lp, C * max_length * sizeof(float)) != hipSuccess) ||
-        hipHostMalloc((void**)&s.h_len, C * sizeof(int)) != hipSuccess) {
+        hipMalloc((void**)&s.req, C * sizeof(RollReq)) != hipSuccess || hipHostMalloc((void**)&s.h_len, C * sizeof(int)) != hipSuccess) {
         roll_session_free(d);
         set_error("%s: no memory for a ring of %zu sequences of %d tokens", who, C, max_length);
         return RGRG_EHIP;
@@ -476,7 +507,10 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
         roll_session_free(d);
         return rc;
     }
-    s.call = RollCall{s.ids, s.len, d->roll.ukv, max_length, 0, max_length, d->ld_ukv, s.lp, n, (int)C, capacity};
+    s.call = RollCall{s.ids, s.len, d->roll.ukv, max_length, 0, max_length, d->ld_ukv, s.lp, n, (int)C, capacity, s.req};
+    // what a submit without a request asks for: the session's limit and parameters, its numbering (q0 = 0), EOS alone
+    s.defaults = RollReq{seed, sample ? 1.0f / temperature : 1.0f, sample ? top_k : 0, sample ? top_p : 1.0f, max_length, 0,
+                         {ROLL_NO_STOP, ROLL_NO_STOP, ROLL_NO_STOP, ROLL_NO_STOP}, 0u};
     s.R = R; s.use_graph = use_graph; s.end = sample ? STEP_ROLL_SAMPLE : STEP_ROLL;
     // the device block, every row idle, nothing pending (S = 0: roll_begin_kernel writes no output row)
     hipLaunchKernelGGL(roll_begin_kernel, dim3(1), dim3(256), 0, d->stream, s.call, static_cast<RollCall*>(d->roll.call), roll_rows(d), R);
@@ -486,11 +520,9 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
     return RGRG_OK;
 }
 
-extern "C" int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int m, long long* first_out, void* stream) {
-    RGRG_CHECK_ARG(d && feats && m > 0);
-    const char* who = "rgrg_decoder_roll_submit";
+// submit with the request `req` for all m * n new sequences; q0 < 0 in it: the first new sequence (a request with a seed of its own)
+static int roll_submit(rgrg_decoder* d, const char* who, const float* feats, int m, RollReq req, long long* first_out, void* stream) {
     int rc;
-    if ((rc = roll_session_live(d, who))) return rc;
     rgrg_decoder::RollSession& s = d->sess;
     const int n = s.call.n, C = s.call.C, Cf = s.call.Cf;
     const long long q0 = s.call.S, count = (long long)m * n;
@@ -510,13 +542,83 @@ extern "C" int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int
     if ((rc = enqueue_roll_prefill(d, feats, head, (size_t)f0))) return rc;
     if (m > head && (rc = enqueue_roll_prefill(d, feats + (size_t)head * d->D, m - head, 0))) return rc;
     // 2. + 3. the new output rows, S and the unfinished word; 4. idle rows take what is pending, their slot 0 is filled
-    if ((rc = launch_roll_submit(s.call, static_cast<RollCall*>(d->roll.call), d->roll.shared, (int)q0, (int)count, d->stream))) return rc;
+    if (req.q0 < 0) req.q0 = (int)q0;
+    if ((rc = launch_roll_submit(s.call, static_cast<RollCall*>(d->roll.call), d->roll.shared, (int)q0, (int)count, d->stream, s.req, req)))
+        return rc;
     for (long long q = q0; q < q0 + count; ++q) s.h_len[q % C] = 0;
     s.call.S = (int)(q0 + count);
     s.unfinished += count;
     s.drained = false;
     if ((rc = roll_retire_refill(d, s.R, 1))) return rc;
     if (first_out) *first_out = q0;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int m, long long* first_out, void* stream) {
+    RGRG_CHECK_ARG(d && feats && m > 0);
+    const char* who = "rgrg_decoder_roll_submit";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    return roll_submit(d, who, feats, m, d->sess.defaults, first_out, stream);
+}
+
+extern "C" int rgrg_decoder_roll_submit_req(rgrg_decoder* d, const float* feats, int m, int max_length, float temperature, int top_k,
+                                            float top_p, int has_seed, uint64_t seed, const int* stop_ids, int n_stop,
+                                            long long* first_out, void* stream) {
+    RGRG_CHECK_ARG(d && feats && m > 0 && (n_stop == 0 || stop_ids));
+    const char* who = "rgrg_decoder_roll_submit_req";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    const rgrg_decoder::RollSession& s = d->sess;
+    RollReq req = s.defaults;
+    if (max_length != 0) {
+        if (max_length < 2 || max_length > s.call.max_length) {
+            set_error("%s: max_length %d, 2 .. %d (the session's) are possible", who, max_length, s.call.max_length);
+            return RGRG_EINVAL;
+        }
+        req.max_length = max_length;
+    }
+    const bool sampling = temperature != 0.f || top_k >= 0 || top_p != 0.f || has_seed;
+    if (sampling && s.end != STEP_ROLL_SAMPLE) {
+        set_error("%s: temperature, top_k, top_p and seed belong to a sampling session, this one is a greedy session", who);
+        return RGRG_EINVAL;
+    }
+    if (temperature != 0.f) {
+        if (!(temperature > 0.f)) { set_error("%s: temperature %g has to be positive", who, (double)temperature); return RGRG_EINVAL; }
+        req.inv_T = 1.0f / temperature;
+    }
+    if (top_k >= 0) req.top_k = top_k;
+    if (top_p != 0.f) {
+        if (!(top_p > 0.f && top_p <= 1.0f)) { set_error("%s: top_p %g, (0, 1] is possible", who, (double)top_p); return RGRG_EINVAL; }
+        req.top_p = top_p;
+    }
+    if (has_seed) { req.seed = seed; req.q0 = -1; }   // (roll_submit: the submit's first sequence)
+    if (n_stop < 0 || n_stop > ROLL_MAX_STOPS) {
+        set_error("%s: %d stop token ids, 0 .. %d are possible", who, n_stop, ROLL_MAX_STOPS);
+        return RGRG_EINVAL;
+    }
+    for (int i = 0; i < n_stop; ++i) {
+        if (stop_ids[i] < 0 || stop_ids[i] >= (int)ROLL_NO_STOP) {
+            set_error("%s: stop token id %d, 0 .. %d are possible", who, stop_ids[i], (int)ROLL_NO_STOP - 1);
+            return RGRG_EINVAL;
+        }
+        req.stop[i] = (unsigned short)stop_ids[i];
+    }
+    return roll_submit(d, who, feats, m, req, first_out, stream);
+}
+
+extern "C" int rgrg_decoder_roll_cancel(rgrg_decoder* d, long long first, int count) {
+    RGRG_CHECK_ARG(d && count > 0);
+    const char* who = "rgrg_decoder_roll_cancel";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    const rgrg_decoder::RollSession& s = d->sess;
+    if (first < s.watermark || first + count > s.call.S) {
+        set_error("%s: sequences %lld .. %lld, the ring holds %lld .. %d", who, first, first + count - 1, s.watermark, s.call.S - 1);
+        return RGRG_EINVAL;
+    }
+    hipLaunchKernelGGL(roll_cancel_kernel, dim3((count + 255) / 256), dim3(256), 0, d->stream, s.req, s.call.C, (int)first, count);
+    RGRG_LAUNCH_CHECK();
     return RGRG_OK;
 }
 
@@ -639,11 +741,11 @@ extern "C" int rgrg_decoder_roll_close(rgrg_decoder* d) {
 // Test hook: what a session enqueues around one step, on the caller's state with a ring - submit-init of `submit` new sequences
 // (S_before .. S_before + submit - 1; 0: none), the hand-out-only pass (handout), a whole retire pass (retire), each pass with its
 // refill launch when ukv / kv are given.  Arrays as rgrg_debug_roll_step, but ids / lp [C][ld_ids], lens [C], ukv [C / n][ld_ukv].
-extern "C" int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared,
-                                            const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before,
-                                            int submit, int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv,
-                                            void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16,
-                                            int fp16, void* stream) {
+static int debug_roll_session_step(const char* who, int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared,
+                                   const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before,
+                                   int submit, int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv,
+                                   void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16,
+                                   int fp16, const RollReq* req, void* stream) {
     RGRG_CHECK_ARG(row_seq && row_len && row_tok && row_pos && row_step && shared && arg && ids && lens);
     RGRG_CHECK_ARG(C > 0 && n > 0 && C % n == 0 && S_before >= 0 && submit >= 0 && submit % n == 0 && submit <= C &&
                    (long long)S_before + submit < 0x7fffffffLL / 1024);
@@ -655,8 +757,8 @@ extern "C" int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row
     int* list = nullptr;
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
-    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("rgrg_debug_roll_session_step: hipMalloc failed"); return RGRG_EHIP; }
-    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S_before, max_length, ld_ukv, lp, n, C, C / n};
+    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("%s: hipMalloc failed", who); return RGRG_EHIP; }
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S_before, max_length, ld_ukv, lp, n, C, C / n, req};
     hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
     const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
     const KvFormat fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32;
@@ -676,24 +778,69 @@ extern "C" int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row
     (void)hipFree(list);
     (void)hipFree(dcall);
     if (!rc && (e != hipSuccess || es != hipSuccess)) {
-        set_error("rgrg_debug_roll_session_step: %s", hipGetErrorString(e != hipSuccess ? e : es));
+        set_error("%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
         return RGRG_EHIP;
     }
     return rc;
 }
 
+extern "C" int rgrg_debug_roll_session_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared,
+                                            const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before,
+                                            int submit, int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv,
+                                            void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16,
+                                            int fp16, void* stream) {
+    return debug_roll_session_step("rgrg_debug_roll_session_step", row_seq, row_len, row_tok, row_pos, row_step, shared, arg, ids, lp, ld_ids,
+                                   lens, C, n, S_before, submit, handout, retire, R, max_length, ukv, ld_ukv, kv, layer_stride, kv_stride, H,
+                                   T_slots, n_layer, kv16, fp16, nullptr, stream);
+}
+
+// The request ring `req` [C] of a test hook, read back and checked on the host before any kernel trusts it: limits 2 .. max_length
+// (0: not checked - the sampler hook), parameters the sampler accepts, stop ids below 65535 or unused.  Synchronises `st`.
+static int debug_check_req_ring(const char* who, const void* req, int C, int max_length, hipStream_t st) {
+    std::vector<RollReq> h((size_t)C);
+    RGRG_HIP(hipMemcpyAsync(h.data(), req, (size_t)C * sizeof(RollReq), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < C; ++i) {
+        const RollReq& q = h[(size_t)i];
+        const bool ok = (max_length == 0 || (q.max_length >= 2 && q.max_length <= max_length)) && q.inv_T > 0.f && q.top_k >= 0 &&
+                        q.top_p > 0.f && q.top_p <= 1.0f && q.q0 >= 0;
+        if (!ok) {
+            set_error("%s: request ring entry %d: max_length %d (2 .. %d), 1 / temperature %g (> 0), top_k %d (>= 0), top_p %g ((0, 1]), q0 %d (>= 0)",
+                      who, i, q.max_length, max_length, (double)q.inv_T, q.top_k, (double)q.top_p, q.q0);
+            return RGRG_EINVAL;
+        }
+    }
+    return RGRG_OK;
+}
+
+// Test hook: rgrg_debug_roll_session_step with the caller's request ring `req` [C] (40-byte entries, include/rgrg_hip.h "Request ring";
+// NULL: the hook above).  The submit-init does not write the ring: the caller has written the entries of the new sequences.
+extern "C" int rgrg_debug_roll_session_step_req(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared,
+                                                const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n,
+                                                int S_before, int submit, int handout, int retire, int R, int max_length,
+                                                const float* ukv, int ld_ukv, void* kv, size_t layer_stride, size_t kv_stride, int H,
+                                                int T_slots, int n_layer, int kv16, int fp16, const void* req, void* stream) {
+    const char* who = "rgrg_debug_roll_session_step_req";
+    RGRG_CHECK_ARG(C > 0 && max_length >= 2);
+    int rc;
+    if (req && (rc = debug_check_req_ring(who, req, C, max_length, as_stream(stream)))) return rc;
+    return debug_roll_session_step(who, row_seq, row_len, row_tok, row_pos, row_step, shared, arg, ids, lp, ld_ids, lens, C, n, S_before,
+                                   submit, handout, retire, R, max_length, ukv, ld_ukv, kv, layer_stride, kv_stride, H, T_slots, n_layer,
+                                   kv16, fp16, static_cast<const RollReq*>(req), stream);
+}
+
 // Test hook: the rolling sampler (roll_sample_kernel as a STEP_ROLL_SAMPLE step launches it) on the caller's state.  Device: logits f32
 // [R][ld], row_seq / row_len / arg int32 [R], lp f32 [largest sequence + 1][ld_lp] or NULL.  Synchronises `stream`.
-extern "C" int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len,
-                                      float temperature, int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp,
-                                      void* stream) {
+static int debug_roll_sample(const char* who, const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len,
+                             float temperature, int top_k, float top_p, uint64_t seed, const RollReq* req, int C, int* arg, float* lp,
+                             int ld_lp, void* stream) {
     RGRG_CHECK_ARG(logits && row_seq && row_len && arg && R > 0 && R < 65536 && V > 0 && ld >= V && (!lp || ld_lp >= 2));
     hipStream_t st = as_stream(stream);
     void* prm = nullptr;
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc(&prm, sample_params_bytes()));
-    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(prm); set_error("rgrg_debug_roll_sample: hipMalloc failed"); return RGRG_EHIP; }
-    const RollCall call{nullptr, nullptr, nullptr, ld_lp, 0, 0, 0, lp, 1, 0x7fffffff, 0x7fffffff};   // no ring: the row is the sequence
+    if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(prm); set_error("%s: hipMalloc failed", who); return RGRG_EHIP; }
+    const RollCall call{nullptr, nullptr, nullptr, ld_lp, 0, 0, 0, lp, 1, C, C, req};   // C = 0x7fffffff: no ring, the row is the sequence
     int rc = enqueue_sample_params(prm, temperature, top_k, top_p, seed, st);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
@@ -702,8 +849,32 @@ extern "C" int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, in
     (void)hipFree(prm);
     (void)hipFree(dcall);
     if (!rc && (e != hipSuccess || es != hipSuccess)) {
-        set_error("rgrg_debug_roll_sample: %s", hipGetErrorString(e != hipSuccess ? e : es));
+        set_error("%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
         return RGRG_EHIP;
     }
     return rc;
+}
+
+extern "C" int rgrg_debug_roll_sample(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len,
+                                      float temperature, int top_k, float top_p, uint64_t seed, int* arg, float* lp, int ld_lp,
+                                      void* stream) {
+    return debug_roll_sample("rgrg_debug_roll_sample", logits, ld, V, R, row_seq, row_len, temperature, top_k, top_p, seed, nullptr,
+                             0x7fffffff, arg, lp, ld_lp, stream);
+}
+
+// Test hook: rgrg_debug_roll_sample with the caller's request ring `req` [C]: an active row draws with the parameters of entry
+// row_seq[r] % C under the counter (row_seq[r] - q0, row_len[r] - 1) and its log-prob goes to lp[(row_seq[r] % C) * ld_lp + row_len[r]].
+// (temperature, top_k, top_p, seed) fill the parameter block of the step, which the kernel must NOT read then.  req NULL: the hook
+// above (C is not used).
+extern "C" int rgrg_debug_roll_sample_req(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len,
+                                          float temperature, int top_k, float top_p, uint64_t seed, const void* req, int C, int* arg,
+                                          float* lp, int ld_lp, void* stream) {
+    const char* who = "rgrg_debug_roll_sample_req";
+    if (!req) return debug_roll_sample(who, logits, ld, V, R, row_seq, row_len, temperature, top_k, top_p, seed, nullptr, 0x7fffffff, arg, lp,
+                                       ld_lp, stream);
+    RGRG_CHECK_ARG(C > 0);
+    int rc;
+    if ((rc = debug_check_req_ring(who, req, C, 0, as_stream(stream)))) return rc;
+    return debug_roll_sample(who, logits, ld, V, R, row_seq, row_len, temperature, top_k, top_p, seed, static_cast<const RollReq*>(req), C,
+                             arg, lp, ld_lp, stream);
 }

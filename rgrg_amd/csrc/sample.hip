@@ -184,12 +184,23 @@ __global__ __launch_bounds__(SM_THREADS) void roll_sample_kernel(const float* __
     const int seq = row_seq[row];
     if (seq < 0) return;
     const int len = row_len[row];
+    const int slot = seq % call->C;   // the sequence's ring row (a one-shot call: C = S, the row itself)
+    // A session: the parameters and the counter row seq - q0 are those of the sequence's request; else the step's block
+    SampleParams prm;
+    unsigned rr = (unsigned)seq;
+    if (const RollReq* ring = call->req) {
+        const RollReq q = ring[slot];
+        prm = SampleParams{q.seed, q.inv_T, q.top_k, q.top_p, 0};
+        rr = (unsigned)(seq - q.q0);
+    } else {
+        prm = *prm_dev;
+    }
     int tok;
     float logq;
-    if (!sample_row<VEC>(logits + (size_t)row * ld, V, *prm_dev, (unsigned)seq, (unsigned)(len - 1), &tok, &logq)) return;
+    if (!sample_row<VEC>(logits + (size_t)row * ld, V, prm, rr, (unsigned)(len - 1), &tok, &logq)) return;
     arg[row] = tok;
     float* lp = call->lp;
-    if (lp) lp[(size_t)(seq % call->C) * call->ld + len] = logq;   // the sequence's ring row (a one-shot call: C = S, the row itself)
+    if (lp) lp[(size_t)slot * call->ld + len] = logq;
 }
 
 static int launch_sample(const float* logits, size_t ld, int S, int V, const SampleParams* prm_dev, SampleParams prm_val, int step,

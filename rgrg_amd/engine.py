@@ -841,7 +841,8 @@ class HipEngine:
         ``capacity``: the feature rows the session holds at a time (None: 4 * rows sequences); ``sample``: None = greedy, or
         ``dict(temperature, top_k, top_p, seed, num_return_sequences)``.  The decoder - cache, step plan, precision - is the one of
         ``rows`` token rows in the modes given HERE; later submits use them.  One session per engine: ValueError while another is
-        open.  Any other decode call on the engine makes the session stale.
+        open.  Any other decode call on the engine makes the session stale.  A submit may carry parameters of its own and
+        submitted sentences can be cancelled (rgrg_decoder_roll_submit_req / _cancel).
         ``beam``: ``dict(num_beams, early_stopping, length_penalty, num_return_sequences)`` opens a ``RollingBeamSession``
         (rgrg_decoder_beam_roll_open, DESIGN.md 7.17) on ``rows // num_beams`` slots instead; ``capacity`` then counts regions (None:
         4 * slots).  Not together with ``sample``."""

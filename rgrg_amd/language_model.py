@@ -404,6 +404,9 @@ class LanguageModel(EngineOwner):
         until sentences in front have been collected.  Precision and step plan are those of ``rows`` under the autocast state of
         THIS call.  Argument errors (ValueError, before any device work) are those of ``generate_rolling`` / ``sample_rolling``,
         ``rows`` is required; any other decode call on the model makes the session stale (RgrgHipError "stale").
+        What is given HERE holds for every submit that says nothing else: ``submit(feats, max_length=.., temperature=.., top_k=..,
+        top_p=.., seed=.., stop_token_ids=..)`` decodes its sentences with parameters of their own and ``cancel(qs)`` cuts
+        submitted sentences (not in a beam session).
         ``num_beams > 1``: ``beam_search_rolling`` over an open list -> a ``RollingBeamSession`` on
         ``rows // num_beams`` slots.  ``submit(feats)`` -> the range of REGION numbers, one per feature row; ``collect()`` ->
         ``(q, ids)`` with ids int64 [num_return_sequences, L_q], the rows ``generate(num_beams=..)`` gives the region.  ``capacity``

@@ -216,7 +216,9 @@ class ReportGenerationModel(EngineOwner):
         ``advance``; ``collect()`` -> ``(ticket, result)`` for every ticket whose sentences have all ended, ``result`` being the
         4-tuple ``generate_rolling(images)`` returns for that submit, or ``-1`` when no region was selected (such a ticket
         completes at once).  With ``num_beams > 1`` the regions are decoded by a ``RollingBeamSession`` and ``result`` is the 4-tuple
-        ``generate(images, num_beams=.., early_stopping=.., num_return_sequences=..)`` returns for that submit."""
+        ``generate(images, num_beams=.., early_stopping=.., num_return_sequences=..)`` returns for that submit.
+        ``submit(images, max_length=.., temperature=.., top_k=.., top_p=.., seed=.., stop_token_ids=..)`` decodes that submit's
+        sentences with parameters of their own and ``cancel(ticket)`` cuts them (``RollingSession``)."""
         from .rolling_session import ReportRollingSession
         return ReportRollingSession(self, self.language_model.open_rolling(
             max_length, rows=rows, capacity=capacity, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,

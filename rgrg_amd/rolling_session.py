@@ -1,11 +1,11 @@
-"""Rolling sessions: rolling-batch greedy decoding and sampling over an open list.  ``RollingSession`` is what
-``HipEngine.open_rolling`` / ``LanguageModel.open_rolling`` return - feature rows in, numbered sequences out -,
+"""Rolling sessions (per-submit parameters and cancel: 7.18): rolling-batch greedy decoding and sampling over an open
+list.  ``RollingSession`` is what ``HipEngine.open_rolling`` / ``LanguageModel.open_rolling`` return - feature rows in, numbered sequences out -,
 ``ReportRollingSession`` what ``ReportGenerationModel.open_rolling`` returns - images in, one ``generate_rolling`` result per
 submit out.  Every FLOP runs in ``librgrg_hip.so`` (rgrg_decoder_roll_*)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import Iterable, List, Optional, Union
 
 import torch
 
@@ -27,6 +27,7 @@ class RollingSession:
         self.unfinished = 0         # sequences pending or in a row, as of the last advance plus what was submitted since
         self.steps = 0              # the device's count of steps that had a sequence in a row
         self._collected = set()     # delivered sequences at or above the watermark
+        self.cancelled = set()      # sequences that ``cancel`` has cut, as their delivery by ``collect`` told
         self._known_stale = False
         self._hold = []
 
@@ -57,21 +58,80 @@ class RollingSession:
         return self._dec is None
 
     # ------------------------------------------------------------------ the calls
-    def submit(self, feats: torch.Tensor) -> range:
+    def _request(self, max_length=None, temperature=None, top_k=None, top_p=None, seed=None, stop_token_ids=None):
+        """The keywords of ``submit`` -> the arguments of rgrg_decoder_roll_submit_req behind m, or None when no keyword is given
+        (ValueError before anything is enqueued)."""
+        from .language_model import check_sample_args
+        sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        given = [k for k, v in sampling.items() if v is not None]
+        if max_length is None and not given and stop_token_ids is None:
+            return None
+        if max_length is not None and (int(max_length) != max_length or not 2 <= max_length <= self.max_length):
+            raise ValueError(f"max_length of a submit has to be in 2 .. {self.max_length} (the session's), but is {max_length}")
+        if given and not self.sampled:
+            raise ValueError(f"{', '.join(given)}: sampling parameters of a submit need a sampling session, this is a greedy session")
+        check_sample_args(1.0 if temperature is None else temperature, 0 if top_k is None else top_k, 1.0 if top_p is None else top_p, 1)
+        if seed is not None and int(seed) != seed:
+            raise ValueError(f"seed has to be an integer, but is {seed}")
+        stops = [] if stop_token_ids is None else list(stop_token_ids)
+        if len(stops) > 4:
+            raise ValueError(f"stop_token_ids holds {len(stops)} token ids, up to 4 are possible")
+        for t in stops:
+            if int(t) != t or not 0 <= t < 65535:
+                raise ValueError(f"stop_token_ids has to hold token ids in 0 .. 65534, but holds {t}")
+        return (0 if max_length is None else int(max_length), 0.0 if temperature is None else float(temperature),
+                -1 if top_k is None else int(top_k), 0.0 if top_p is None else float(top_p), 0 if seed is None else 1,
+                0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF, (C.c_int * max(len(stops), 1))(*[int(t) for t in stops]), len(stops))
+
+    def submit(self, feats: torch.Tensor, *, max_length: Optional[int] = None, temperature: Optional[float] = None,
+               top_k: Optional[int] = None, top_p: Optional[float] = None, seed: Optional[int] = None,
+               stop_token_ids: Optional[Iterable[int]] = None) -> range:
         """feats [m, 1024] on the engine's device -> the sequence numbers of its m * n sentences.  Enqueued behind the steps already
-        launched; an idle row starts a new sentence in the very next step.  Does not wait for the device."""
+        launched; an idle row starts a new sentence in the very next step.  Does not wait for the device.
+        The keywords hold for all m * n sentences of this submit, None being the session's value: ``max_length`` in
+        2 .. the session's; ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` in a sampling session only, validated as ``sample``
+        does (``top_k=1``: a greedy sentence); with ``seed`` the sentences draw what ``sample_rolling(feats, .., seed=seed)`` draws for
+        these rows alone; ``stop_token_ids``: up to 4 token ids that end a sentence as EOS does, the stop token being its last.
+        ValueError, the session as it was, for a value out of range."""
         lib, dec = self._live()
         if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] != 1024:
             raise ValueError(f"submit takes feature rows [m >= 1, 1024], got {tuple(feats.shape)}")
+        req = self._request(max_length=max_length, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, stop_token_ids=stop_token_ids)
         with torch.cuda.device(self._eng.device):
             f = feats.to(device=self._eng.device, dtype=torch.float32).contiguous()
             first = C.c_longlong(0)
-            self._check(self._fn("submit")(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), self._abi + "submit")
+            if req is None:
+                self._check(self._fn("submit")(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), self._abi + "submit")
+            else:
+                self._check(lib.rgrg_decoder_roll_submit_req(dec, _hip.ptr(f), f.shape[0], *req, C.byref(first), self._eng._s()),
+                            "rgrg_decoder_roll_submit_req")
             self._hold.append(f)   # the GEMMs read it on the decoder's stream: kept until an advance has synchronised
         count = f.shape[0] * self.n
         self.submitted = first.value + count
         self.unfinished += count
         return range(first.value, first.value + count)
+
+    def cancel(self, qs: Union[int, Iterable[int]]) -> None:
+        """Cancels sequences - a number or an iterable of numbers at or above the watermark and below ``submitted`` (ValueError
+        otherwise, nothing cancelled).  Enqueued on the decoder's stream: the next step launched cuts a sequence that is running
+        (that step's token is not appended, its row takes the next pending sequence in the same step); a pending one is cut in the
+        first step of the row it takes, as BOS alone; one that has ended is left as it is.  ``collect`` delivers a cut sequence with
+        the tokens it had, and ``cancelled`` then holds its number."""
+        lib, dec = self._live()
+        qs = [qs] if isinstance(qs, int) else list(qs)
+        for q in qs:
+            if int(q) != q or not self.watermark <= q < self.submitted:
+                raise ValueError(f"cancel: sequence {q}, {self.watermark} .. {self.submitted - 1} can be cancelled (collected and "
+                                 f"released ones, and ones not submitted yet, cannot)")
+        qs = sorted(set(int(q) for q in qs))
+        with torch.cuda.device(self._eng.device):
+            i = 0
+            while i < len(qs):   # whole runs of consecutive numbers
+                j = i
+                while j + 1 < len(qs) and qs[j + 1] == qs[j] + 1:
+                    j += 1
+                self._check(lib.rgrg_decoder_roll_cancel(dec, qs[i], j - i + 1), "rgrg_decoder_roll_cancel")
+                i = j + 1
 
     def advance(self, steps: Optional[int] = None) -> int:
         """Runs up to ``steps`` decode steps (None: until nothing is unfinished) and waits for them -> the steps launched; 0 at once
@@ -90,7 +150,8 @@ class RollingSession:
     def collect(self) -> List[tuple]:
         """Every finished sequence not delivered yet, in ascending q: ``(q, ids)`` - int64 [len], BOS first, the EOS included - and for
         a sampling session ``(q, ids, logprobs)``.  Sequences finish out of order and are delivered so; the ring is released over
-        the delivered PREFIX only, so one long sentence in front keeps the room of those behind it."""
+        the delivered PREFIX only, so one long sentence in front keeps the room of those behind it.  A sequence that ``cancel`` has
+        cut is delivered likewise, with the tokens it had and no EOS added, and joins ``cancelled``."""
         lib, dec = self._live()
         first, count = self.watermark, self.submitted - self.watermark
         if count == 0:
@@ -98,7 +159,7 @@ class RollingSession:
         lens = (C.c_int * count)()
         with torch.cuda.device(self._eng.device):
             self._check(lib.rgrg_decoder_roll_collect(dec, first, count, None, None, lens, self._eng._s()), "rgrg_decoder_roll_collect")
-            new = [i for i in range(count) if lens[i] > 0 and first + i not in self._collected]
+            new = [i for i in range(count) if lens[i] != 0 and first + i not in self._collected]   # (< 0: cut by cancel)
             if not new:
                 return []
             lo, span = new[0], new[-1] - new[0] + 1
@@ -109,9 +170,11 @@ class RollingSession:
                         "rgrg_decoder_roll_collect")
             out = []
             for i in new:
-                row = (first + i, ids[i - lo, :lens[i]])   # (views of this call's own copy of the ring rows)
-                out.append(row + (lp[i - lo, :lens[i]],) if self.sampled else row)
+                row = (first + i, ids[i - lo, :abs(lens[i])])   # (views of this call's own copy of the ring rows)
+                out.append(row + (lp[i - lo, :abs(lens[i])],) if self.sampled else row)
                 self._collected.add(first + i)
+                if lens[i] < 0:
+                    self.cancelled.add(first + i)
             wm = self.watermark
             while wm in self._collected:
                 self._collected.discard(wm)
@@ -150,6 +213,19 @@ class RollingBeamSession(RollingSession):
     def __init__(self, engine, dec, rows: int, capacity: int, max_length: int, num_beams: int, num_return_sequences: int):
         super().__init__(engine, dec, rows, capacity, 1, max_length, False)
         self.num_beams, self.num_return_sequences, self.slots = num_beams, num_return_sequences, rows // num_beams
+
+    def _request(self, **params):
+        if any(v is not None for v in params.values()):
+            raise ValueError(f"{', '.join(k for k, v in params.items() if v is not None)}: a rolling beam session takes no parameters "
+                             f"per submit (its scheduler lives on the host)")
+        return None
+
+    def submit(self, feats: torch.Tensor, **params) -> range:
+        self._request(**params)
+        return super().submit(feats)
+
+    def cancel(self, qs) -> None:
+        raise ValueError("cancel: a rolling beam session cannot cancel a region (its scheduler lives on the host)")
 
     def collect(self) -> List[tuple]:
         """Every finished region not delivered yet, in ascending q: ``(q, ids)`` with ids int64 [num_return_sequences, L_q] - the rows
@@ -193,21 +269,46 @@ class ReportRollingSession:
         self._model, self.session = model, session
         self._tickets = {}      # ticket -> [range of sequences, rest of the 4-tuple, {q: ids}]
         self._done = []         # (ticket, -1) of submits without a selected region
+        self._cancelled = set()
         self._next = 0
 
     @torch.no_grad()
-    def submit(self, images: torch.Tensor) -> int:
+    def submit(self, images: torch.Tensor, **params) -> int:
+        """``params``: the keywords of ``RollingSession.submit`` for the sentences of these images.  An argument error leaves
+        the session as it was and takes no ticket."""
         m = self._model
         if self.session.closed:
             raise _hip.RgrgHipError("the rolling session is closed")
         _, detections, top_region_features, class_detected = m.object_detector(images)
         selected_regions, feats = m.binary_classifier_region_selection(top_region_features, class_detected, return_loss=False)
-        ticket, self._next = self._next, self._next + 1
         if feats.shape[0] == 0:
+            self.session._request(**params)   # (the argument errors of a submit that has sentences)
+            rng = None
+        else:
+            rng = self.session.submit(feats, **params)
+        ticket, self._next = self._next, self._next + 1
+        if rng is None:
             self._done.append((ticket, -1))
         else:
-            self._tickets[ticket] = [self.session.submit(feats), (selected_regions, detections, class_detected), {}]
+            self._tickets[ticket] = [rng, (selected_regions, detections, class_detected), {}]
         return ticket
+
+    def cancel(self, ticket: int) -> None:
+        """Cancels the sentences of a ticket that have not ended (``RollingSession.cancel``); the ticket completes with the cut
+        sentences and is in ``cancelled`` then if at least one was cut.  A ticket that has been delivered: ValueError."""
+        if ticket not in self._tickets:
+            if any(t == ticket for t, _ in self._done):
+                return   # (no region was selected: nothing runs)
+            raise ValueError(f"cancel: ticket {ticket} is not open (never given, or delivered already)")
+        rng, _, got = self._tickets[ticket]
+        qs = [q for q in rng if q not in got]
+        if qs:
+            self.session.cancel(qs)
+
+    @property
+    def cancelled(self) -> set:
+        """Tickets of which ``cancel`` has cut at least one sentence, as their sentences' delivery told."""
+        return self._cancelled
 
     def advance(self, steps: Optional[int] = None) -> int:
         return self.session.advance(steps)
@@ -224,6 +325,9 @@ class ReportRollingSession:
                     if item[0] in rng:
                         got[item[0]] = item[1]
                         break
+            for ticket, (rng, _, _) in self._tickets.items():
+                if any(q in self.session.cancelled for q in rng):
+                    self._cancelled.add(ticket)
         for ticket in sorted(self._tickets):
             rng, rest, got = self._tickets[ticket]
             if len(got) == len(rng):

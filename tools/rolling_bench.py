@@ -19,7 +19,8 @@ unrepeated rows into ``--submits`` submits that arrive ``--gap`` steps apart int
 ``advance(gap)`` between them; a second pass with ``advance(1)`` gives, per submit, the steps from its arrival to its last sentence);
 ``--session arrivals-generate`` / ``arrivals-rolling`` are what a tree without sessions offers for the same arrivals - one
 ``generate()`` / one ``generate_rolling`` per arrival, a call starting when the one before it has returned (they use nothing newer
-than ``generate_rolling``, so this file also runs them on such a tree).
+than ``generate_rolling``, so this file also runs them on such a tree).  ``--requests``: every submit of ``--session
+all`` / ``arrivals`` carries request parameters that change no result (the session's max_length, EOS as a stop token).
 Usage: python tools/rolling_bench.py --mode rolling --rows 128 256 464 928 [--repeat 4] [--weights bench|ragged] [--runs 3]
 Prints one JSON line per configuration: sequences, length histogram, steps executed, the longest sequence's steps, sum of the
 steps every sequence needs / rows, ms per call (median of --runs after one warm-up), ms per step, generated tokens per second."""
@@ -68,6 +69,7 @@ def run_session(args, model, lm, batch, stream, L, report):
             out[q, :ids.shape[0]] = ids.cpu()
         return out
 
+    req = dict(max_length=L, stop_token_ids=[EOS]) if args.requests else {}   # values that change no result: the request path alone
     if args.session == "all":
         for R in args.rows:
             S = int(stream.shape[0])
@@ -75,7 +77,7 @@ def run_session(args, model, lm, batch, stream, L, report):
 
             def run():
                 with lm.open_rolling(L, rows=R, capacity=S) as ses:   # (open and close are part of the call: the rings are allocated)
-                    ses.submit(stream)
+                    ses.submit(stream, **req)
                     ses.advance()
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
@@ -105,7 +107,7 @@ def run_session(args, model, lm, batch, stream, L, report):
                                     i = max(j for j in range(len(first)) if first[j] <= q)
                                     latency[i] = max(latency[i], clock - i * gap)
                     for c in chunks:
-                        ses.submit(c)
+                        ses.submit(c, **req)
                         tick(gap)
                     while ses.unfinished:
                         tick(gap if latency is None else 1)
@@ -144,6 +146,7 @@ def main():
     ap.add_argument("--session", choices=("all", "arrivals", "arrivals-generate", "arrivals-rolling"))
     ap.add_argument("--submits", type=int, default=8)
     ap.add_argument("--gap", type=int, default=8)
+    ap.add_argument("--requests", action="store_true", help="--session all / arrivals: every submit carries request parameters (DESIGN.md 7.18)")
     ap.add_argument("--rows", type=int, nargs="*", default=[128, 256, 464, 928])
     ap.add_argument("--repeat", type=int, default=4)
     ap.add_argument("--images", type=int, default=32)
@@ -181,6 +184,8 @@ def main():
         stream = batch
     base = {"mode": args.mode, "weights": args.weights, "dtype": args.dtype, "max_length": L, "sequences": int(stream.shape[0]),
             "rows_per_image_batch": int(batch.shape[0]), "repeat": args.repeat, "data": "synthetic weights and images"}
+    if args.session:
+        base["requests"] = bool(args.requests)
     if sampling:
         base.update(draw, hypotheses=args.hypotheses, sequences=int(batch.shape[0]) * args.hypotheses, repeat=1)
 
