@@ -909,6 +909,73 @@ int rgrg_debug_ce_backward(float* logits, int64_t ld, int V, int row0, int rows,
 int rgrg_debug_gelu(const float* pre, float* out, float* d, int64_t n, void* stream);
 int rgrg_debug_dropout_add(const float* src, const float* resid, float* out, int64_t n, uint64_t seed, uint32_t stream_id, float p,
                            void* stream);
+/* Test hooks for the kernels that start a decode step and for the bookkeeping kernels between steps (embedding + LayerNorm, the cache
+ * writes of the image slot and of a prompt, positions and masks of src/language_model/language_model.py:298-334 and :498-527, the
+ * ancestor tables of beam search).  As above: the product's own launchers - its grids, grid-stride loops included - on the caller's
+ * device buffers, no decoder object; rows are D == 1024 floats where a D is passed.  Token ids and positions that index a table are the
+ * caller's to keep inside it unless the kernel is documented to clamp.  RGRG_EINVAL with rgrg_last_error() set for a missing operand,
+ * rows / S / R < 1, D != 1024, fp16 != 0 where no 16-bit output or cache is selected, and what each entry names below.
+ * rgrg_debug_ln_rows: ln_rows_kernel - LayerNorm(x[row]) * g + b into xn16 (bf16; fp16 != 0: IEEE half) when it is given, else into xn
+ *   (fp32); with both given, as the decode step gives them, xn is not written.
+ * rgrg_debug_embed_ln: embed_ln_kernel - x[s] = wte[token] + wte[position] (fp32), token = tok_override[s] or ids[s][*step], position
+ *   = pos_override[s] or *step.  Then one of three outputs: stats given: xn16 = round16(x) and stats f32 [rows][16][2] = (sum x, sum
+ *   x^2) in slot 0, zeros in slots 1 .. 15; else xn16 given: round16(LayerNorm(x)); else xn (fp32).  An output of another mode that is
+ *   given as well is not written.
+ * rgrg_debug_embed_seq_ln: embed_seq_ln_kernel over S x T token rows - x = wte[ids] + wte[position], xn = LayerNorm(x); position =
+ *   t, or pos_ids[row % pos_rows] with pos_rows == S * T ([S,T]) or T ([1,T] broadcast; anything else: RGRG_EINVAL).  An id or a
+ *   position outside [0, V) is clamped (negative: 0, else V - 1) and *id_error is OR-ed with 1; clean inputs leave it alone.
+ * rgrg_debug_kv_slot0: kv_slot0_kernel - ukv f32 [S][ld], column (l * 2 + kv) * H * 64 + d -> slot 0 of head d / 64 of cache row
+ *   s * row_mul, plane kv of layer l at element l * layer_stride + kv * kv_stride of kv, planes [rows][H][slots][64].  kv_bytes 4: fp32
+ *   copy; 2: one rounding to bf16 / fp16; 1: clamp to +-448 and one rounding to e4m3.  RGRG_EINVAL: another kv_bytes, fp16 != 0 unless
+ *   kv_bytes == 2, ld < L * 2 * H * 64, strides that let the planes the launch writes overlap.
+ * rgrg_debug_decode_reset: decode_reset_kernel - ids [S][ld_ids >= L]: column 0 = BOS, columns 1 .. L - 1 = PAD (both 50256);
+ *   finished [S] = 0, *step = 0, *done_len = 0, sync [2] = 0.
+ * rgrg_debug_beam_first_mask: kmask f32 [R][slots] = -1e4 on slots 1 .. first[r], 0 elsewhere.
+ * rgrg_debug_key_mask: key_mask_kernel - kmask f32 [S][slots] = (1 - am[s][j - 1]) * -1e4 on slots 1 .. L of am f32 [S][L], 0 on the
+ *   image slot 0 and behind L (:316-334).
+ * rgrg_debug_forward_cached_tokens: tok [S] = ids[s][j] and, with pos_ids, row_pos [S] = pos_ids[s][j] of int64 [S][T], both clamped
+ *   into [0, V); *step = position.  Without pos_ids row_pos is not written.
+ * rgrg_debug_prompt_mask_scan: pad [S] = the zeros in front of row s of am f32 [S][T]; *flags |= 1 a row of zeros only, 2 a zero
+ *   behind a one, 4 some row is padded, 8 a value other than 0 and 1.  The caller clears *flags.
+ * rgrg_debug_prompt_setup: prompt_setup_kernel - ids [S][ld_ids >= T] columns 0 .. T - 1 = the prompt clamped into [0, V); *step =
+ *   T - 1; with pad [S]: pos int64 [S][T] = t - pad[s], 1 where t < pad[s] (cumsum(mask) - 1, masked_fill 1, :506-509); with kmask
+ *   f32 [S][slots]: -1e4 on slots 1 .. pad[s], 0 elsewhere.  RGRG_EINVAL: kmask without pad, pad without pos, kmask with slots <= T.
+ * rgrg_debug_prompt_kv_store: prompt_kv_store_kernel - the k and v thirds of qkv f32 [S * T][3 * H * 64] -> slots 1 .. T of cache row
+ *   s * row_mul of kplane / vplane [rows][H][slots][64]; kv_bytes 4 (copy) or 2 (one rounding; fp16 as above).  RGRG_EINVAL: slots <= T.
+ * rgrg_debug_prompt_last_rows: xn [R][D] (and xn16, when given) = row (r / row_div) * T + T - 1 of xn_all f32 [..][D].
+ * rgrg_debug_prompt_step_rows: tok [S] = (int) ids[s][*step], row_pos [S] = *step - pad[s].
+ * rgrg_debug_beam_prompt_init: slots 0 .. T of rows 0 .. R - 1 of src_a and src_b int32 [R][slots] = (r / nb) * nb; beam_pad [R] =
+ *   pad[r / nb], or 0 without pad.  RGRG_EINVAL: R % nb != 0, slots <= T.
+ * rgrg_debug_beam_row_pos: row_pos [R] = *step - beam_pad[r].
+ * rgrg_debug_beam_init: slot 0 of every row of src int32 [R][T] = (r / nb) * nb; *step = 0.
+ * rgrg_debug_beam_advance: beam_advance_kernel - src_new[r][0 .. t] = src_old[parent[r]][0 .. t], src_new[r][t + 1] = parent[r], t =
+ *   *step; tables int32 [R][T].  *step and parent are read back and checked first (the call synchronises): 0 <= *step <= T - 2 and
+ *   0 <= parent[r] < R, else RGRG_EINVAL; so is src_old == src_new. */
+int rgrg_debug_ln_rows(const float* x, const float* g, const float* b, float* xn, uint16_t* xn16, int fp16, int rows, int D, void* stream);
+int rgrg_debug_embed_ln(const float* wte, const int64_t* ids, int ld_ids, const int* step, const int* tok_override, const int* pos_override,
+                        const float* g, const float* b, float* x, float* xn, uint16_t* xn16, float* stats, int fp16, int rows, int D,
+                        void* stream);
+int rgrg_debug_embed_seq_ln(const float* wte, const int64_t* ids, const int64_t* pos_ids, int pos_rows, const float* g, const float* b,
+                            float* x, float* xn, int* id_error, int S, int T, int D, int V, void* stream);
+int rgrg_debug_kv_slot0(const float* ukv, int ld, void* kv, int64_t layer_stride, int64_t kv_stride, int S, int H, int slots, int L,
+                        int row_mul, int kv_bytes, int fp16, void* stream);
+int rgrg_debug_decode_reset(int64_t* ids, int ld_ids, int* finished, int* step, int* done_len, int* sync, int S, int L, void* stream);
+int rgrg_debug_beam_first_mask(const int* first, int R, int slots, float* kmask, void* stream);
+int rgrg_debug_key_mask(const float* am, int L, int S, int slots, float* kmask, void* stream);
+int rgrg_debug_forward_cached_tokens(const int64_t* ids, const int64_t* pos_ids, int T, int j, int S, int V, int* tok, int* row_pos,
+                                     int* step, int position, void* stream);
+int rgrg_debug_prompt_mask_scan(const float* am, int S, int T, int* pad, int* flags, void* stream);
+int rgrg_debug_prompt_setup(const int64_t* in, int S, int T, int V, int64_t* ids, int ld_ids, int* step, const int* pad, int64_t* pos,
+                            float* kmask, int slots, void* stream);
+int rgrg_debug_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul, int kv_bytes,
+                               int fp16, void* stream);
+int rgrg_debug_prompt_last_rows(const float* xn_all, int T, int D, float* xn, uint16_t* xn16, int fp16, int R, int row_div, void* stream);
+int rgrg_debug_prompt_step_rows(const int64_t* ids, int ld_ids, const int* step, const int* pad, int* tok, int* row_pos, int S,
+                                void* stream);
+int rgrg_debug_beam_prompt_init(int* src_a, int* src_b, int slots, int nb, int R, int T, const int* pad, int* beam_pad, void* stream);
+int rgrg_debug_beam_row_pos(const int* step, const int* beam_pad, int* row_pos, int R, void* stream);
+int rgrg_debug_beam_init(int* src, int T, int nb, int R, int* step, void* stream);
+int rgrg_debug_beam_advance(const int* src_old, int* src_new, const int* parent, int* step, int T, int R, void* stream);
 /* ---- test hooks of the weight-streaming ("skinny") GEMMs of <= 128 token rows: the fused decode plan (skinny_direct.inc) and the
  * prefill GEMMs (decoder.hip).  No decoder object: device pointers of the caller, launched on `stream`, through the shape rules,
  * packing steps and kernel dispatch of the product path.  Every argument is validated first: RGRG_EINVAL with rgrg_last_error() set

@@ -157,7 +157,24 @@ SIGNATURES = {
     "rgrg_debug_ce_backward": (_i, [_p, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _i, _p]),
     "rgrg_debug_gelu": (_i, [_p, _p, _p, C.c_int64, _p]),
     "rgrg_debug_dropout_add": (_i, [_p, _p, _p, C.c_int64, C.c_uint64, C.c_uint32, _f, _p]),
-    "rgrg_decoder_copy_last_logits": (_i, [_p, _p, _i, _p]),
+    "rgrg_debug_ln_rows": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "rgrg_debug_embed_ln": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "rgrg_debug_embed_seq_ln": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "rgrg_debug_kv_slot0": (_i, [_p, _i, _p, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_decode_reset": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "rgrg_debug_beam_first_mask": (_i, [_p, _i, _i, _p, _p]),
+    "rgrg_debug_key_mask": (_i, [_p, _i, _i, _i, _p, _p]),
+    "rgrg_debug_forward_cached_tokens": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p]),
+    "rgrg_debug_prompt_mask_scan": (_i, [_p, _i, _i, _p, _p, _p]),
+    "rgrg_debug_prompt_setup": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _p]),
+    "rgrg_debug_prompt_kv_store": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rgrg_debug_prompt_last_rows": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _p]),
+    "rgrg_debug_prompt_step_rows": (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
+    "rgrg_debug_beam_prompt_init": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "rgrg_debug_beam_row_pos": (_i, [_p, _p, _p, _i, _p]),
+    "rgrg_debug_beam_init": (_i, [_p, _i, _i, _i, _p, _p]),
+    "rgrg_debug_beam_advance": (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    "rgrg_decoder_copy_last_logits":(_i, [_p, _p, _i, _p]),
     "rgrg_box_match_f32": (_i, [_p, _p, _i, _p, C.c_int64, _p, _i, _i, _f, _f, _i, _p, _p, _p]),
     "rgrg_balanced_sample": (_i, [_p, _p, _i, _p, _p, C.c_uint64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "rgrg_rpn_loss_sampled_f32": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),

@@ -328,6 +328,15 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const float* __restrict__
     if (xn16) store_16x4(xn16 + (size_t)s * D + 4 * tid, o, f16);  // 16-bit-activation mode: the GEMMs read only this copy
     else reinterpret_cast<f32x4*>(xn + (size_t)s * D)[tid] = o;
 }
+// one workgroup per row; the three output modes are the kernel's: stats (raw 16-bit row + slots), else xn16, else xn
+static int launch_embed_ln(const float* wte, const long long* ids, int ld_ids, const int* step, const float* g, const float* b, float* x,
+                           float* xn, int D, const int* tok_override, unsigned short* xn16, int f16, const int* pos_override, float* stats,
+                           int rows, hipStream_t st) {
+    hipLaunchKernelGGL(embed_ln_kernel, dim3(rows), dim3(256), 0, st, wte, ids, ld_ids, step, g, b, x, xn, D, tok_override, xn16, f16,
+                       pos_override, stats);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 // xn[row] = LayerNorm(x[row]) (many-sequence path and the teacher-forced passes: the tiled GEMM's epilogue already added
 // bias + residual into x).  One WAVE per row of 1024 (four rows per workgroup): 16 values per lane as four coalesced 1-KiB
@@ -783,6 +792,22 @@ __global__ __launch_bounds__(256) void kv_slot0_kernel(const float* __restrict__
         else kv_all[o] = val;
     }
 }
+// The cache lives in one allocation with the same ELEMENT strides in every format (half / a quarter of the bytes used); f16 names the
+// 16-bit type and is read by that format alone.  1024 workgroups whatever the size: the kernel strides.
+static int launch_kv_slot0(const float* ukv, int ld, void* kv, size_t layer_stride, size_t kv_stride, int S, int H, int T, int L, int row_mul,
+                           KvFormat fmt, int f16, hipStream_t st) {
+    if (fmt == KV_E4M3)
+        hipLaunchKernelGGL(kv_slot0_kernel<uint8_t>, dim3(1024), dim3(256), 0, st, ukv, ld, static_cast<uint8_t*>(kv), layer_stride, kv_stride, S,
+                           H, T, L, row_mul, 0);
+    else if (fmt != KV_F32)
+        hipLaunchKernelGGL(kv_slot0_kernel<u16>, dim3(1024), dim3(256), 0, st, ukv, ld, static_cast<u16*>(kv), layer_stride, kv_stride, S, H, T, L,
+                           row_mul, f16);
+    else
+        hipLaunchKernelGGL(kv_slot0_kernel<float>, dim3(1024), dim3(256), 0, st, ukv, ld, static_cast<float*>(kv), layer_stride, kv_stride, S, H,
+                           T, L, row_mul, 0);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 // First-occurrence arg-max over the vocabulary (torch.argmax) fused with the greedy_search
 // bookkeeping (:629-650).  The lm_head GEMM already reduced every 16- / 32-column tile to one
@@ -858,6 +883,11 @@ __global__ __launch_bounds__(256) void decode_reset_kernel(long long* __restrict
         if (threadIdx.x == 0) { *step = 0; *done_len = 0; }
         if (threadIdx.x < 2) sync[threadIdx.x] = 0;
     }
+}
+static int launch_decode_reset(long long* ids, int ld_ids, int* finished, int* step, int* done_len, int* sync, int S, int L, hipStream_t st) {
+    hipLaunchKernelGGL(decode_reset_kernel, dim3(64), dim3(256), 0, st, ids, ld_ids, finished, step, done_len, sync, S, L);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
 }
 
 // LayerNorm(gain, beta) folded into the [N,K] weight of the GEMM behind it, 16-bit flavour (one wave per output column):
@@ -1545,11 +1575,11 @@ static int enqueue_step_tiled(rgrg_decoder* d, const StepSpec& s, bool count) {
         prod_r.Yb16 = xn16r; prod_r.stats_out = statr; cons_r.ln_stats = statr;
         const GemmLnFold* pfr = fold ? &prod_r : nullptr;
         const GemmLnFold* cfr = fold ? &cons_r : nullptr;
-        hipLaunchKernelGGL(embed_ln_kernel, dim3(rows), dim3(256), 0, rs, d->wte, d->ids + (size_t)r0 * d->max_len, d->max_len, d->step,
-                           d->layers[0].ln1_g, d->layers[0].ln1_b, x, xn, D, s.tok ? s.tok + r0 : nullptr, xn16r, d->f16(),
-                           s.row_pos ? s.row_pos + r0 : nullptr, fold ? statr : (float*)nullptr);
-        RGRG_LAUNCH_CHECK();
         int rc2;
+        if ((rc2 = launch_embed_ln(d->wte, d->ids + (size_t)r0 * d->max_len, d->max_len, d->step, d->layers[0].ln1_g, d->layers[0].ln1_b, x, xn,
+                                   D, s.tok ? s.tok + r0 : nullptr, xn16r, d->f16(), s.row_pos ? s.row_pos + r0 : nullptr,
+                                   fold ? statr : (float*)nullptr, rows, rs)))
+            return rc2;
         if ((rc2 = trace_mark(d, r0, 1000))) return rc2;
         for (int l = 0; l < d->n_layer; ++l) {
             const LayerW& w = d->layers[l];
@@ -1597,11 +1627,9 @@ StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad) {
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
     hipStream_t st = d->stream;
     const int D = d->D;
-    hipLaunchKernelGGL(decode_reset_kernel, dim3(64), dim3(256), 0, st, d->ids, d->max_len, d->finished, d->step,
-                       d->done_len, d->sync, S, d->max_len);
-    RGRG_LAUNCH_CHECK();
-    RGRG_HIP(hipMemcpyAsync(d->feats, feats, (size_t)S * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     int rc;
+    if ((rc = launch_decode_reset(d->ids, d->max_len, d->finished, d->step, d->done_len, d->sync, S, d->max_len, st))) return rc;
+    RGRG_HIP(hipMemcpyAsync(d->feats, feats, (size_t)S * D * sizeof(float), hipMemcpyDeviceToDevice, st));
     // feature_space_transformation_nn (:284) - needed once: only step 0 consumes it (:135-157)
     if ((rc = linear(d, d->fst0, d->feats, nullptr, d->h1, S, D, RGRG_ACT_RELU, false))) return rc;
     if ((rc = linear(d, d->fst2, d->h1, nullptr, d->img, S, D, RGRG_ACT_NONE, false))) return rc;
@@ -1609,17 +1637,8 @@ int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul) {
     if ((rc = linear(d, d->ukv, d->img, nullptr, d->ukv_out, S, d->ld_ukv, RGRG_ACT_NONE, false))) return rc;
     // the 16-bit / e4m3 cache lives in the same allocation with the same ELEMENT strides (half / a quarter of the bytes used)
     const KvFormat fmt = kv_format(d, S * row_mul);
-    if (fmt == KV_E4M3)
-        hipLaunchKernelGGL(kv_slot0_kernel<uint8_t>, dim3(1024), dim3(256), 0, st, d->ukv_out, d->ld_ukv,
-                           reinterpret_cast<uint8_t*>(d->kv), d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, 0);
-    else if (fmt != KV_F32)
-        hipLaunchKernelGGL(kv_slot0_kernel<u16>, dim3(1024), dim3(256), 0, st, d->ukv_out, d->ld_ukv,
-                           reinterpret_cast<u16*>(d->kv), d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, d->f16());
-    else
-        hipLaunchKernelGGL(kv_slot0_kernel<float>, dim3(1024), dim3(256), 0, st, d->ukv_out, d->ld_ukv, d->kv,
-                           d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, 0);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    return launch_kv_slot0(d->ukv_out, d->ld_ukv, d->kv, d->kv_layer_stride, d->kv_kv_stride, S, d->H, d->T, d->n_layer, row_mul, fmt,
+                           d->f16(), st);
 }
 
 }  // namespace rgrg
@@ -1906,6 +1925,18 @@ __global__ __launch_bounds__(256) void forward_cached_tokens_kernel(const long l
     }
     if (s == 0) *step = position;
 }
+static int launch_key_mask(const float* am, int L, int S, int T, float* kmask, hipStream_t st) {
+    hipLaunchKernelGGL(key_mask_kernel, dim3((S * T + 255) / 256), dim3(256), 0, st, am, L, S, T, kmask);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+static int launch_forward_cached_tokens(const long long* ids, const long long* pos_ids, int T, int j, int S, int V, int* tok, int* row_pos,
+                                        int* step, int position, hipStream_t st) {
+    hipLaunchKernelGGL(forward_cached_tokens_kernel, dim3((S + 255) / 256), dim3(256), 0, st, ids, pos_ids, T, j, S, V, tok, row_pos, step,
+                       position);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 }  // namespace rgrg
 
 // LanguageModel.forward(input_ids, ..., past_key_values, use_cache=True) (language_model.py:258-366, :396-399): the
@@ -1937,18 +1968,16 @@ extern "C" int rgrg_decoder_forward_cached(rgrg_decoder* d, const float* feats, 
     if (past_len == 0 && feats && (rc = enqueue_prefill(d, feats, S))) return rc;   // also resets the step counter to 0
     if (attention_mask) {   // [S][past_len + T]: padding inside the prompt / the past -> additive mask per cache slot
         if (!d->key_mask && (rc = dmalloc(d, (void**)&d->key_mask, (size_t)d->rows * d->T * sizeof(float), true))) return rc;
-        hipLaunchKernelGGL(key_mask_kernel, dim3((S * d->T + 255) / 256), dim3(256), 0, st, attention_mask, past_len + T, S, d->T, d->key_mask);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_key_mask(attention_mask, past_len + T, S, d->T, d->key_mask, st))) return rc;
     }
     StepSpec step;   // ... lm_head: logits, nothing else
     step.rows = S; step.tok = d->beam_tok; step.end = STEP_LOGITS;
     step.row_pos = position_ids ? d->row_pos : nullptr;   // embedding rows wte[position_ids[s][j]]; the cache slot stays past_len + j + 1
     step.key_mask = attention_mask ? d->key_mask : nullptr;
     for (int j = 0; j < T; ++j) {
-        hipLaunchKernelGGL(forward_cached_tokens_kernel, dim3((S + 255) / 256), dim3(256), 0, st,
-                           reinterpret_cast<const long long*>(input_ids), reinterpret_cast<const long long*>(position_ids), T, j, S, d->V,
-                           d->beam_tok, d->row_pos, d->step, past_len + j);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_forward_cached_tokens(reinterpret_cast<const long long*>(input_ids), reinterpret_cast<const long long*>(position_ids), T,
+                                               j, S, d->V, d->beam_tok, d->row_pos, d->step, past_len + j, st)))
+            return rc;
         if ((rc = enqueue_step(d, step, false))) return rc;
         RGRG_HIP(hipMemcpy2DAsync(logits_out + (size_t)j * d->V, (size_t)T * d->V * sizeof(float), d->logits,
                                   (size_t)d->ld_logits * sizeof(float), (size_t)d->V * sizeof(float), S, hipMemcpyDeviceToDevice, st));
@@ -2163,6 +2192,62 @@ extern "C" int rgrg_debug_ln_fold16(const float* w, const float* gain, const flo
                        fp16 ? 1 : 0);
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
+}
+
+// Test hooks of the kernels that start a decode step and of the bookkeeping kernels between steps (tests/test_gpu_step_rows.py; the
+// other files' kernels have theirs next to them).  No decoder: the caller's device buffers, the given stream, the launchers above.
+extern "C" int rgrg_debug_ln_rows(const float* x, const float* g, const float* b, float* xn, uint16_t* xn16, int fp16, int rows, int D,
+                                  void* stream) {
+    RGRG_CHECK_ARG(x && g && b && (xn || xn16) && rows >= 1 && D == 1024);   // both given, as the step gives them: xn16 is written
+    RGRG_CHECK_ARG(xn16 || !fp16);
+    return launch_ln_rows(x, g, b, xn, D, xn16, fp16 ? 1 : 0, rows, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_embed_ln(const float* wte, const int64_t* ids, int ld_ids, const int* step, const int* tok_override,
+                                   const int* pos_override, const float* g, const float* b, float* x, float* xn, uint16_t* xn16,
+                                   float* stats, int fp16, int rows, int D, void* stream) {
+    RGRG_CHECK_ARG(wte && step && x && rows >= 1 && D == 1024);
+    RGRG_CHECK_ARG(tok_override || (ids && ld_ids >= 1));
+    if (stats) RGRG_CHECK_ARG(xn16);                        // the raw 16-bit row and its slots
+    else RGRG_CHECK_ARG(g && b && (xn || xn16));            // LayerNorm as 16 bit where xn16 is given, else as fp32
+    RGRG_CHECK_ARG(xn16 || !fp16);
+    return launch_embed_ln(wte, reinterpret_cast<const long long*>(ids), ld_ids, step, g, b, x, xn, D, tok_override, xn16, fp16 ? 1 : 0,
+                           pos_override, stats, rows, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_kv_slot0(const float* ukv, int ld, void* kv, int64_t layer_stride, int64_t kv_stride, int S, int H, int slots, int L,
+                                   int row_mul, int kv_bytes, int fp16, void* stream) {
+    RGRG_CHECK_ARG(ukv && kv && S >= 1 && H >= 1 && slots >= 1 && L >= 1 && row_mul >= 1);
+    RGRG_CHECK_ARG(kv_bytes == 4 || kv_bytes == 2 || kv_bytes == 1);
+    RGRG_CHECK_ARG(kv_bytes == 2 || !fp16);   // the 16-bit type of a cache that is not 16 bit
+    const int64_t plane = ((int64_t)(S - 1) * row_mul + 1) * H * slots * 64;   // elements up to the end of the last row written
+    RGRG_CHECK_ARG((int64_t)ld >= (int64_t)L * 2 * H * 64 && kv_stride >= plane && layer_stride >= kv_stride + plane);
+    const KvFormat fmt = kv_bytes == 4 ? KV_F32 : kv_bytes == 1 ? KV_E4M3 : (fp16 ? KV_F16 : KV_BF16);
+    return launch_kv_slot0(ukv, ld, kv, (size_t)layer_stride, (size_t)kv_stride, S, H, slots, L, row_mul, fmt, fp16 ? 1 : 0, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_decode_reset(int64_t* ids, int ld_ids, int* finished, int* step, int* done_len, int* sync, int S, int L,
+                                       void* stream) {
+    RGRG_CHECK_ARG(ids && finished && step && done_len && sync && S >= 1 && L >= 1 && ld_ids >= L);
+    return launch_decode_reset(reinterpret_cast<long long*>(ids), ld_ids, finished, step, done_len, sync, S, L, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_beam_first_mask(const int* first, int R, int slots, float* kmask, void* stream) {
+    RGRG_CHECK_ARG(first && kmask && R >= 1 && slots >= 1);
+    return launch_beam_first_mask(first, R, slots, kmask, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_key_mask(const float* am, int L, int S, int slots, float* kmask, void* stream) {
+    RGRG_CHECK_ARG(am && kmask && S >= 1 && L >= 1 && slots >= 1);
+    return launch_key_mask(am, L, S, slots, kmask, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_forward_cached_tokens(const int64_t* ids, const int64_t* pos_ids, int T, int j, int S, int V, int* tok, int* row_pos,
+                                                int* step, int position, void* stream) {
+    RGRG_CHECK_ARG(ids && tok && step && S >= 1 && T >= 1 && j >= 0 && j < T && V >= 1);
+    RGRG_CHECK_ARG(!pos_ids || row_pos);
+    return launch_forward_cached_tokens(reinterpret_cast<const long long*>(ids), reinterpret_cast<const long long*>(pos_ids), T, j, S, V, tok,
+                                        row_pos, step, position, as_stream(stream));
 }
 
 // Test hooks of the two weight-streaming families (tests/test_gpu_skinny_gemms.py).  No decoder: the caller's device buffers, the

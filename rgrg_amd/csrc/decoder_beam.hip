@@ -346,6 +346,17 @@ __global__ __launch_bounds__(256) void beam_init_kernel(int* __restrict__ src, i
     if (r < R) src[(size_t)r * T] = (r / nb) * nb;  // slot 0 (image key/value) is stored once per item, in its first beam row
     if (r == 0) *step = 0;
 }
+// the two launches on raw pointers, shared by beam_search_run and the test hooks (rgrg_debug_beam_init / _advance)
+int launch_beam_init(int* src, int T, int nb, int R, int* step, hipStream_t st) {
+    hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, src, T, nb, R, step);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int launch_beam_advance(const int* src_old, int* src_new, const int* parent, int* step, int T, int R, hipStream_t st) {
+    hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_old, src_new, parent, step, T, R);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 // The two launches of a plain ranking, shared by beam_search_run and the test hooks (rgrg_debug_beam_row_topk / _merge), and the
 // one place that chooses the kernel.  More than 16 beams (K > BEAM_K): the K-round kernels on candidate rows K wide; up to 16: the
@@ -551,8 +562,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
     if (prompt) {
         if ((rc = enqueue_beam_prompt(d, *prompt, S, nb, &padded, &prompt_ids))) return rc;
     } else {
-        hipLaunchKernelGGL(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, st, d->src_a, d->T, nb, R, d->step);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_beam_init(d->src_a, d->T, nb, R, d->step, st))) return rc;
     }
 
     std::vector<std::vector<long long>> ids(R, std::vector<long long>(1, BOS_ID));
@@ -641,8 +651,7 @@ int rgrg::beam_search_run(rgrg_decoder* d, const float* feats, int S, int num_be
             first_ranking = false;
         } else {
             RGRG_HIP(hipMemcpyAsync(d->beam_parent, parent.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(beam_advance_kernel, dim3(R), dim3(256), 0, st, src_cur, src_nxt, d->beam_parent, d->step, d->T, R);
-            RGRG_LAUNCH_CHECK();
+            if ((rc = launch_beam_advance(src_cur, src_nxt, d->beam_parent, d->step, d->T, R, st))) return rc;
         }
         hipLaunchKernelGGL(beam_step_inc_kernel, dim3(1), dim3(64), 0, st, d->step);
         RGRG_LAUNCH_CHECK();
@@ -773,4 +782,30 @@ extern "C" int rgrg_debug_beam_merge(const float* row_max, const float* row_logs
     launch_beam_merge(row_max, row_logsum, top_val, top_tok, beam_scores, S, nb, V, score_scratch, out_score, out_tok, out_beam,
                       debug_force_wide(), st);
     return debug_sync("rgrg_debug_beam_merge", st);
+}
+
+// Test hooks: the two ancestor-table kernels of the plain loop alone (tests/test_gpu_step_rows.py).  rgrg_debug_beam_advance reads
+// *step and parent [R] back first (one synchronisation): 0 <= *step <= T - 2 and 0 <= parent[r] < R, or nothing is launched.
+extern "C" int rgrg_debug_beam_init(int* src, int T, int nb, int R, int* step, void* stream) {
+    RGRG_CHECK_ARG(src && step && T >= 1 && nb >= 1 && R >= 1);
+    return launch_beam_init(src, T, nb, R, step, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_beam_advance(const int* src_old, int* src_new, const int* parent, int* step, int T, int R, void* stream) {
+    RGRG_CHECK_ARG(src_old && src_new && src_old != src_new && parent && step && T >= 2 && R >= 1);
+    hipStream_t st = as_stream(stream);
+    std::vector<int> host(R + 1);
+    RGRG_HIP(hipStreamSynchronize(st));
+    RGRG_HIP(hipMemcpy(host.data(), parent, (size_t)R * sizeof(int), hipMemcpyDeviceToHost));
+    RGRG_HIP(hipMemcpy(&host[R], step, sizeof(int), hipMemcpyDeviceToHost));
+    if (host[R] < 0 || host[R] > T - 2) {
+        set_error("rgrg_debug_beam_advance: *step = %d, a table of %d slots takes 0 .. %d", host[R], T, T - 2);
+        return RGRG_EINVAL;
+    }
+    for (int r = 0; r < R; ++r)
+        if (host[r] < 0 || host[r] >= R) {
+            set_error("rgrg_debug_beam_advance: parent[%d] = %d, the table has rows 0 .. %d", r, host[r], R - 1);
+            return RGRG_EINVAL;
+        }
+    return launch_beam_advance(src_old, src_new, parent, step, T, R, st);
 }

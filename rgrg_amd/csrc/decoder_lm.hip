@@ -42,6 +42,12 @@ __global__ __launch_bounds__(256) void embed_seq_ln_kernel(const float* __restri
     reinterpret_cast<f32x4*>(x + (size_t)row * D)[tid] = v;
     reinterpret_cast<f32x4*>(xn + (size_t)row * D)[tid] = ln_row(v, g, b, sh, D);
 }
+static int launch_embed_seq_ln(const float* wte, const long long* ids, int T, const float* g, const float* b, float* x, float* xn, int D, int V,
+                               int* id_error, const long long* pos_ids, int pos_rows, int M, hipStream_t st) {
+    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, wte, ids, T, g, b, x, xn, D, V, id_error, pos_ids, pos_rows);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 // GPT2PseudoAttention.forward without layer_past (:124-160) and _attn (:84-122) over T tokens: keys/values are
 // [uk(img) ; k_0..k_{T-1}], scores / 8, future token columns replaced by -1e4 (the image column is never masked),
@@ -494,9 +500,9 @@ int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention
     const int D = d->D, M = S * T;
     hipStream_t st = d->stream;
     int rc;
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       d->tf.x, d->tf.xn, D, d->V, d->id_error, pos, pos_rows);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_embed_seq_ln(d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b, d->tf.x, d->tf.xn, D, d->V, d->id_error, pos,
+                                  pos_rows, M, st)))
+        return rc;
     for (int l = 0; l < d->n_layer; ++l) {
         const LayerW& w = d->layers[l];
         const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
@@ -726,9 +732,9 @@ static int tr_body16(rgrg_decoder* d, const long long* ids, const float* attenti
     const bool a16 = d->tr.a16;
     if (a16 && (rc = convert_f32_to_bf16(d->ukv_out, d->tr.ukv16, (size_t)S * LD, st, f16))) return rc;
 
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       xs(0), d->tf.xn, D, d->V, d->id_error, d->tf.pos, d->tf.pos_rows);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_embed_seq_ln(d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b, xs(0), d->tf.xn, D, d->V, d->id_error, d->tf.pos,
+                                  d->tf.pos_rows, M, st)))
+        return rc;
     d->tf.pos = nullptr; d->tf.pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
     // self.drop on the embeddings (language_model.py:311) and ln_1 of layer 0 as 16 bit
     if ((rc = launch_resid_dropout_ln16(xs(0), nullptr, nullptr, xs(0), d->layers[0].ln1_g, d->layers[0].ln1_b, d->tr.xn16, dp(0, 0), f16, M, D, st)))
@@ -845,9 +851,9 @@ extern "C" int rgrg_decoder_lm_loss_grad(rgrg_decoder* d, const float* feats, co
     if (h16) {
         if ((rc = tr_body16(d, ids, attention_mask, S, T, loss_scale, dropout_p, dropout_seed, loss_out))) return rc;
     } else {
-    hipLaunchKernelGGL(embed_seq_ln_kernel, dim3(M), dim3(256), 0, st, d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b,
-                       xs(0), d->tf.xn, D, d->V, d->id_error, d->tf.pos, d->tf.pos_rows);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_embed_seq_ln(d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b, xs(0), d->tf.xn, D, d->V, d->id_error, d->tf.pos,
+                                  d->tf.pos_rows, M, st)))
+        return rc;
     d->tf.pos = nullptr; d->tf.pos_rows = 1;   // consumed (rgrg_decoder_set_lm_positions)
     if (dropout_p > 0.f) {  // self.drop on the embeddings (language_model.py:311), then ln_1 of layer 0 again
         if ((rc = launch_dropout_add(xs(0), nullptr, xs(0), MD, DropoutParams{dropout_seed, 0u, dropout_p}, st))) return rc;
@@ -1040,4 +1046,14 @@ extern "C" int rgrg_debug_ce_finalize(const float* row_loss, const int* row_vali
                                       void* stream) {
     RGRG_CHECK_ARG(row_loss && row_valid && n > 0 && (loss || n_scored));
     return launch_ce_finalize(row_loss, row_valid, n, loss, n_scored, id_error, as_stream(stream));
+}
+
+// Test hook: embed_seq_ln_kernel alone (tests/test_gpu_step_rows.py), one workgroup per token row of S x T.
+extern "C" int rgrg_debug_embed_seq_ln(const float* wte, const int64_t* ids, const int64_t* pos_ids, int pos_rows, const float* g,
+                                       const float* b, float* x, float* xn, int* id_error, int S, int T, int D, int V, void* stream) {
+    RGRG_CHECK_ARG(wte && ids && g && b && x && xn && id_error && S >= 1 && T >= 1 && D == 1024 && V >= 1);
+    RGRG_CHECK_ARG((long long)S * T <= 0x7fffffffLL);
+    RGRG_CHECK_ARG(!pos_ids || pos_rows == T || pos_rows == S * T);   // [1,T] broadcast over the sentences, or [S,T]
+    return launch_embed_seq_ln(wte, reinterpret_cast<const long long*>(ids), T, g, b, x, xn, D, V, id_error,
+                               reinterpret_cast<const long long*>(pos_ids), pos_ids ? pos_rows : 1, S * T, as_stream(stream));
 }

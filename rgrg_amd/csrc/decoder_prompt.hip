@@ -134,6 +134,55 @@ __global__ __launch_bounds__(256) void prompt_step_rows_kernel(const long long* 
     row_pos[s] = t - pad[s];
 }
 
+// The launches of the kernels above on raw pointers: the product path below and the test hooks at the end of the file share them.
+int launch_prompt_mask_scan(const float* am, int S, int T, int* pad, int* flags, hipStream_t st) {
+    hipLaunchKernelGGL(prompt_mask_scan_kernel, dim3((S + 255) / 256), dim3(256), 0, st, am, S, T, pad, flags);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+// one thread per prompt token and, with kmask, per cache slot of the S rows
+int launch_prompt_setup(const long long* in, int S, int T, int V, long long* ids, int ld_ids, int* step, const int* pad, long long* pos,
+                        float* kmask, int slots, hipStream_t st) {
+    const int n = std::max(S * T, kmask ? S * slots : 0);
+    hipLaunchKernelGGL(prompt_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, st, in, S, T, V, ids, ld_ids, step, pad, pos, kmask, slots);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+// kv16: the planes are 16 bit in the type f16; at most 4096 workgroups, the kernel strides
+int launch_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul, bool kv16, int f16,
+                           hipStream_t st) {
+    const size_t total = (size_t)S * H * 2 * T * (kv16 ? 8 : 16);
+    const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096)), blk(256);
+    if (!kv16)
+        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, st, qkv, static_cast<float*>(kplane), static_cast<float*>(vplane), S, H, T,
+                           slots, 0, row_mul);
+    else
+        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, st, qkv, static_cast<u16*>(kplane), static_cast<u16*>(vplane), S, H, T,
+                           slots, f16, row_mul);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int launch_prompt_last_rows(const float* xn_all, int T, int D, float* xn, u16* xn16, int f16, int row_div, int R, hipStream_t st) {
+    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, xn_all, T, D, xn, xn16, f16, row_div);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int launch_prompt_step_rows(const long long* ids, int ld_ids, const int* step, const int* pad, int* tok, int* row_pos, int S, hipStream_t st) {
+    hipLaunchKernelGGL(prompt_step_rows_kernel, dim3((S + 255) / 256), dim3(256), 0, st, ids, ld_ids, step, pad, tok, row_pos, S);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int launch_beam_prompt_init(int* src_a, int* src_b, int slots, int nb, int R, int T, const int* pad, int* beam_pad, hipStream_t st) {
+    hipLaunchKernelGGL(beam_prompt_init_kernel, dim3((R * (T + 1) + 255) / 256), dim3(256), 0, st, src_a, src_b, slots, nb, R, T, pad, beam_pad);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+int launch_beam_row_pos(const int* step, const int* beam_pad, int* row_pos, int R, hipStream_t st) {
+    hipLaunchKernelGGL(beam_row_pos_kernel, dim3((R + 255) / 256), dim3(256), 0, st, step, beam_pad, row_pos, R);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
+
 struct PromptCall {
     const long long* ids;
     const float* am;     // NULL unless the prompt is padded
@@ -145,17 +194,13 @@ struct PromptCall {
 int store_prompt_kv(rgrg_decoder* d, int l, const float* qkv, const void* arg) {
     const PromptCall& c = *static_cast<const PromptCall*>(arg);
     const int S = c.S, fmt = rgrg_decoder_kv_format_in_use(d, S * c.row_mul);
-    const size_t total = (size_t)S * d->H * 2 * c.T * (fmt == KV_F32 ? 16 : 8);
-    const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096)), blk(256);
     if (fmt == KV_F32) {
         float* kc = d->kv + (size_t)l * d->kv_layer_stride;
-        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, 0, c.row_mul);
-    } else {   // the 16-bit cache lives in the same allocation with the same element strides (enqueue_prefill)
-        u16* kc = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride;
-        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, d->stream, qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, d->f16(), c.row_mul);
+        return launch_prompt_kv_store(qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, c.row_mul, false, 0, d->stream);
     }
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    // the 16-bit cache lives in the same allocation with the same element strides (enqueue_prefill)
+    u16* kc = reinterpret_cast<u16*>(d->kv) + (size_t)l * d->kv_layer_stride;
+    return launch_prompt_kv_store(qkv, kc, kc + d->kv_kv_stride, S, d->H, c.T, d->T, c.row_mul, true, d->f16(), d->stream);
 }
 
 // The prompt pass of every prompted entry, between the image slot and the head: ids, step counter and position ids (and, with
@@ -165,15 +210,12 @@ int enqueue_prompt_pass(rgrg_decoder* d, const PromptCall& c, float* kmask) {
     const int S = c.S, T = c.T, R = S * c.row_mul, fmt = rgrg_decoder_kv_format_in_use(d, R);
     hipStream_t st = d->stream;
     int rc;
-    const int n = std::max(S * T, kmask ? S * d->T : 0);
-    hipLaunchKernelGGL(prompt_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c.ids, S, T, d->V, d->ids, d->max_len, d->step,
-                       c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, kmask, d->T);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_prompt_setup(c.ids, S, T, d->V, d->ids, d->max_len, d->step, c.am ? d->prompt_pad : (const int*)nullptr, d->prompt_pos, kmask,
+                                  d->T, st)))
+        return rc;
     if ((rc = tf_hidden_pass(d, c.ids, c.am, c.am ? d->prompt_pos : nullptr, c.am ? S * T : 1, S, T, store_prompt_kv, &c))) return rc;
     u16* xn16 = (fmt != KV_F32 && d->xn16) ? d->xn16 : nullptr;
-    hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, d->tf.xn, T, d->D, d->xn, xn16, d->f16(), c.row_mul);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    return launch_prompt_last_rows(d->tf.xn, T, d->D, d->xn, xn16, d->f16(), c.row_mul, R, st);
 }
 
 // the prologue of run_decode_loop: everything between the image slot and step T
@@ -191,10 +233,7 @@ int enqueue_prompt(rgrg_decoder* d, int S, const void* arg) {
 
 // in front of every greedy / sampling step behind a padded prompt
 int enqueue_prompt_step_rows(rgrg_decoder* d, int S) {
-    hipLaunchKernelGGL(prompt_step_rows_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, d->ids, d->max_len, d->step, d->prompt_pad,
-                       d->beam_tok, d->row_pos, S);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    return launch_prompt_step_rows(d->ids, d->max_len, d->step, d->prompt_pad, d->beam_tok, d->row_pos, S, d->stream);
 }
 
 // The mask scan of every prompted entry on d->stream, with ONE read-back: a mask the kernels cannot honour is refused before any
@@ -208,8 +247,7 @@ int prompt_mask_check(rgrg_decoder* d, const char* who, const float* attention_m
     if (attention_mask) {
         int* flags = d->next;   // a scratch word of the decoder
         RGRG_HIP(hipMemsetAsync(flags, 0, sizeof(int), d->stream));
-        hipLaunchKernelGGL(prompt_mask_scan_kernel, dim3((S + 255) / 256), dim3(256), 0, d->stream, attention_mask, S, T, d->prompt_pad, flags);
-        RGRG_LAUNCH_CHECK();
+        if ((rc = launch_prompt_mask_scan(attention_mask, S, T, d->prompt_pad, flags, d->stream))) return rc;
         RGRG_HIP(hipMemcpyAsync(d->h_done, flags, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     }
     if (attention_mask || extra_dst) RGRG_HIP(hipStreamSynchronize(d->stream));
@@ -295,17 +333,13 @@ int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, boo
     c.row_mul = nb;
     // (the id buffer rows the pass writes are not read: beam search keeps its histories on the host; the slot mask is per beam row)
     if ((rc = enqueue_prompt_pass(d, c, nullptr))) return rc;
-    hipLaunchKernelGGL(beam_prompt_init_kernel, dim3((R * (T + 1) + 255) / 256), dim3(256), 0, st, d->src_a, d->src_b, d->T, nb, R, T,
-                       c.am ? d->prompt_pad : (const int*)nullptr, d->beam_pad);
-    RGRG_LAUNCH_CHECK();
+    if ((rc = launch_beam_prompt_init(d->src_a, d->src_b, d->T, nb, R, T, c.am ? d->prompt_pad : (const int*)nullptr, d->beam_pad, st))) return rc;
     if (*padded && rgrg_decoder_kv_format_in_use(d, R) == KV_F32) return launch_beam_first_mask(d->beam_pad, R, d->T, d->key_mask, st);
     return RGRG_OK;
 }
 
 int enqueue_beam_row_pos(rgrg_decoder* d, int R) {
-    hipLaunchKernelGGL(beam_row_pos_kernel, dim3((R + 255) / 256), dim3(256), 0, d->stream, d->step, d->beam_pad, d->row_pos, R);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
+    return launch_beam_row_pos(d->step, d->beam_pad, d->row_pos, R, d->stream);
 }
 
 }  // namespace rgrg
@@ -379,4 +413,53 @@ extern "C" int rgrg_decoder_sample_prompted(rgrg_decoder* d, const float* feats,
         return rc;
     d->logits_stale_rows = 0;   // the head behind the prompt and every step wrote d->logits
     return RGRG_OK;
+}
+
+// Test hooks of the prompt kernels alone (tests/test_gpu_step_rows.py): the caller's device buffers, the given stream, the launchers
+// the prompt pass itself goes through.  Every argument is validated before anything is launched.
+extern "C" int rgrg_debug_prompt_mask_scan(const float* am, int S, int T, int* pad, int* flags, void* stream) {
+    RGRG_CHECK_ARG(am && pad && flags && S >= 1 && T >= 1);
+    return launch_prompt_mask_scan(am, S, T, pad, flags, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_prompt_setup(const int64_t* in, int S, int T, int V, int64_t* ids, int ld_ids, int* step, const int* pad,
+                                       int64_t* pos, float* kmask, int slots, void* stream) {
+    RGRG_CHECK_ARG(in && ids && step && S >= 1 && T >= 1 && V >= 1 && ld_ids >= T);
+    RGRG_CHECK_ARG(!pad || pos);             // positions are written whenever pad is given
+    RGRG_CHECK_ARG(!kmask || pad);           // the slot mask is made from pad[]
+    RGRG_CHECK_ARG(!kmask || slots >= T + 1);
+    return launch_prompt_setup(reinterpret_cast<const long long*>(in), S, T, V, reinterpret_cast<long long*>(ids), ld_ids, step, pad,
+                               reinterpret_cast<long long*>(pos), kmask, slots, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul,
+                                          int kv_bytes, int fp16, void* stream) {
+    RGRG_CHECK_ARG(qkv && kplane && vplane && S >= 1 && H >= 1 && T >= 1 && slots >= T + 1 && row_mul >= 1);
+    RGRG_CHECK_ARG(kv_bytes == 4 || kv_bytes == 2);   // the e4m3 cache takes no prompt
+    RGRG_CHECK_ARG(kv_bytes == 2 || !fp16);
+    return launch_prompt_kv_store(qkv, kplane, vplane, S, H, T, slots, row_mul, kv_bytes == 2, fp16 ? 1 : 0, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_prompt_last_rows(const float* xn_all, int T, int D, float* xn, uint16_t* xn16, int fp16, int R, int row_div,
+                                           void* stream) {
+    RGRG_CHECK_ARG(xn_all && xn && T >= 1 && D == 1024 && R >= 1 && row_div >= 1);
+    RGRG_CHECK_ARG(xn16 || !fp16);
+    return launch_prompt_last_rows(xn_all, T, D, xn, xn16, fp16 ? 1 : 0, row_div, R, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_prompt_step_rows(const int64_t* ids, int ld_ids, const int* step, const int* pad, int* tok, int* row_pos, int S,
+                                           void* stream) {
+    RGRG_CHECK_ARG(ids && step && pad && tok && row_pos && S >= 1 && ld_ids >= 1);
+    return launch_prompt_step_rows(reinterpret_cast<const long long*>(ids), ld_ids, step, pad, tok, row_pos, S, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_beam_prompt_init(int* src_a, int* src_b, int slots, int nb, int R, int T, const int* pad, int* beam_pad,
+                                           void* stream) {
+    RGRG_CHECK_ARG(src_a && src_b && beam_pad && nb >= 1 && R >= 1 && R % nb == 0 && T >= 1 && slots >= T + 1);
+    return launch_beam_prompt_init(src_a, src_b, slots, nb, R, T, pad, beam_pad, as_stream(stream));
+}
+
+extern "C" int rgrg_debug_beam_row_pos(const int* step, const int* beam_pad, int* row_pos, int R, void* stream) {
+    RGRG_CHECK_ARG(step && beam_pad && row_pos && R >= 1);
+    return launch_beam_row_pos(step, beam_pad, row_pos, R, as_stream(stream));
 }
