@@ -328,6 +328,40 @@ int rgrg_debug_roll_session_step_req(int* row_seq, int* row_len, int* row_tok, i
 int rgrg_debug_roll_sample_req(const float* logits, int64_t ld, int V, int R, const int* row_seq, const int* row_len, float temperature,
                                int top_k, float top_p, uint64_t seed, const void* req, int C, int* arg, float* lp, int ld_lp,
                                void* stream);
+/* ---- Prompts in a rolling session: a submit's sentences continue a prompt of P tokens (greedy_search's semantics with a mask of
+ * ones: no padding, ever; one submit has one P).
+ * open_prompt: rgrg_decoder_roll_open with max_prompt_length = MP.  0 is exactly rgrg_decoder_roll_open: no memory, the same step.
+ *   1 .. max_length - 1 (RGRG_EINVAL otherwise) allocates, at open, a token ring int32 [capacity][MP], a length ring [capacity], a prompt
+ *   K/V ring in the cache's element format for R rows with planes [layer][2][capacity][H][MP][64], and the work space of a
+ *   teacher-forced pass over 512 prompt rows (at least MP - 1); RGRG_EHIP with the ring's size when that does not fit.  The step of
+ *   such a session has one more launch, the prompt refill, and a graph of its own.
+ * submit_prompt: rgrg_decoder_roll_submit_req (same request arguments) with prompt_ids int64 [m][P] on the HOST, row i for feature row
+ *   i; the n hypotheses of a feature row share it.  Ids are any tokens 0 .. vocabulary - 1: an EOS or stop token inside the prompt
+ *   ends nothing.  1 <= P <= MP and P + 1 <= the sequence's max_length, which counts the prompt.  Enqueued in front of the
+ *   hand-out pass: the prompt's tokens and length into ring row (q / n) % capacity, rows 0 .. P - 2 of the prompt as teacher-forced
+ *   passes (at most 512 token rows each) that attend to the submit's ukv ring rows and leave their keys / values in slots 1 .. P - 1 of
+ *   the K/V ring row.  The output row starts with the P prompt tokens (log-probs 0).  A row that takes the sequence gets len = P,
+ *   tok = prompt[P - 1], pos = step = P - 1, and the prompt refill copies ring slots 1 .. P - 1 to its cache row next to slot 0; the
+ *   last prompt token runs through the row's ordinary decode step.  A prompted sequence cut before its first step has the length
+ *   word -P.  rgrg_decoder_roll_submit / _submit_req in such a session are P = 1, the BOS column.  Does not synchronise or allocate.
+ *   RGRG_EINVAL before anything is enqueued, the session intact: the refusals of submit_req; a session opened without
+ *   max_prompt_length; a rolling beam session; P out of range; an id outside the vocabulary. */
+int rgrg_decoder_roll_open_prompt(rgrg_decoder* d, int R, int capacity, int n, int max_length, int max_prompt_length, int sample,
+                                  float temperature, int top_k, float top_p, uint64_t seed, int use_graph, void* stream);
+int rgrg_decoder_roll_submit_prompt(rgrg_decoder* d, const float* feats, int m, const int64_t* prompt_ids, int P, int max_length,
+                                    float temperature, int top_k, float top_p, int has_seed, uint64_t seed, const int* stop_ids, int n_stop,
+                                    long long* first_out, void* stream);
+/* Test hook: rgrg_debug_roll_session_step_req with prompt rings on the device: ptok int32 [C / n][MP], plen int32 [C / n] (1 .. MP; MP <
+ * max_length, MP + 1 <= T_slots) and pkv [n_layer][2][C / n][H][MP][64] in the cache's element format (NULL together with kv).  The
+ * submit-init writes the prompt of feature row (q / n) % (C / n) into the id row of sequence q; a seating pass gives the row len = P,
+ * tok = prompt[P - 1], pos = step = P - 1 and is followed by the refill and the prompt refill (ring slots 1 .. P - 1 -> the row's cache
+ * slots 1 .. P - 1, every layer, plane and head; nothing else is written).  RGRG_EINVAL: a ring row the product would refuse (the rings
+ * are read back and checked first). */
+int rgrg_debug_roll_prompt_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                                int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before, int submit, int handout,
+                                int retire, int R, int max_length, const float* ukv, int ld_ukv, void* kv, size_t layer_stride,
+                                size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16, const void* req, const int* ptok,
+                                const int* plen, const void* pkv, int MP, void* stream);
 /* Rolling-batch beam search: rgrg_decoder_beam_search over the S regions of feats [S,1024] with the regions flowing through
  * G = min(R / num_beams, S) SLOTS of num_beams consecutive decoder rows (num_beams <= R <= max_seqs of the decoder; S is not bounded
  * by it; rows behind G * num_beams are not used, and the step plan, precision and cache format are those of a step of G * num_beams

@@ -72,6 +72,10 @@ SIGNATURES = {
     "rgrg_decoder_roll_submit": (_i, [_p, _p, _i, C.POINTER(C.c_longlong), _p]),
     "rgrg_decoder_roll_submit_req": (_i, [_p, _p, _i, _i, _f, _i, _f, _i, C.c_uint64, C.POINTER(_i), _i, C.POINTER(C.c_longlong), _p]),
     "rgrg_decoder_roll_cancel": (_i, [_p, C.c_longlong, _i]),
+    "rgrg_decoder_roll_open_prompt": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _i, _f, C.c_uint64, _i, _p]),
+    "rgrg_decoder_roll_submit_prompt": (_i, [_p, _p, _i, _p, _i, _i, _f, _i, _f, _i, C.c_uint64, C.POINTER(_i), _i, C.POINTER(C.c_longlong), _p]),
+    "rgrg_debug_roll_prompt_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, C.c_size_t,
+                                         C.c_size_t, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "rgrg_decoder_roll_advance": (_i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "rgrg_decoder_roll_collect": (_i, [_p, C.c_longlong, _i, _p, _p, C.POINTER(_i), _p]),
     "rgrg_decoder_roll_release": (_i, [_p, C.c_longlong]),

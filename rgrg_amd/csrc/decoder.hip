@@ -1391,7 +1391,7 @@ static int enqueue_step_fused(rgrg_decoder* d, const StepSpec& s, bool count) {
     h.Xf = cur; h.part = d->part; h.Y = d->logits; h.ldy = d->ld_logits; h.act = RGRG_ACT_NONE;
     if ((rc = direct_linear(d, d->lm_head, h, DX_COMBINE4, S, count, !logits))) return rc;
     if (logits) return RGRG_OK;
-    if (s.end == STEP_ROLL) return enqueue_roll_end(d, S, d->lm_head.NT);
+    if (s.end == STEP_ROLL) return enqueue_roll_end(d, S, d->lm_head.NT, s.roll_prompt);
     hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, d->lm_head.NT, d->ids,
                        d->max_len, d->finished, d->step, d->done_len, d->sync, S);
     RGRG_LAUNCH_CHECK();
@@ -1483,7 +1483,7 @@ static GemmLnFold cons_kv_cache(const rgrg_decoder* d, const GemmLnFold& cons, i
 // The end of a step: lm_head over the ln_f rows (d->xn, or xn16 where the step's GEMMs read 16-bit activations).  logits: d->logits
 // and nothing else (the sampler or a ranking follows); otherwise per-tile arg-max candidates, arg-max and the bookkeeping - of the
 // greedy loop, or (roll) of rolling-batch decoding, from the same candidates.
-static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigned short* xn16, bool roll = false) {
+static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigned short* xn16, bool roll = false, bool roll_prompt = false) {
     hipStream_t st = d->stream;
     int rc;
     if (!logits && xn16 && lm_head_cand_path(d, S)) {
@@ -1492,7 +1492,7 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigne
         ce.cand_val = d->cand_val; ce.cand_idx = d->cand_idx;
         if ((rc = linear(d, d->lm_head, d->xn, nullptr, nullptr, S, d->ld_logits, RGRG_ACT_NONE, count, xn16, nullptr, &ce))) return rc;
         if ((rc = trace_mark(d, 0, 1002))) return rc;
-        if (roll) return enqueue_roll_end(d, S, (d->lm_head.N + 255) / 256);
+        if (roll) return enqueue_roll_end(d, S, (d->lm_head.N + 255) / 256, roll_prompt);
         hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, (d->lm_head.N + 255) / 256, d->ids,
                            d->max_len, d->finished, d->step, d->done_len, d->sync, S);
         RGRG_LAUNCH_CHECK();
@@ -1504,7 +1504,7 @@ static int enqueue_head(rgrg_decoder* d, int S, bool count, bool logits, unsigne
     hipLaunchKernelGGL(logits_candidates_kernel, dim3(4, S), dim3(256), 0, st, d->logits, d->ld_logits, d->V,
                        cand_nt, d->cand_val, d->cand_idx);
     RGRG_LAUNCH_CHECK();
-    if (roll) return enqueue_roll_end(d, S, cand_nt);
+    if (roll) return enqueue_roll_end(d, S, cand_nt, roll_prompt);
     hipLaunchKernelGGL(argmax_update_kernel, dim3(S), dim3(256), 0, st, d->cand_val, d->cand_idx, cand_nt, d->ids,
                        d->max_len, d->finished, d->step, d->done_len, d->sync, S);
     RGRG_LAUNCH_CHECK();
@@ -1607,14 +1607,14 @@ static int enqueue_step_tiled(rgrg_decoder* d, const StepSpec& s, bool count) {
         return RGRG_OK;
     };
     if ((rc = run_row_ranges(d, S, step_chains(d, S, s.end == STEP_ARGMAX && !s.tok && !s.src, fold), run_rows))) return rc;
-    return enqueue_head(d, S, count, s.end != STEP_ARGMAX && s.end != STEP_ROLL, xn16, s.end == STEP_ROLL);
+    return enqueue_head(d, S, count, s.end != STEP_ARGMAX && s.end != STEP_ROLL, xn16, s.end == STEP_ROLL, s.roll_prompt);
 }
 // One decode step: the fused plan up to its row limit (128 token rows; 64 under autocast), the tiled plan above
 int enqueue_step(rgrg_decoder* d, const StepSpec& s, bool count) {
     const int rc = s.rows <= decode_row_limit(d) ? enqueue_step_fused(d, s, count) : enqueue_step_tiled(d, s, count);
     if (rc) return rc;
     if (s.end == STEP_SAMPLE) return enqueue_sampler(d, s.rows);
-    return s.end == STEP_ROLL_SAMPLE ? enqueue_roll_sample_end(d, s.rows) : RGRG_OK;
+    return s.end == STEP_ROLL_SAMPLE ? enqueue_roll_sample_end(d, s.rows, s.roll_prompt) : RGRG_OK;
 }
 
 StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad) {

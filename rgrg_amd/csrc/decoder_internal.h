@@ -142,9 +142,10 @@ struct StepSpec {
     const int* row_step = nullptr;     // [rows] every row at a step of its own: key count t + 2 and slot t + 1 per row; NULL: *d->step for all
     StepEnd end = STEP_ARGMAX;
     int nb = 0, G = 0;                 // STEP_BEAM (nb, G), STEP_BEAM_SAMPLE (nb)
+    bool roll_prompt = false;          // STEP_ROLL / STEP_ROLL_SAMPLE: the prompt refill behind the refill (a session with max_prompt_length > 0)
     bool operator==(const StepSpec& o) const {
         return rows == o.rows && tok == o.tok && src == o.src && row_pos == o.row_pos && kv_first == o.kv_first && key_mask == o.key_mask &&
-               row_step == o.row_step && end == o.end && nb == o.nb && G == o.G;
+               row_step == o.row_step && end == o.end && nb == o.nb && G == o.G && roll_prompt == o.roll_prompt;
     }
 };
 
@@ -164,6 +165,14 @@ struct RollCall {
     // The request ring of a rolling session: entry q % C holds what sequence q asked for.  NULL - the one-shot calls,
     // rolling beam search, the test hooks without a ring - is the call's max_length, EOS alone and the parameter block of the step.
     const RollReq* req;
+    // The prompt rings of a rolling session opened with max_prompt_length = MP > 0, one row per FEATURE row, row
+    // (q / n) % Cf like ukv: ptok [Cf][MP] the prompt's tokens, plen [Cf] its length P (1 = BOS alone, a submit without a prompt),
+    // pkv the prompt's keys / values in the cache's element format, planes [layer][2][Cf][H][MP][64] of which slots 1 .. P - 1 are
+    // written (the last prompt token runs through the row's decode step).  NULL / 0: no prompts.
+    const int* ptok;
+    const int* plen;
+    const void* pkv;
+    int MP;
 };
 
 // What one sequence of a rolling session asked for (include/rgrg_hip.h "Request ring" states the layout for the test hooks): 40 bytes,
@@ -381,6 +390,13 @@ struct rgrg_decoder {
         // the request ring [C] and what a submit without a request writes into it: the session's own parameters
         rgrg::RollReq* req = nullptr;
         rgrg::RollReq defaults{};
+        // the prompt rings (max_prompt_length = call.MP > 0 only): device ptok / plen / pkv as RollCall states them,
+        // h_ptok / h_plen their pinned sources (a ring row is rewritten only after its sequences have been released), pids the
+        // int64 [prompt_chunk] token rows of one teacher-forced pass, prompt_chunk the token rows the work space was reserved for
+        int *ptok = nullptr, *plen = nullptr, *h_ptok = nullptr, *h_plen = nullptr;
+        void* pkv = nullptr;
+        long long* pids = nullptr;
+        int prompt_chunk = 0;
     } sess;
     // The rolling beam session (decoder_beam_roll.hip): one per decoder, and never next to `sess`.  Regions are numbered
     // over the life of the session; `next` is the lowest one not yet seated (pending: next .. submitted - 1), hyps / finalized hold
@@ -486,9 +502,10 @@ int beam_write_best(const std::vector<BeamHyps>& hyps, int keep, int max_length,
 int enqueue_sampler(rgrg_decoder* d, int S);
 int sample_begin(rgrg_decoder* d, int S, float temperature, int top_k, float top_p, uint64_t seed, void* stream);
 // decoder_roll.hip: the end of a STEP_ROLL step - the arg-max of R rows over their NT candidates, retire, refill
-int enqueue_roll_end(rgrg_decoder* d, int R, int NT);
+// (prompt: StepSpec::roll_prompt - the prompt refill behind the refill)
+int enqueue_roll_end(rgrg_decoder* d, int R, int NT, bool prompt = false);
 // ... and of a STEP_ROLL_SAMPLE step: the rolling sampler over the R logits rows, retire, refill
-int enqueue_roll_sample_end(rgrg_decoder* d, int R);
+int enqueue_roll_sample_end(rgrg_decoder* d, int R, bool prompt = false);
 // ... and what rolling beam search (decoder_beam_roll.hip) shares with them: the work space for S feature rows, the refusals (R rows,
 // max_length, the e4m3 cache), feature_space_transformation_nn and the uk / uv GEMM of the S feature rows -> roll.ukv, and
 // roll_refill_kernel alone over a HOST-written refill list: n (row, feature row) pairs -> roll.list / roll.shared, then the launch
@@ -504,7 +521,17 @@ int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R);
 int launch_roll_sample(const float* logits, size_t ld, int R, int V, const void* prm_dev, const int* row_seq, const int* row_len,
                        const RollCall* call, int* arg, hipStream_t st);
 int tf_reserve(rgrg_decoder* d, size_t rows);
+// ... and the 16-bit copy of a GEMM input of `rows` token rows that a pass under autocast makes: reserved up front, the pass never waits
+int tf_reserve_a16(rgrg_decoder* d, size_t rows);
+// ukv (or NULL = d->ukv_out): the S image key / value rows [S][ld_ukv] the pass attends to in slot 0.
+// kv_only (the prompt passes of a rolling session, which want every layer's q | k | v and nothing else): the pass ends behind the
+// last layer's after_qkv - d->tf.xn is NOT the ln_f rows then - and its fp32 GEMMs take no split-K: every output element is one K
+// loop in a fixed order, whatever the row count.
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
-                   int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr);
+                   int (*after_qkv)(rgrg_decoder*, int layer, const float* qkv, const void* arg) = nullptr, const void* arg = nullptr,
+                   const float* ukv = nullptr, bool kv_only = false);
+// decoder_prompt.hip: q | k | v rows [S*T][3D] (fp32) of one layer -> slots 1 .. T of the planes [rows][H][slots][64] (prompt_kv_store_kernel)
+int launch_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul, bool kv16, int f16,
+                           hipStream_t st);
 
 }  // namespace rgrg

@@ -475,9 +475,7 @@ int tf_reserve(rgrg_decoder* d, size_t rows) {
 // bf16-weight GEMM of the teacher-forced / training passes on an fp32 activation matrix: X is rounded to bf16 ONCE into a
 // scratch buffer (the same round-to-nearest-even the register-staged kernel applied tile by tile, so the operands are
 // identical) and the product runs on the LDS-DMA kernel - at M = S x T token rows it reaches 2-3x the register-staged rate.
-static int bf16_linear_f32in(rgrg_decoder* d, const float* X, const void* Wb, const float* b, const float* R, float* Y, int M, int N,
-                             int K, int ldy, int act) {
-    const size_t need = (size_t)M * K * sizeof(unsigned short);
+static int a16_reserve(rgrg_decoder* d, size_t need) {
     if (need > d->tr.a16_bytes) {
         RGRG_HIP(hipStreamSynchronize(d->stream));  // the old buffer may still be read by a queued GEMM
         if (d->tr.a16_scratch) (void)hipFree(d->tr.a16_scratch);
@@ -485,19 +483,28 @@ static int bf16_linear_f32in(rgrg_decoder* d, const float* X, const void* Wb, co
         RGRG_HIP(hipMalloc(&d->tr.a16_scratch, need));
         d->tr.a16_bytes = need;
     }
-    int rc = convert_f32_to_bf16(X, d->tr.a16_scratch, (size_t)M * K, d->stream, d->f16());
+    return RGRG_OK;
+}
+int tf_reserve_a16(rgrg_decoder* d, size_t rows) { return a16_reserve(d, rows * 4 * (size_t)d->D * sizeof(unsigned short)); }   // (c_fc's output is the widest input)
+
+static int bf16_linear_f32in(rgrg_decoder* d, const float* X, const void* Wb, const float* b, const float* R, float* Y, int M, int N,
+                             int K, int ldy, int act) {
+    int rc = a16_reserve(d, (size_t)M * K * sizeof(unsigned short));
+    if (rc) return rc;
+    rc = convert_f32_to_bf16(X, d->tr.a16_scratch, (size_t)M * K, d->stream, d->f16());
     if (rc) return rc;
     return launch_gemm_bf16w_ex(nullptr, d->tr.a16_scratch, Wb, b, R, Y, nullptr, M, N, K, ldy, act, d->stream, d->f16());
 }
 
-static int tf_linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act) {
+static int tf_linear(rgrg_decoder* d, const Lin& l, const float* X, const float* R, float* Y, int M, int ldy, int act, bool no_splitk = false) {
     if (d->bf16_gemms && l.wb && l.K % 256 == 0 && M > skinny_max_rows())
         return bf16_linear_f32in(d, X, l.wb, l.b, R, Y, M, l.N, l.K, ldy, act);
-    return launch_gemm_dense(X, l.w, l.b, R, Y, M, l.N, l.K, ldy, act, d->tf.ws, d->tf.ws_floats, d->stream);
+    return launch_gemm_dense(X, l.w, l.b, R, Y, M, l.N, l.K, ldy, act, d->tf.ws, no_splitk ? 0 : d->tf.ws_floats, d->stream);
 }
 int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention_mask, const long long* pos, int pos_rows, int S, int T,
-                   int (*after_qkv)(rgrg_decoder*, int, const float*, const void*), const void* arg) {
+                   int (*after_qkv)(rgrg_decoder*, int, const float*, const void*), const void* arg, const float* ukv, bool kv_only) {
     const int D = d->D, M = S * T;
+    if (!ukv) ukv = d->ukv_out;
     hipStream_t st = d->stream;
     int rc;
     if ((rc = launch_embed_seq_ln(d->wte, ids, T, d->layers[0].ln1_g, d->layers[0].ln1_b, d->tf.x, d->tf.xn, D, d->V, d->id_error, pos,
@@ -507,15 +514,16 @@ int tf_hidden_pass(rgrg_decoder* d, const long long* ids, const float* attention
         const LayerW& w = d->layers[l];
         const float* ng = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_g : d->lnf_g;
         const float* nb = (l + 1 < d->n_layer) ? d->layers[l + 1].ln1_b : d->lnf_b;
-        if ((rc = tf_linear(d, w.c_attn, d->tf.xn, nullptr, d->tf.qkv, M, 3 * D, RGRG_ACT_NONE))) return rc;
+        if ((rc = tf_linear(d, w.c_attn, d->tf.xn, nullptr, d->tf.qkv, M, 3 * D, RGRG_ACT_NONE, kv_only))) return rc;
         if (after_qkv && (rc = after_qkv(d, l, d->tf.qkv, arg))) return rc;
-        if ((rc = launch_attn_prefill(d->tf.qkv, d->ukv_out, d->ld_ukv, l * 2 * D, attention_mask, d->tf.att, S, d->H, T, nullptr,
+        if (kv_only && l + 1 == d->n_layer) return RGRG_OK;   // nothing reads what the last layer does with its q | k | v
+        if ((rc = launch_attn_prefill(d->tf.qkv, ukv, d->ld_ukv, l * 2 * D, attention_mask, d->tf.att, S, d->H, T, nullptr,
                                       DropoutParams{0ull, 0u, 0.f}, st)))
             return rc;
-        if ((rc = tf_linear(d, w.attn_proj, d->tf.att, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
+        if ((rc = tf_linear(d, w.attn_proj, d->tf.att, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE, kv_only))) return rc;
         if ((rc = launch_ln_rows(d->tf.x, w.ln2_g, w.ln2_b, d->tf.xn, D, nullptr, 0, M, st))) return rc;
-        if ((rc = tf_linear(d, w.c_fc, d->tf.xn, nullptr, d->tf.ff, M, 4 * D, RGRG_ACT_GELU_NEW))) return rc;
-        if ((rc = tf_linear(d, w.mlp_proj, d->tf.ff, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE))) return rc;
+        if ((rc = tf_linear(d, w.c_fc, d->tf.xn, nullptr, d->tf.ff, M, 4 * D, RGRG_ACT_GELU_NEW, kv_only))) return rc;
+        if ((rc = tf_linear(d, w.mlp_proj, d->tf.ff, d->tf.x, d->tf.x, M, D, RGRG_ACT_NONE, kv_only))) return rc;
         if ((rc = launch_ln_rows(d->tf.x, ng, nb, d->tf.xn, D, nullptr, 0, M, st))) return rc;
     }
     return RGRG_OK;

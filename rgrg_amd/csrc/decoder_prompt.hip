@@ -148,20 +148,6 @@ int launch_prompt_setup(const long long* in, int S, int T, int V, long long* ids
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
 }
-// kv16: the planes are 16 bit in the type f16; at most 4096 workgroups, the kernel strides
-int launch_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul, bool kv16, int f16,
-                           hipStream_t st) {
-    const size_t total = (size_t)S * H * 2 * T * (kv16 ? 8 : 16);
-    const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096)), blk(256);
-    if (!kv16)
-        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, st, qkv, static_cast<float*>(kplane), static_cast<float*>(vplane), S, H, T,
-                           slots, 0, row_mul);
-    else
-        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, st, qkv, static_cast<u16*>(kplane), static_cast<u16*>(vplane), S, H, T,
-                           slots, f16, row_mul);
-    RGRG_LAUNCH_CHECK();
-    return RGRG_OK;
-}
 int launch_prompt_last_rows(const float* xn_all, int T, int D, float* xn, u16* xn16, int f16, int row_div, int R, hipStream_t st) {
     hipLaunchKernelGGL(prompt_last_rows_kernel, dim3(R), dim3(256), 0, st, xn_all, T, D, xn, xn16, f16, row_div);
     RGRG_LAUNCH_CHECK();
@@ -318,6 +304,21 @@ int prompted_decode_loop(rgrg_decoder* d, const char* who, const float* feats, c
 }
 
 }  // namespace
+
+// (declared in decoder_internal.h: the rolling session's prompt pass writes its ring through it)  kv16: the planes are 16 bit in the type f16; at most 4096 workgroups, the kernel strides
+int launch_prompt_kv_store(const float* qkv, void* kplane, void* vplane, int S, int H, int T, int slots, int row_mul, bool kv16, int f16,
+                           hipStream_t st) {
+    const size_t total = (size_t)S * H * 2 * T * (kv16 ? 8 : 16);
+    const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096)), blk(256);
+    if (!kv16)
+        hipLaunchKernelGGL(prompt_kv_store_kernel<float>, grid, blk, 0, st, qkv, static_cast<float*>(kplane), static_cast<float*>(vplane), S, H, T,
+                           slots, 0, row_mul);
+    else
+        hipLaunchKernelGGL(prompt_kv_store_kernel<u16>, grid, blk, 0, st, qkv, static_cast<u16*>(kplane), static_cast<u16*>(vplane), S, H, T,
+                           slots, f16, row_mul);
+    RGRG_LAUNCH_CHECK();
+    return RGRG_OK;
+}
 
 int enqueue_beam_prompt(rgrg_decoder* d, const BeamPrompt& p, int S, int nb, bool* padded, std::vector<long long>* host_ids) {
     const int T = p.T, R = S * nb;

@@ -8,6 +8,7 @@
 //   roll_retire_kernel   ONE workgroup: append, retire, hand pending sequences to the free rows in ascending row order (a prefix
 //                        scan, no atomics: which row gets which sequence is a function of the tokens alone)
 //   roll_refill_kernel   the image key / value of every sequence handed out -> slot 0 of its row's cache, all layers
+//   (a session with prompts, DESIGN.md 7.19, adds roll_prompt_refill_kernel: the prompt's keys / values from a ring -> slots 1 .. P - 1)
 // What changes from call to call (output buffers, sequence count, max_length) is read from a device block, so one captured graph
 // per (R, plan) serves every call.
 //
@@ -25,6 +26,10 @@ struct RollRows {
     int *seq, *len, *tok, *pos, *step, *list, *shared;
 };
 constexpr int ROLL_NEXT = 0, ROLL_UNFINISHED = 1, ROLL_REFILLS = 2, ROLL_STEPS = 3;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// a length word of the prompt ring, kept inside 1 .. MP whatever the ring holds (the host has checked it: no kernel indexes by trust)
+__device__ __forceinline__ int roll_prompt_len(int P, int MP) { return min(max(P, 1), MP); }
 
 __global__ __launch_bounds__(256) void roll_argmax_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx, int NT,
                                                           int* __restrict__ arg) {
@@ -60,7 +65,8 @@ __global__ __launch_bounds__(256) void roll_begin_kernel(const RollCall c, RollC
 //   an ACTIVE row (seq >= 0) appends arg[r] at ids[seq][len]; on EOS, or when that was the max_length-th token, the sequence's
 //   length is recorded and the row is free; otherwise the token, len - 1 as position and step are the row's next input.
 //   FREE rows - just retired, or idle - take the pending sequences next, next + 1, ... in ascending row order as long as there
-//   are any: BOS, position 0, step 0, and (row, sequence) goes to the refill list.  A free row without a sequence is idle: it
+//   are any: BOS, position 0, step 0 - behind a prompt of P tokens (call->plen): its last token, position and step P - 1, length P -,
+//   and (row, sequence) goes to the refill list.  A free row without a sequence is idle: it
 //   keeps the BOS state, runs along and writes nothing.
 // `next` advances by the sequences handed out, not by the free rows.  Sequence q writes ring row q % C of the output.
 // handout_only (the first hand-out of a call, a submit of a session): a row that holds a sequence is not touched - no append, no
@@ -127,9 +133,17 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
             const int k = base_rank + before + in_wave;
             const int seq = next0 + k;
             const bool given = seq < c.S;
+            // with prompt rings the sequence starts behind its prompt of P tokens: the last prompt token is the row's
+            // next input, at position and step P - 1 (without rings: P = 1 and BOS)
+            int P = 1, tok = BOS_ID;
+            if (given && c.plen) {
+                const int f = seq / c.n % c.Cf;
+                P = roll_prompt_len(c.plen[f], c.MP);
+                tok = c.ptok[(size_t)f * c.MP + P - 1];
+            }
             st.seq[r] = given ? seq : -1;
-            st.len[r] = given ? 1 : 0;
-            st.tok[r] = BOS_ID; st.pos[r] = 0; st.step[r] = 0;
+            st.len[r] = given ? P : 0;
+            st.tok[r] = tok; st.pos[r] = P - 1; st.step[r] = P - 1;
             if (given) { st.list[2 * k] = r; st.list[2 * k + 1] = seq; }
         }
         base_rank += pass_free;
@@ -152,6 +166,7 @@ __global__ __launch_bounds__(256) void roll_retire_kernel(const RollRows st, con
 // kv_slot0_kernel's rounding for the cache format (16 bit: to16_rt; fp32: the value).  Grid (layers * 2, ROLL_REFILL_ROWS): workgroup
 // (x, y) copies the D values of plane x for list entries y, y + gridDim.y, ...; a step without refills costs the empty launch.
 constexpr int ROLL_REFILL_ROWS = 32;
+constexpr int ROLL_PROMPT_CHUNK = 512;   // token rows of one teacher-forced pass over the prompts of a submit (the work space a session reserves)
 template <typename KV>
 __global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict__ list, const int* __restrict__ shared,
                                                           const RollCall* __restrict__ call, KV* __restrict__ kv_all, size_t layer_stride,
@@ -172,10 +187,46 @@ __global__ __launch_bounds__(256) void roll_refill_kernel(const int* __restrict_
     }
 }
 
+// The prompt's keys / values of every sequence handed out in this step (a session with prompt rings): slots 1 .. P - 1
+// of ring row (sequence / n) % Cf of call->pkv -> the same slots of its row's cache, every layer.  Ring and cache hold the same element
+// format, so these are bytes: per (row, head) the (P - 1) * 64 elements are contiguous on both sides, a lane moves 16 bytes
+// (prompt_kv_store_kernel's piece), consecutive lanes consecutive pieces.  Grid as roll_refill_kernel: workgroup (x, y) serves plane x
+// of list entries y, y + gridDim.y, ...; a prompt of one token (a submit without a prompt) has nothing to copy.
+template <typename KV>
+__global__ __launch_bounds__(256) void roll_prompt_refill_kernel(const int* __restrict__ list, const int* __restrict__ shared,
+                                                                 const RollCall* __restrict__ call, KV* __restrict__ kv_all, size_t layer_stride,
+                                                                 size_t kv_stride, int H, int T) {
+    constexpr int PER = 16 / sizeof(KV);      // elements per lane
+    constexpr int LANES = 64 / PER;           // lanes per slot of a head
+    const int n = shared[ROLL_REFILLS];
+    const int l = blockIdx.x >> 1, kv = blockIdx.x & 1;
+    const int per_row = call->n, Cf = call->Cf, MP = call->MP;
+    const int* plen = call->plen;
+    const KV* ring = static_cast<const KV*>(call->pkv) + ((size_t)l * 2 + kv) * Cf * H * MP * 64;
+    KV* plane = kv_all + (size_t)l * layer_stride + (size_t)kv * kv_stride;
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const int r = list[2 * k], f = list[2 * k + 1] / per_row % Cf;
+        const int per_head = (roll_prompt_len(plen[f], MP) - 1) * LANES;   // 16-byte pieces of one head
+        for (int i = threadIdx.x; i < H * per_head; i += 256) {
+            const int hd = i / per_head, j = i - hd * per_head;
+            const KV* src = ring + (((size_t)f * H + hd) * MP + 1) * 64 + (size_t)j * PER;
+            KV* dst = plane + (((size_t)r * H + hd) * T + 1) * 64 + (size_t)j * PER;
+            *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+        }
+    }
+}
+
+// One thread per token of the M x T prompt rows of a teacher-forced pass: ptok rows (pitch MP) -> ids [M][T] int64
+__global__ __launch_bounds__(256) void roll_prompt_ids_kernel(const int* __restrict__ ptok, int MP, int T, int M, long long* __restrict__ ids) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < M * T) ids[i] = ptok[(size_t)(i / T) * MP + (i % T)];
+}
+
 namespace {
 
+// prompt: the call block holds prompt rings - roll_prompt_refill_kernel behind the refill
 int launch_retire_refill(const RollRows& st, const int* arg, const RollCall* call, int R, void* kv, size_t layer_stride, size_t kv_stride,
-                         int H, int T, int n_layer, KvFormat fmt, int f16, hipStream_t s, int handout_only = 0) {
+                         int H, int T, int n_layer, KvFormat fmt, int f16, hipStream_t s, int handout_only = 0, bool prompt = false) {
     hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, s, st, arg, call, R, handout_only);
     RGRG_LAUNCH_CHECK();
     const dim3 grid(n_layer * 2, std::min(R, ROLL_REFILL_ROWS));
@@ -185,6 +236,14 @@ int launch_retire_refill(const RollRows& st, const int* arg, const RollCall* cal
     else
         hipLaunchKernelGGL(roll_refill_kernel<unsigned short>, grid, dim3(256), 0, s, st.list, st.shared, call,
                            static_cast<unsigned short*>(kv), layer_stride, kv_stride, H, T, f16);
+    RGRG_LAUNCH_CHECK();
+    if (!prompt) return RGRG_OK;
+    if (fmt == KV_F32)
+        hipLaunchKernelGGL(roll_prompt_refill_kernel<float>, grid, dim3(256), 0, s, st.list, st.shared, call, static_cast<float*>(kv),
+                           layer_stride, kv_stride, H, T);
+    else
+        hipLaunchKernelGGL(roll_prompt_refill_kernel<unsigned short>, grid, dim3(256), 0, s, st.list, st.shared, call,
+                           static_cast<unsigned short*>(kv), layer_stride, kv_stride, H, T);
     RGRG_LAUNCH_CHECK();
     return RGRG_OK;
 }
@@ -255,22 +314,22 @@ int enqueue_roll_refill_list(rgrg_decoder* d, const int* pairs, int n, int R) {
     return RGRG_OK;
 }
 
-static int roll_retire_refill(rgrg_decoder* d, int R, int handout_only = 0) {
+static int roll_retire_refill(rgrg_decoder* d, int R, int handout_only = 0, bool prompt = false) {
     const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
     return launch_retire_refill(roll_rows(d), d->roll.arg, static_cast<const RollCall*>(d->roll.call), R, d->kv, d->kv_layer_stride,
-                                d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream, handout_only);
+                                d->kv_kv_stride, d->H, d->T, d->n_layer, fmt, d->f16(), d->stream, handout_only, prompt);
 }
 
-int enqueue_roll_end(rgrg_decoder* d, int R, int NT) {
+int enqueue_roll_end(rgrg_decoder* d, int R, int NT, bool prompt) {
     hipLaunchKernelGGL(roll_argmax_kernel, dim3(R), dim3(256), 0, d->stream, d->cand_val, d->cand_idx, NT, d->roll.arg);
     RGRG_LAUNCH_CHECK();
-    return roll_retire_refill(d, R);
+    return roll_retire_refill(d, R, 0, prompt);
 }
 
-int enqueue_roll_sample_end(rgrg_decoder* d, int R) {
+int enqueue_roll_sample_end(rgrg_decoder* d, int R, bool prompt) {
     const int rc = launch_roll_sample(d->logits, (size_t)d->ld_logits, R, d->V, d->sample_prm, d->roll.seq, d->roll.len,
                                       static_cast<const RollCall*>(d->roll.call), d->roll.arg, d->stream);
-    return rc ? rc : roll_retire_refill(d, R);
+    return rc ? rc : roll_retire_refill(d, R, 0, prompt);
 }
 
 namespace {
@@ -422,15 +481,21 @@ extern "C" int rgrg_debug_roll_step(int* row_seq, int* row_len, int* row_tok, in
 namespace rgrg {
 
 // A submit of `count` sequences q0 .. q0 + count - 1 (c: the host's block, S = q0 still): their ring rows in the state
-// roll_begin_kernel gives a sequence that never ran - BOS then PAD, log-probs 0, len 0 - and nothing else; then S and the
-// unfinished word grow by count.  The kernels behind it in the stream see the new S.
+// roll_begin_kernel gives a sequence that never ran - BOS then PAD (with prompt rings, c.plen: the P prompt tokens of its feature
+// row's ring row, then PAD), log-probs 0, len 0 - and nothing else; then S and the unfinished word grow by count.  The kernels behind it in the stream see the new S.
 // ring (or NULL: no request ring, or a test hook whose caller has written it): entry q % C of every new sequence becomes `req`.
 __global__ __launch_bounds__(256) void roll_submit_kernel(const RollCall c, RollCall* __restrict__ call, int* __restrict__ shared, int q0,
                                                           int count, RollReq* __restrict__ ring, const RollReq req) {
     const size_t total = (size_t)count * c.max_length;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t o = (size_t)((q0 + (int)(i / c.max_length)) % c.C) * c.ld + (i % c.max_length);
-        c.ids[o] = (i % c.max_length) == 0 ? BOS_ID : PAD_ID;
+        const int q = q0 + (int)(i / c.max_length), col = (int)(i % c.max_length);
+        const size_t o = (size_t)(q % c.C) * c.ld + col;
+        long long tok = col == 0 ? BOS_ID : PAD_ID;
+        if (c.plen) {
+            const int f = q / c.n % c.Cf;
+            if (col < roll_prompt_len(c.plen[f], c.MP)) tok = c.ptok[(size_t)f * c.MP + col];
+        }
+        c.ids[o] = tok;
         if (c.lp) c.lp[o] = 0.f;
     }
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x) {
@@ -463,6 +528,12 @@ void roll_session_free(rgrg_decoder* d) {
     if (s.lp) (void)hipFree(s.lp);
     if (s.len) (void)hipFree(s.len);
     if (s.req) (void)hipFree(s.req);
+    if (s.ptok) (void)hipFree(s.ptok);
+    if (s.plen) (void)hipFree(s.plen);
+    if (s.pkv) (void)hipFree(s.pkv);
+    if (s.pids) (void)hipFree(s.pids);
+    if (s.h_ptok) (void)hipHostFree(s.h_ptok);
+    if (s.h_plen) (void)hipHostFree(s.h_plen);
     if (s.h_len) (void)hipHostFree(s.h_len);
     s = rgrg_decoder::RollSession{};
 }
@@ -479,10 +550,46 @@ static int roll_session_live(rgrg_decoder* d, const char* who) {
 
 }  // namespace rgrg
 
+// The prompt rings of a session that is being opened (s.call is not set yet) and the work space of its prompt passes: everything a
+// submit needs, so that a submit allocates nothing.  On failure the caller frees the session.
+static int roll_prompt_reserve(rgrg_decoder* d, const char* who, int R, int Cf, int MP) {
+    rgrg_decoder::RollSession& s = d->sess;
+    const KvFormat fmt = (KvFormat)rgrg_decoder_kv_format_in_use(d, R);
+    const size_t kv_bytes = (size_t)d->n_layer * 2 * Cf * d->H * MP * 64 * (fmt == KV_F32 ? 4 : 2);
+    s.prompt_chunk = MP > 1 ? std::max(MP - 1, ROLL_PROMPT_CHUNK) : 0;
+    if (hipMalloc(&s.pkv, kv_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: no memory for the prompt K/V ring: %d feature rows x %d prompt slots x %d layers need %.1f MiB (a smaller capacity or "
+                  "max_prompt_length fits)", who, Cf, MP, d->n_layer, (double)kv_bytes / (1024.0 * 1024.0));
+        return RGRG_EHIP;
+    }
+    const size_t tok_bytes = (size_t)Cf * MP * sizeof(int);
+    if (hipMalloc((void**)&s.ptok, tok_bytes) != hipSuccess || hipMalloc((void**)&s.plen, (size_t)Cf * sizeof(int)) != hipSuccess ||
+        hipHostMalloc((void**)&s.h_ptok, tok_bytes) != hipSuccess || hipHostMalloc((void**)&s.h_plen, (size_t)Cf * sizeof(int)) != hipSuccess ||
+        (s.prompt_chunk && hipMalloc((void**)&s.pids, (size_t)s.prompt_chunk * sizeof(long long)) != hipSuccess)) {
+        (void)hipGetLastError();
+        set_error("%s: no memory for the prompt token rings: %d feature rows x %d tokens need %.1f MiB on the device and as much pinned on the "
+                  "host (the K/V ring of %.1f MiB is allocated)", who, Cf, MP, (double)tok_bytes / (1024.0 * 1024.0), (double)kv_bytes / (1024.0 * 1024.0));
+        return RGRG_EHIP;
+    }
+    if (s.prompt_chunk && (tf_reserve(d, (size_t)s.prompt_chunk) || (d->bf16_gemms && tf_reserve_a16(d, (size_t)s.prompt_chunk)))) {
+        (void)hipGetLastError();
+        set_error("%s: no memory for the work space of a prompt pass over %d token rows (about %.0f MiB behind the K/V ring of %.1f MiB)", who,
+                  s.prompt_chunk, (double)s.prompt_chunk * (14.0 * d->D + d->V) * 4.0 / (1024.0 * 1024.0), (double)kv_bytes / (1024.0 * 1024.0));
+        return RGRG_EHIP;
+    }
+    return RGRG_OK;
+}
+
 extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int n, int max_length, int sample, float temperature, int top_k,
                                       float top_p, uint64_t seed, int use_graph, void* stream) {
+    return rgrg_decoder_roll_open_prompt(d, R, capacity, n, max_length, 0, sample, temperature, top_k, top_p, seed, use_graph, stream);
+}
+
+extern "C" int rgrg_decoder_roll_open_prompt(rgrg_decoder* d, int R, int capacity, int n, int max_length, int max_prompt_length, int sample,
+                                             float temperature, int top_k, float top_p, uint64_t seed, int use_graph, void* stream) {
     RGRG_CHECK_ARG(d && n > 0);
-    const char* who = "rgrg_decoder_roll_open";
+    const char* who = max_prompt_length ? "rgrg_decoder_roll_open_prompt" : "rgrg_decoder_roll_open";
     if (d->sess.open) { set_error("%s: a rolling session is already open on this decoder (one per decoder: close it first)", who); return RGRG_EINVAL; }
     if (d->bsess.open) { set_error("%s: a rolling beam session is already open on this decoder (one per decoder: close it first)", who); return RGRG_EINVAL; }
     if (capacity < 1 || (long long)capacity * n >= 0x7fffffffLL / 1024) {
@@ -491,6 +598,12 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
     }
     int rc;
     if ((rc = roll_check(d, who, R, max_length))) return rc;
+    const int MP = max_prompt_length;
+    if (MP < 0 || MP >= max_length) {
+        set_error("%s: max_prompt_length %d, 0 (no prompts) .. %d are possible (max_length %d counts the prompt and one token is always generated)",
+                  who, MP, max_length - 1, max_length);
+        return RGRG_EINVAL;
+    }
     if ((rc = roll_reserve(d, capacity))) return rc;
     if (sample && !d->sample_prm && (rc = dmalloc(d, &d->sample_prm, sample_params_bytes(), true))) return rc;
     rgrg_decoder::RollSession& s = d->sess;
@@ -503,11 +616,15 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
         return RGRG_EHIP;
     }
     std::fill(s.h_len, s.h_len + C, 0);
+    if (MP > 0 && (rc = roll_prompt_reserve(d, who, R, capacity, MP))) {
+        roll_session_free(d);
+        return rc;
+    }
     if ((rc = decode_begin(d, stream)) || (sample && (rc = enqueue_sample_params(d->sample_prm, temperature, top_k, top_p, seed, d->stream)))) {
         roll_session_free(d);
         return rc;
     }
-    s.call = RollCall{s.ids, s.len, d->roll.ukv, max_length, 0, max_length, d->ld_ukv, s.lp, n, (int)C, capacity, s.req};
+    s.call = RollCall{s.ids, s.len, d->roll.ukv, max_length, 0, max_length, d->ld_ukv, s.lp, n, (int)C, capacity, s.req, s.ptok, s.plen, s.pkv, MP};
     // what a submit without a request asks for: the session's limit and parameters, its numbering (q0 = 0), EOS alone
     s.defaults = RollReq{seed, sample ? 1.0f / temperature : 1.0f, sample ? top_k : 0, sample ? top_p : 1.0f, max_length, 0,
                          {ROLL_NO_STOP, ROLL_NO_STOP, ROLL_NO_STOP, ROLL_NO_STOP}, 0u};
@@ -520,8 +637,40 @@ extern "C" int rgrg_decoder_roll_open(rgrg_decoder* d, int R, int capacity, int 
     return RGRG_OK;
 }
 
-// submit with the request `req` for all m * n new sequences; q0 < 0 in it: the first new sequence (a request with a seed of its own)
-static int roll_submit(rgrg_decoder* d, const char* who, const float* feats, int m, RollReq req, long long* first_out, void* stream) {
+// The prompt of feature rows f0 .. f0 + M - 1 of the ring (no wrap inside; token and ukv ring rows are written): rows 0 .. P - 2 in
+// teacher-forced passes of up to prompt_chunk token rows, every layer's keys / values -> slots 1 .. P - 1 of the ring rows.  The
+// pass reads the ukv ring rows as its image keys / values and writes the work space of tf_reserve and the K/V ring - nothing the
+// captured step reads but the ring: not d->ukv_out, d->tf.pos, d->ids, d->step or the epoch.
+struct RingStore { int f0, M, P; };
+static int store_ring_kv(rgrg_decoder* d, int l, const float* qkv, const void* arg) {
+    const RingStore& a = *static_cast<const RingStore*>(arg);
+    const rgrg_decoder::RollSession& s = d->sess;
+    const bool kv16 = (KvFormat)rgrg_decoder_kv_format_in_use(d, s.R) != KV_F32;
+    const size_t plane = (size_t)s.call.Cf * d->H * s.call.MP * 64, row = (size_t)d->H * s.call.MP * 64, esz = kv16 ? 2 : 4;
+    char* k = static_cast<char*>(s.pkv) + (((size_t)l * 2) * plane + (size_t)a.f0 * row) * esz;
+    return launch_prompt_kv_store(qkv, k, k + plane * esz, a.M, d->H, a.P - 1, s.call.MP, 1, kv16, d->f16(), d->stream);
+}
+static int enqueue_roll_prompt_pass(rgrg_decoder* d, int f0, int M, int P) {
+    rgrg_decoder::RollSession& s = d->sess;
+    const int T = P - 1, per_pass = s.prompt_chunk / T;
+    int rc;
+    if ((rc = tf_reserve(d, (size_t)s.prompt_chunk))) return rc;   // (reserved at open: nothing happens unless the work space was dropped since)
+    for (int m0 = 0; m0 < M; m0 += per_pass) {
+        const RingStore a{f0 + m0, std::min(per_pass, M - m0), P};
+        hipLaunchKernelGGL(roll_prompt_ids_kernel, dim3((a.M * T + 255) / 256), dim3(256), 0, d->stream, s.ptok + (size_t)a.f0 * s.call.MP,
+                           s.call.MP, T, a.M, s.pids);
+        RGRG_LAUNCH_CHECK();
+        // kv_only: the pass ends behind the last layer's q | k | v, and in fp32 its result does not depend on the row count
+        if ((rc = tf_hidden_pass(d, s.pids, nullptr, nullptr, 1, a.M, T, store_ring_kv, &a, d->roll.ukv + (size_t)a.f0 * d->ld_ukv, true)))
+            return rc;
+    }
+    return RGRG_OK;
+}
+
+// submit with the request `req` for all m * n new sequences; q0 < 0 in it: the first new sequence (a request with a seed of its own).
+// prompt (or NULL): HOST int64 [m][P], checked by the caller; a session with prompt rings gives a submit without one P = 1, BOS.
+static int roll_submit(rgrg_decoder* d, const char* who, const float* feats, int m, RollReq req, long long* first_out, void* stream,
+                       const int64_t* prompt = nullptr, int P = 1) {
     int rc;
     rgrg_decoder::RollSession& s = d->sess;
     const int n = s.call.n, C = s.call.C, Cf = s.call.Cf;
@@ -541,6 +690,22 @@ static int roll_submit(rgrg_decoder* d, const char* who, const float* feats, int
     const int f0 = (int)((q0 / n) % Cf), head = std::min(m, Cf - f0);
     if ((rc = enqueue_roll_prefill(d, feats, head, (size_t)f0))) return rc;
     if (m > head && (rc = enqueue_roll_prefill(d, feats + (size_t)head * d->D, m - head, 0))) return rc;
+    // 1b. the prompts: token and length ring rows from their pinned sources (a ring row is free: its earlier sequences have been
+    // released, so the copies that read it are done), then the prompt passes behind the ukv rows they attend to
+    if (const int MP = s.call.MP) {
+        for (int i = 0; i < m; ++i) {
+            const int f = (f0 + i) % Cf;
+            s.h_plen[f] = P;
+            for (int j = 0; j < MP; ++j) s.h_ptok[(size_t)f * MP + j] = (prompt && j < P) ? (int)prompt[(size_t)i * P + j] : BOS_ID;
+        }
+        const int seg[2][2] = {{f0, head}, {0, m - head}};
+        for (const auto& g : seg) {
+            if (g[1] <= 0) continue;
+            RGRG_HIP(hipMemcpyAsync(s.ptok + (size_t)g[0] * MP, s.h_ptok + (size_t)g[0] * MP, (size_t)g[1] * MP * sizeof(int), hipMemcpyHostToDevice, d->stream));
+            RGRG_HIP(hipMemcpyAsync(s.plen + g[0], s.h_plen + g[0], (size_t)g[1] * sizeof(int), hipMemcpyHostToDevice, d->stream));
+            if (P > 1 && (rc = enqueue_roll_prompt_pass(d, g[0], g[1], P))) return rc;
+        }
+    }
     // 2. + 3. the new output rows, S and the unfinished word; 4. idle rows take what is pending, their slot 0 is filled
     if (req.q0 < 0) req.q0 = (int)q0;
     if ((rc = launch_roll_submit(s.call, static_cast<RollCall*>(d->roll.call), d->roll.shared, (int)q0, (int)count, d->stream, s.req, req)))
@@ -549,7 +714,7 @@ static int roll_submit(rgrg_decoder* d, const char* who, const float* feats, int
     s.call.S = (int)(q0 + count);
     s.unfinished += count;
     s.drained = false;
-    if ((rc = roll_retire_refill(d, s.R, 1))) return rc;
+    if ((rc = roll_retire_refill(d, s.R, 1, s.call.MP > 0))) return rc;
     if (first_out) *first_out = q0;
     return RGRG_OK;
 }
@@ -562,13 +727,9 @@ extern "C" int rgrg_decoder_roll_submit(rgrg_decoder* d, const float* feats, int
     return roll_submit(d, who, feats, m, d->sess.defaults, first_out, stream);
 }
 
-extern "C" int rgrg_decoder_roll_submit_req(rgrg_decoder* d, const float* feats, int m, int max_length, float temperature, int top_k,
-                                            float top_p, int has_seed, uint64_t seed, const int* stop_ids, int n_stop,
-                                            long long* first_out, void* stream) {
-    RGRG_CHECK_ARG(d && feats && m > 0 && (n_stop == 0 || stop_ids));
-    const char* who = "rgrg_decoder_roll_submit_req";
-    int rc;
-    if ((rc = roll_session_live(d, who))) return rc;
+// the request of rgrg_decoder_roll_submit_req / _submit_prompt -> *out, or the refusal (0 / -1 / NULL arguments: the session's values)
+static int roll_parse_req(rgrg_decoder* d, const char* who, int max_length, float temperature, int top_k, float top_p, int has_seed,
+                          uint64_t seed, const int* stop_ids, int n_stop, RollReq* out) {
     const rgrg_decoder::RollSession& s = d->sess;
     RollReq req = s.defaults;
     if (max_length != 0) {
@@ -604,7 +765,48 @@ extern "C" int rgrg_decoder_roll_submit_req(rgrg_decoder* d, const float* feats,
         }
         req.stop[i] = (unsigned short)stop_ids[i];
     }
+    *out = req;
+    return RGRG_OK;
+}
+
+extern "C" int rgrg_decoder_roll_submit_req(rgrg_decoder* d, const float* feats, int m, int max_length, float temperature, int top_k,
+                                            float top_p, int has_seed, uint64_t seed, const int* stop_ids, int n_stop,
+                                            long long* first_out, void* stream) {
+    RGRG_CHECK_ARG(d && feats && m > 0 && (n_stop == 0 || stop_ids));
+    const char* who = "rgrg_decoder_roll_submit_req";
+    int rc;
+    if ((rc = roll_session_live(d, who))) return rc;
+    RollReq req;
+    if ((rc = roll_parse_req(d, who, max_length, temperature, top_k, top_p, has_seed, seed, stop_ids, n_stop, &req))) return rc;
     return roll_submit(d, who, feats, m, req, first_out, stream);
+}
+
+extern "C" int rgrg_decoder_roll_submit_prompt(rgrg_decoder* d, const float* feats, int m, const int64_t* prompt_ids, int P, int max_length,
+                                               float temperature, int top_k, float top_p, int has_seed, uint64_t seed, const int* stop_ids,
+                                               int n_stop, long long* first_out, void* stream) {
+    RGRG_CHECK_ARG(d && feats && m > 0 && prompt_ids && (n_stop == 0 || stop_ids));
+    const char* who = "rgrg_decoder_roll_submit_prompt";
+    int rc;
+    if (d->bsess.open) { set_error("%s: a rolling beam session takes no prompts (its scheduler lives on the host)", who); return RGRG_EINVAL; }
+    if ((rc = roll_session_live(d, who))) return rc;
+    const rgrg_decoder::RollSession& s = d->sess;
+    if (s.call.MP == 0) {
+        set_error("%s: the session was opened without max_prompt_length: it holds no prompt rings", who);
+        return RGRG_EINVAL;
+    }
+    RollReq req;
+    if ((rc = roll_parse_req(d, who, max_length, temperature, top_k, top_p, has_seed, seed, stop_ids, n_stop, &req))) return rc;
+    if (P < 1 || P > s.call.MP || P + 1 > req.max_length) {
+        set_error("%s: a prompt of %d tokens, 1 .. %d are possible (max_prompt_length %d; max_length %d counts the prompt and one token is "
+                  "always generated)", who, P, std::min(s.call.MP, req.max_length - 1), s.call.MP, req.max_length);
+        return RGRG_EINVAL;
+    }
+    for (size_t i = 0; i < (size_t)m * P; ++i)
+        if (prompt_ids[i] < 0 || prompt_ids[i] >= d->V) {
+            set_error("%s: prompt token id %lld (row %zu, column %zu), 0 .. %d are possible", who, (long long)prompt_ids[i], i / P, i % P, d->V - 1);
+            return RGRG_EINVAL;
+        }
+    return roll_submit(d, who, feats, m, req, first_out, stream, prompt_ids, P);
 }
 
 extern "C" int rgrg_decoder_roll_cancel(rgrg_decoder* d, long long first, int count) {
@@ -637,6 +839,7 @@ extern "C" int rgrg_decoder_roll_advance(rgrg_decoder* d, int max_steps, int* la
     if (!s.drained && limit > 0) {
         StepSpec step;
         step.rows = R; step.tok = d->roll.tok; step.row_pos = d->roll.pos; step.row_step = d->roll.step; step.end = s.end;
+        step.roll_prompt = s.call.MP > 0;
         hipGraphExec_t exec = nullptr;
         if (s.use_graph && (rc = step_graph(d, step, [&] { return enqueue_step(d, step, true); }, &exec))) return rc;
         // polled as roll_run polls: every 16 steps, waiting for the copy queued 16 steps earlier
@@ -745,7 +948,8 @@ static int debug_roll_session_step(const char* who, int* row_seq, int* row_len, 
                                    const int* arg, int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before,
                                    int submit, int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv,
                                    void* kv, size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16,
-                                   int fp16, const RollReq* req, void* stream) {
+                                   int fp16, const RollReq* req, void* stream, const int* ptok = nullptr, const int* plen = nullptr,
+                                   const void* pkv = nullptr, int MP = 0) {
     RGRG_CHECK_ARG(row_seq && row_len && row_tok && row_pos && row_step && shared && arg && ids && lens);
     RGRG_CHECK_ARG(C > 0 && n > 0 && C % n == 0 && S_before >= 0 && submit >= 0 && submit % n == 0 && submit <= C &&
                    (long long)S_before + submit < 0x7fffffffLL / 1024);
@@ -758,13 +962,14 @@ static int debug_roll_session_step(const char* who, int* row_seq, int* row_len, 
     RollCall* dcall = nullptr;
     RGRG_HIP(hipMalloc((void**)&list, 2 * (size_t)R * sizeof(int)));
     if (hipMalloc((void**)&dcall, sizeof(RollCall)) != hipSuccess) { (void)hipFree(list); set_error("%s: hipMalloc failed", who); return RGRG_EHIP; }
-    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S_before, max_length, ld_ukv, lp, n, C, C / n, req};
+    const RollCall call{reinterpret_cast<long long*>(ids), lens, ukv, ld_ids, S_before, max_length, ld_ukv, lp, n, C, C / n, req, ptok, plen, pkv, MP};
     hipError_t e = hipMemcpyAsync(dcall, &call, sizeof(call), hipMemcpyHostToDevice, st);
     const RollRows rows{row_seq, row_len, row_tok, row_pos, row_step, list, shared};
     const KvFormat fmt = kv16 ? (fp16 ? KV_F16 : KV_BF16) : KV_F32;
     int rc = RGRG_OK;
     auto pass = [&](int handout_only) {
-        if (kv) return launch_retire_refill(rows, arg, dcall, R, kv, layer_stride, kv_stride, H, T_slots, n_layer, fmt, fp16 ? 1 : 0, st, handout_only);
+        if (kv) return launch_retire_refill(rows, arg, dcall, R, kv, layer_stride, kv_stride, H, T_slots, n_layer, fmt, fp16 ? 1 : 0, st, handout_only,
+                                            MP > 0);
         hipLaunchKernelGGL(roll_retire_kernel, dim3(1), dim3(256), 0, st, rows, arg, dcall, R, handout_only);
         RGRG_LAUNCH_CHECK();
         return (int)RGRG_OK;
@@ -877,4 +1082,34 @@ extern "C" int rgrg_debug_roll_sample_req(const float* logits, int64_t ld, int V
     if ((rc = debug_check_req_ring(who, req, C, 0, as_stream(stream)))) return rc;
     return debug_roll_sample(who, logits, ld, V, R, row_seq, row_len, temperature, top_k, top_p, seed, static_cast<const RollReq*>(req), C,
                              arg, lp, ld_lp, stream);
+}
+
+// Test hook: rgrg_debug_roll_session_step_req with prompt rings: ptok int32 [C / n][MP], plen int32 [C / n] - read back
+// and checked on the host before any kernel trusts them: 1 .. MP, below max_length, and tokens 0 .. 65535 -, pkv the K/V ring
+// [n_layer][2][C / n][H][MP][64] in the cache's element format (NULL together with kv).  The submit-init writes the prompts into the id
+// ring, a seating pass gives len = P, tok = prompt[P - 1], pos = step = P - 1 and copies ring slots 1 .. P - 1 behind slot 0.
+extern "C" int rgrg_debug_roll_prompt_step(int* row_seq, int* row_len, int* row_tok, int* row_pos, int* row_step, int* shared, const int* arg,
+                                           int64_t* ids, float* lp, int ld_ids, int* lens, int C, int n, int S_before, int submit,
+                                           int handout, int retire, int R, int max_length, const float* ukv, int ld_ukv, void* kv,
+                                           size_t layer_stride, size_t kv_stride, int H, int T_slots, int n_layer, int kv16, int fp16,
+                                           const void* req, const int* ptok, const int* plen, const void* pkv, int MP, void* stream) {
+    const char* who = "rgrg_debug_roll_prompt_step";
+    RGRG_CHECK_ARG(C > 0 && n > 0 && C % n == 0 && max_length >= 2 && ptok && plen && MP >= 1 && MP < max_length);
+    RGRG_CHECK_ARG((pkv == nullptr) == (kv == nullptr) && (!kv || MP + 1 <= T_slots));
+    int rc;
+    hipStream_t st = as_stream(stream);
+    if (req && (rc = debug_check_req_ring(who, req, C, max_length, st))) return rc;
+    const int Cf = C / n;
+    std::vector<int> h((size_t)Cf * (MP + 1));
+    RGRG_HIP(hipMemcpyAsync(h.data(), plen, (size_t)Cf * sizeof(int), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipMemcpyAsync(h.data() + Cf, ptok, (size_t)Cf * MP * sizeof(int), hipMemcpyDeviceToHost, st));
+    RGRG_HIP(hipStreamSynchronize(st));
+    for (int f = 0; f < Cf; ++f) {
+        bool ok = h[(size_t)f] >= 1 && h[(size_t)f] <= MP;
+        for (int j = 0; ok && j < h[(size_t)f]; ++j) ok = h[(size_t)Cf + (size_t)f * MP + j] >= 0 && h[(size_t)Cf + (size_t)f * MP + j] < 65536;
+        if (!ok) { set_error("%s: prompt ring row %d: a length of %d tokens (1 .. %d), or a token outside 0 .. 65535", who, f, h[(size_t)f], MP); return RGRG_EINVAL; }
+    }
+    return debug_roll_session_step(who, row_seq, row_len, row_tok, row_pos, row_step, shared, arg, ids, lp, ld_ids, lens, C, n, S_before,
+                                   submit, handout, retire, R, max_length, ukv, ld_ukv, kv, layer_stride, kv_stride, H, T_slots, n_layer,
+                                   kv16, fp16, static_cast<const RollReq*>(req), stream, ptok, plen, pkv, MP);
 }

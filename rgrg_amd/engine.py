@@ -835,7 +835,7 @@ class HipEngine:
         return ids, logprobs
 
     def open_rolling(self, max_length: int, rows: int, capacity: Optional[int] = None, *, sample: Optional[dict] = None,
-                     beam: Optional[dict] = None, use_graph: bool = True, bf16=False, kv_fp8: bool = False):
+                     beam: Optional[dict] = None, use_graph: bool = True, bf16=False, kv_fp8: bool = False, max_prompt_length: int = 0):
         """A rolling session (rgrg_decoder_roll_open) on ``rows`` decoder rows: feature rows are submitted at any
         time, steps advanced as far as the caller likes, finished sentences collected as they end -> ``RollingSession``.
         ``capacity``: the feature rows the session holds at a time (None: 4 * rows sequences); ``sample``: None = greedy, or
@@ -845,8 +845,11 @@ class HipEngine:
         submitted sentences can be cancelled (rgrg_decoder_roll_submit_req / _cancel).
         ``beam``: ``dict(num_beams, early_stopping, length_penalty, num_return_sequences)`` opens a ``RollingBeamSession``
         (rgrg_decoder_beam_roll_open, DESIGN.md 7.17) on ``rows // num_beams`` slots instead; ``capacity`` then counts regions (None:
-        4 * slots).  Not together with ``sample``."""
-        from .rolling_session import RollingBeamSession, RollingSession
+        4 * slots).  Not together with ``sample``.
+        ``max_prompt_length`` > 0 (rgrg_decoder_roll_open_prompt): submits may carry ``prompt_ids`` of up to that many
+        tokens; the prompt rings are allocated here (RgrgHipError naming the size when they do not fit).  0: the session without
+        prompts, nothing allocated, the same step.  Not in a beam session."""
+        from .rolling_session import RollingBeamSession, RollingSession, check_max_prompt_length
         _require_gpu(self.device)
         R, limit = int(rows), int(max_length)
         if beam and sample:
@@ -858,6 +861,7 @@ class HipEngine:
         cap = (4 * (R // nb) if beam else -(-4 * R // n)) if capacity is None else int(capacity)
         if limit < 2 or R < 1 or n < 1:
             raise ValueError(f"open_rolling: max_length {limit} (>= 2), rows {R} (>= 1) and {n} sequences per feature row (>= 1)")
+        mp = check_max_prompt_length(max_prompt_length, limit, beam=bool(beam))
         if cap < 1:
             raise ValueError(f"open_rolling: capacity has to be at least 1 feature row, but is {cap}")
         old = getattr(self, "_session", None)
@@ -879,11 +883,13 @@ class HipEngine:
             self._session = RollingBeamSession(self, dec, R, cap, limit, nb, keep)
             return self._session
         sp = sample or {}
-        _hip.check(self.lib.rgrg_decoder_roll_open(dec, R, cap, n, limit, 1 if sample else 0, float(sp.get("temperature", 1.0)),
-                                                   int(sp.get("top_k", 0)), float(sp.get("top_p", 1.0)),
-                                                   int(sp.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, 1 if use_graph else 0, self._s()),
-                   "rgrg_decoder_roll_open")
-        self._session = RollingSession(self, dec, R, cap, n, limit, bool(sample))
+        args = (1 if sample else 0, float(sp.get("temperature", 1.0)), int(sp.get("top_k", 0)), float(sp.get("top_p", 1.0)),
+                int(sp.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF, 1 if use_graph else 0, self._s())
+        if mp:
+            _hip.check(self.lib.rgrg_decoder_roll_open_prompt(dec, R, cap, n, limit, mp, *args), "rgrg_decoder_roll_open_prompt")
+        else:
+            _hip.check(self.lib.rgrg_decoder_roll_open(dec, R, cap, n, limit, *args), "rgrg_decoder_roll_open")
+        self._session = RollingSession(self, dec, R, cap, n, limit, bool(sample), max_prompt_length=mp)
         return self._session
 
     def greedy_decode_prompted(self, feats: Tensor, input_ids: Tensor, attention_mask: Optional[Tensor], max_length: Optional[int],

@@ -394,7 +394,8 @@ class LanguageModel(EngineOwner):
 
     def open_rolling(self, max_length: int, *, rows: int, capacity: Optional[int] = None, do_sample: bool = False,
                      temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1,
-                     seed: Optional[int] = None, num_beams: int = 1, early_stopping: bool = False, length_penalty: float = 1.0):
+                     seed: Optional[int] = None, num_beams: int = 1, early_stopping: bool = False, length_penalty: float = 1.0,
+                     max_prompt_length: int = 0):
         """``generate_rolling`` / ``sample_rolling`` (``do_sample``) over an OPEN list: a ``RollingSession`` on
         ``rows`` decoder rows.  ``submit(feats)`` -> the range of sentence numbers q (n = num_return_sequences per feature row, in
         submit order), at any time between steps; ``advance(steps=None)`` runs steps (None: until nothing is unfinished);
@@ -407,15 +408,22 @@ class LanguageModel(EngineOwner):
         What is given HERE holds for every submit that says nothing else: ``submit(feats, max_length=.., temperature=.., top_k=..,
         top_p=.., seed=.., stop_token_ids=..)`` decodes its sentences with parameters of their own and ``cancel(qs)`` cuts
         submitted sentences (not in a beam session).
+        ``max_prompt_length`` > 0 (not in a beam session, below ``max_length``): ``submit(feats, prompt_ids=..)``
+        continues prompts of up to that many tokens - int64 [m, P] or [P], one P per submit, no padding, ``max_length`` counting
+        the prompt - as ``greedy_search`` continues ``input_ids`` under a mask of ones; ragged prompts are separate submits.  The
+        rings that hold the prompts are allocated here (RgrgHipError naming their size when they do not fit).  0: no prompts,
+        nothing allocated, the session as it was.
         ``num_beams > 1``: ``beam_search_rolling`` over an open list -> a ``RollingBeamSession`` on
         ``rows // num_beams`` slots.  ``submit(feats)`` -> the range of REGION numbers, one per feature row; ``collect()`` ->
         ``(q, ids)`` with ids int64 [num_return_sequences, L_q], the rows ``generate(num_beams=..)`` gives the region.  ``capacity``
         counts regions (None: 4 * (rows // num_beams)).  Argument errors are those of ``beam_search_rolling``; ``do_sample``
         with beams raises ValueError (beam-sampling has no session)."""
+        from .rolling_session import check_max_prompt_length
         if num_beams != 1:
             if do_sample:
                 raise ValueError("do_sample has to be False with num_beams > 1: beam-sampling has no rolling session")
             check_rolling_beam_args(max_length, num_beams, rows, num_return_sequences)
+            check_max_prompt_length(max_prompt_length, max_length, beam=True)
             if rows is None:
                 raise ValueError("rows has to be given for a rolling session (the decoder rows the regions flow through)")
             if capacity is not None and (int(capacity) != capacity or capacity < 1):
@@ -429,6 +437,7 @@ class LanguageModel(EngineOwner):
         elif num_return_sequences != 1:
             raise ValueError("num_return_sequences has to be 1 without do_sample (greedy search has one hypothesis per row)")
         check_rolling_args(max_length, rows)
+        mp = check_max_prompt_length(max_prompt_length, max_length)
         if rows is None:
             raise ValueError("rows has to be given for a rolling session (the decoder rows the sentences flow through)")
         if capacity is not None and (int(capacity) != capacity or capacity < 1):
@@ -440,7 +449,8 @@ class LanguageModel(EngineOwner):
                 seed = int(torch.empty((), dtype=torch.int64).random_().item())
             sample = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed),
                           num_return_sequences=int(num_return_sequences))
-        return self.engine().open_rolling(int(max_length), int(rows), None if capacity is None else int(capacity), sample=sample, **modes)
+        return self.engine().open_rolling(int(max_length), int(rows), None if capacity is None else int(capacity), sample=sample,
+                                          max_prompt_length=mp, **modes)
 
     @torch.no_grad()
     def beam_search_rolling(self, image_hidden_states: torch.FloatTensor, max_length: int, num_beams: int, *, rows: Optional[int] = None,

@@ -210,7 +210,8 @@ class ReportGenerationModel(EngineOwner):
 
     def open_rolling(self, max_length: int, *, rows: int, capacity: Optional[int] = None, do_sample: bool = False,
                      temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1,
-                     seed: Optional[int] = None, num_beams: int = 1, early_stopping: bool = False, length_penalty: float = 1.0):
+                     seed: Optional[int] = None, num_beams: int = 1, early_stopping: bool = False, length_penalty: float = 1.0,
+                     max_prompt_length: int = 0):
         """``LanguageModel.open_rolling`` behind the detector (same arguments and errors): ``submit(images)`` runs the detector and
         the region selection as ``generate_rolling`` does, enqueues the selected regions' feature rows and returns a ticket;
         ``advance``; ``collect()`` -> ``(ticket, result)`` for every ticket whose sentences have all ended, ``result`` being the
@@ -218,12 +219,14 @@ class ReportGenerationModel(EngineOwner):
         completes at once).  With ``num_beams > 1`` the regions are decoded by a ``RollingBeamSession`` and ``result`` is the 4-tuple
         ``generate(images, num_beams=.., early_stopping=.., num_return_sequences=..)`` returns for that submit.
         ``submit(images, max_length=.., temperature=.., top_k=.., top_p=.., seed=.., stop_token_ids=..)`` decodes that submit's
-        sentences with parameters of their own and ``cancel(ticket)`` cuts them (``RollingSession``)."""
+        sentences with parameters of their own and ``cancel(ticket)`` cuts them (``RollingSession``).
+        With ``max_prompt_length`` > 0, ``submit(images, region_prompts=..)`` takes int64 [B, 29, P]: the selected regions' sentences
+        continue their prompts and the ticket's ids start with them."""
         from .rolling_session import ReportRollingSession
         return ReportRollingSession(self, self.language_model.open_rolling(
             max_length, rows=rows, capacity=capacity, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
             num_return_sequences=num_return_sequences, seed=seed, num_beams=num_beams, early_stopping=early_stopping,
-            length_penalty=length_penalty))
+            length_penalty=length_penalty, max_prompt_length=max_prompt_length))
 
     @torch.no_grad()
     def generate_rolling_beam(self, images: torch.FloatTensor, max_length: int, num_beams: int, *, rows: Optional[int] = None,

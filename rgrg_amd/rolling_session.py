@@ -13,15 +13,30 @@ from . import _hip
 from .constants import PAD_TOKEN_ID
 
 
+def check_max_prompt_length(max_prompt_length, max_length: int, beam: bool = False) -> int:
+    """``open_rolling(max_prompt_length=..)`` -> the int, or ValueError: 0 (no prompts) .. max_length - 1, and 0 in a beam session."""
+    mp = max_prompt_length
+    if isinstance(mp, bool) or int(mp) != mp or mp < 0:
+        raise ValueError(f"max_prompt_length has to be a non-negative integer, but is {mp}")
+    if mp and beam:
+        raise ValueError("max_prompt_length: a rolling beam session takes no prompts (its scheduler lives on the host); open it with "
+                         "max_prompt_length=0")
+    if mp >= max_length:
+        raise ValueError(f"max_prompt_length has to be below max_length {max_length} (which counts the prompt, and one token is always "
+                         f"generated), but is {mp}")
+    return int(mp)
+
+
 class RollingSession:
     """R decoder rows through which the sequences of any number of ``submit`` calls flow.  Sequences are numbered q = 0, 1, ... in
     submit order, n per feature row.  The session holds ``capacity`` feature rows at a time: a submit that does not fit until
     finished sequences have been collected raises ``RgrgHipError`` and leaves the session as it was.  Any other decode call on the
     engine makes the session stale: its next call raises ``RgrgHipError`` ("stale"), ``close`` still works."""
 
-    def __init__(self, engine, dec, rows: int, capacity: int, n: int, max_length: int, sample: bool):
+    def __init__(self, engine, dec, rows: int, capacity: int, n: int, max_length: int, sample: bool, max_prompt_length: int = 0):
         self._eng, self._dec = engine, dec
         self.rows, self.capacity, self.n, self.max_length, self.sampled = rows, capacity, n, max_length, sample
+        self.max_prompt_length = max_prompt_length   # 0: the session takes no prompts
         self.submitted = 0          # sequences numbered so far
         self.watermark = 0          # the lowest sequence number not yet released
         self.unfinished = 0         # sequences pending or in a row, as of the last advance plus what was submitted since
@@ -83,24 +98,63 @@ class RollingSession:
                 -1 if top_k is None else int(top_k), 0.0 if top_p is None else float(top_p), 0 if seed is None else 1,
                 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF, (C.c_int * max(len(stops), 1))(*[int(t) for t in stops]), len(stops))
 
-    def submit(self, feats: torch.Tensor, *, max_length: Optional[int] = None, temperature: Optional[float] = None,
-               top_k: Optional[int] = None, top_p: Optional[float] = None, seed: Optional[int] = None,
-               stop_token_ids: Optional[Iterable[int]] = None) -> range:
+    def _prompt(self, prompt_ids, m: int, max_length: Optional[int]) -> Optional[torch.Tensor]:
+        """``submit(prompt_ids=..)`` -> int64 [m, P] on the host, contiguous (None without a prompt); ValueError before anything is
+        enqueued.  (A device tensor is copied to the host here, which waits for its stream: callers that must not wait pass host ids.)"""
+        if prompt_ids is None:
+            return None
+        if not self.max_prompt_length:
+            raise ValueError("prompt_ids: the session was opened without max_prompt_length (open_rolling(.., max_prompt_length=P_max) "
+                             "allocates the prompt rings)")
+        if not isinstance(prompt_ids, torch.Tensor) or prompt_ids.dtype != torch.int64:
+            raise ValueError(f"prompt_ids has to be an int64 tensor [m, P] or [P], but is "
+                             f"{prompt_ids.dtype if isinstance(prompt_ids, torch.Tensor) else type(prompt_ids).__name__}")
+        if prompt_ids.dim() == 1:
+            prompt_ids = prompt_ids.unsqueeze(0).expand(m, -1)
+        if prompt_ids.dim() != 2 or prompt_ids.shape[0] != m:
+            raise ValueError(f"prompt_ids has to be [m = {m}, P] (one prompt length per submit) or [P], but is {tuple(prompt_ids.shape)}")
+        P, limit = prompt_ids.shape[1], self.max_length if max_length is None else max_length
+        if not 1 <= P <= self.max_prompt_length or P + 1 > limit:
+            raise ValueError(f"prompt_ids holds {P} tokens per prompt: 1 .. {min(self.max_prompt_length, limit - 1)} are possible "
+                             f"(max_prompt_length {self.max_prompt_length}; max_length {limit} counts the prompt and one token is always "
+                             f"generated)")
+        ids = prompt_ids.detach().to("cpu").contiguous()
+        vocab = self._eng.vocab
+        if int(ids.min()) < 0 or int(ids.max()) >= vocab:
+            raise ValueError(f"prompt_ids has to hold token ids in 0 .. {vocab - 1}, but holds {int(ids.min())} .. {int(ids.max())}")
+        return ids
+
+    def submit(self, feats: torch.Tensor, *, prompt_ids: Optional[torch.Tensor] = None, max_length: Optional[int] = None,
+               temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+               seed: Optional[int] = None, stop_token_ids: Optional[Iterable[int]] = None) -> range:
         """feats [m, 1024] on the engine's device -> the sequence numbers of its m * n sentences.  Enqueued behind the steps already
         launched; an idle row starts a new sentence in the very next step.  Does not wait for the device.
         The keywords hold for all m * n sentences of this submit, None being the session's value: ``max_length`` in
         2 .. the session's; ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` in a sampling session only, validated as ``sample``
         does (``top_k=1``: a greedy sentence); with ``seed`` the sentences draw what ``sample_rolling(feats, .., seed=seed)`` draws for
         these rows alone; ``stop_token_ids``: up to 4 token ids that end a sentence as EOS does, the stop token being its last.
+        ``prompt_ids`` (a session opened with ``max_prompt_length``): int64 [m, P], or [P] for all m rows - the
+        sentences continue it as ``greedy_search`` continues ``input_ids`` under a mask of ones.  One P per submit, 1 ..
+        ``max_prompt_length``, and P + 1 <= the submit's ``max_length``, which counts the prompt; no padding and no mask.  Any ids
+        of the vocabulary: an EOS or a stop token inside the prompt ends nothing.  The n hypotheses of a row share its prompt;
+        ``collect`` delivers the prompt in front, its log-probs 0.  A BOS column is the submit without a prompt.  Pass a HOST
+        tensor: the ids are checked and handed over on the host, so a tensor on the device is copied back first, and that copy
+        waits for the device - the one case in which ``submit`` does.
         ValueError, the session as it was, for a value out of range."""
         lib, dec = self._live()
         if feats.dim() != 2 or feats.shape[0] < 1 or feats.shape[1] != 1024:
             raise ValueError(f"submit takes feature rows [m >= 1, 1024], got {tuple(feats.shape)}")
         req = self._request(max_length=max_length, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, stop_token_ids=stop_token_ids)
+        prompt = self._prompt(prompt_ids, feats.shape[0], max_length)
         with torch.cuda.device(self._eng.device):
             f = feats.to(device=self._eng.device, dtype=torch.float32).contiguous()
             first = C.c_longlong(0)
-            if req is None:
+            if prompt is not None:
+                if req is None:
+                    req = (0, 0.0, -1, 0.0, 0, 0, (C.c_int * 1)(), 0)   # the session's values
+                self._check(lib.rgrg_decoder_roll_submit_prompt(dec, _hip.ptr(f), f.shape[0], prompt.data_ptr(), prompt.shape[1], *req,
+                                                                C.byref(first), self._eng._s()), "rgrg_decoder_roll_submit_prompt")
+            elif req is None:
                 self._check(self._fn("submit")(dec, _hip.ptr(f), f.shape[0], C.byref(first), self._eng._s()), self._abi + "submit")
             else:
                 self._check(lib.rgrg_decoder_roll_submit_req(dec, _hip.ptr(f), f.shape[0], *req, C.byref(first), self._eng._s()),
@@ -115,7 +169,7 @@ class RollingSession:
         """Cancels sequences - a number or an iterable of numbers at or above the watermark and below ``submitted`` (ValueError
         otherwise, nothing cancelled).  Enqueued on the decoder's stream: the next step launched cuts a sequence that is running
         (that step's token is not appended, its row takes the next pending sequence in the same step); a pending one is cut in the
-        first step of the row it takes, as BOS alone; one that has ended is left as it is.  ``collect`` delivers a cut sequence with
+        first step of the row it takes, as BOS - or its prompt - alone; one that has ended is left as it is.  ``collect`` delivers a cut sequence with
         the tokens it had, and ``cancelled`` then holds its number."""
         lib, dec = self._live()
         qs = [qs] if isinstance(qs, int) else list(qs)
@@ -220,7 +274,9 @@ class RollingBeamSession(RollingSession):
                              f"per submit (its scheduler lives on the host)")
         return None
 
-    def submit(self, feats: torch.Tensor, **params) -> range:
+    def submit(self, feats: torch.Tensor, *, prompt_ids=None, **params) -> range:
+        if prompt_ids is not None:
+            raise ValueError("prompt_ids: a rolling beam session takes no prompts (its scheduler lives on the host)")
         self._request(**params)
         return super().submit(feats)
 
@@ -273,16 +329,28 @@ class ReportRollingSession:
         self._next = 0
 
     @torch.no_grad()
-    def submit(self, images: torch.Tensor, **params) -> int:
-        """``params``: the keywords of ``RollingSession.submit`` for the sentences of these images.  An argument error leaves
-        the session as it was and takes no ticket."""
+    def submit(self, images: torch.Tensor, *, region_prompts: Optional[torch.Tensor] = None, **params) -> int:
+        """``params``: the keywords of ``RollingSession.submit`` for the sentences of these images.  ``region_prompts``: int64
+        [B, 29, P], a prompt for every region of every image (``generate_from_prompts``' layout, without a mask); the prompts of the
+        selected regions go with their feature rows and the ticket's ids start with them.  An argument error leaves the session as
+        it was and takes no ticket."""
         m = self._model
         if self.session.closed:
             raise _hip.RgrgHipError("the rolling session is closed")
+        if region_prompts is not None and (not isinstance(region_prompts, torch.Tensor) or region_prompts.dim() != 3
+                                           or region_prompts.shape[:2] != (images.shape[0], 29)):
+            raise ValueError(f"region_prompts has to be an int64 tensor [B = {images.shape[0]}, 29, P], but is "
+                             f"{tuple(region_prompts.shape) if isinstance(region_prompts, torch.Tensor) else type(region_prompts).__name__}")
         _, detections, top_region_features, class_detected = m.object_detector(images)
         selected_regions, feats = m.binary_classifier_region_selection(top_region_features, class_detected, return_loss=False)
+        if region_prompts is not None:
+            flat = region_prompts.reshape(-1, region_prompts.shape[2])
+            # the argument errors are those of a submit that has sentences, whatever was selected
+            params["prompt_ids"] = flat[selected_regions.reshape(-1).to(flat.device)] if feats.shape[0] else flat[:1]
         if feats.shape[0] == 0:
-            self.session._request(**params)   # (the argument errors of a submit that has sentences)
+            self.session._request(**{k: v for k, v in params.items() if k != "prompt_ids"})   # (the argument errors of a submit that has sentences)
+            if region_prompts is not None:
+                self.session._prompt(params["prompt_ids"], 1, params.get("max_length"))
             rng = None
         else:
             rng = self.session.submit(feats, **params)
