@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librgrg_hip.so")
 SOURCES = ("runtime.hip", "gemm_f32.hip", "gemm_bf16.hip", "detector_ops.hip", "det_train.hip", "decoder.hip", "decoder_beam.hip", "decoder_beam_roll.hip",
-           "decoder_lm.hip", "decoder_sample.hip", "decoder_prompt.hip", "decoder_roll.hip", "sample.hip", "beam_sample.hip", "train_ops.hip", "attn_train16.hip", "attn_kv8.hip")
+           "decoder_lm.hip", "decoder_sample.hip", "decoder_prompt.hip", "decoder_roll.hip", "sample.hip", "beam_sample.hip", "train_ops.hip", "attn_train16.hip", "attn_kv8.hip", "attn_decode.hip")
 ARCH = "gfx950"
 
 

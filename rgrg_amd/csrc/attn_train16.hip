@@ -25,7 +25,6 @@
 namespace rgrg {
 
 typedef short h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 template <bool F16>
 __device__ __forceinline__ f32x16 mfma_h(const h16x8& a, const h16x8& b, const f32x16& c) {

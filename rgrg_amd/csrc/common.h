@@ -9,6 +9,7 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16;   // the bits of a bf16 / fp16 value
 
 namespace rgrg {
 
@@ -102,6 +103,16 @@ __device__ __forceinline__ unsigned f32x4_to_e4m3_bits(float a, float b, float c
 }
 __device__ __forceinline__ unsigned f32_to_e4m3_bits(float f) {
     return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(f), 0.0f, 0, false) & 0xffu;
+}
+
+// Element (row, k) of a matrix with rows of K floats kept fragment-major, the order v_mfma_f32_16x16x4_f32 consumes its A operand in
+// (skinny_direct.inc states the layout); the fp32 decode attention (attn_decode.hip) writes its output through it for the fused plan.
+__host__ __device__ inline size_t frag_off(int row, int k, int K) {
+    return ((((size_t)(row >> 5) * 2 + ((row >> 4) & 1)) * (size_t)(K >> 4) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + (row & 15)) * 4 + (k & 3);
+}
+// a raw buffer descriptor over everything behind p: 32-bit byte offsets, no bounds (skinny_direct.inc, attn_decode.hip)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dx_rsrc(const void* p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
 }
 
 __device__ __forceinline__ float wave_max(float v) {

@@ -1,4 +1,4 @@
-// What the decoder's translation units (decoder.hip: the decode step and the object; decoder_beam.hip: beam search;
+// What the decoder's translation units (decoder.hip: the decode step and the object; attn_decode.hip: the decode attention; decoder_beam.hip: beam search;
 // decoder_beam_roll.hip: rolling-batch beam search; decoder_lm.hip: the teacher-forced and training passes; decoder_roll.hip: rolling-batch decoding, greedy and sampled) share: the rgrg_decoder object, its constants and the few host
 // helpers that are called across those files.  Everything else is static in the file that uses it.
 #pragma once
@@ -436,6 +436,31 @@ int step_graph(rgrg_decoder* d, const StepSpec& s, const std::function<int()>& b
 StepSpec padded_step_spec(rgrg_decoder* d, StepSpec s, const int* pad);
 int enqueue_prefill(rgrg_decoder* d, const float* feats, int S, int row_mul = 1);
 int decode_begin(rgrg_decoder* d, void* stream);
+// attn_decode.hip.  One decode-attention launch on plain device pointers: the variant and grid rules of the product path.
+// launch_attention (decoder.hip) fills it from the decoder object, the test hooks rgrg_debug_attn_decode* from their arguments - the
+// rules exist once, in launch_attn_decode.
+struct AttnDecodeLaunch {
+    const float* qkv; int ld_qkv;          // [S][ld_qkv]: q | k | v of the current token, D floats each
+    void *kc, *vc;                         // K / V plane [rows][H][T][64]: fp32, 16 bit or e4m3 bytes (fmt)
+    size_t plane_elems;                    // elements of one plane (16 bit / e4m3: bounds the 32-bit byte offsets of the buffer loads)
+    const int* step;
+    float* out; unsigned short* out16;
+    int S, H, T;
+    const int* src;                        // beam search: [S][T] ancestor table, or NULL
+    const float* kmask;                    // [S][T] additive padding mask of the cache slots, or NULL (fp32 kernel only)
+    KvFormat fmt;                          // KV_F32, KV_BF16 / KV_F16 (one kernel; the type is f16), KV_E4M3
+    int f16;                               // the 16-bit type of a 16-bit cache and of out16 (0 bf16, 1 fp16)
+    int ni;                                // fp32 kernel: 9 / 2 keys per group and chunk; 0 = S * H <= 4096 ? 9 : 2
+    int frag_out;
+    int max_wgs;                           // wave kernels (16 bit, e4m3): > 0 caps the grid, each wave then walks several (sequence, head) items
+    hipStream_t st;
+    bool q_only = false;                   // 16-bit cache without src: slot t + 1 already holds the new k / v (c_attn's K/V-cache epilogue) -
+                                           // the kernel reads q only and stores nothing to the cache
+    const int* first = nullptr;            // 16-bit cache: [S] padded prompt slots, cache slots 1 .. first[s] are left out (with src: not q_only)
+    const int* row_step = nullptr;         // fp32 / 16-bit cache: [S] the step of every row on its own, instead of the one word *step (rolling-batch
+                                           // decoding); plain or with src (rolling beam search) - no mask, no padded slots, not q_only
+};
+int launch_attn_decode(const AttnDecodeLaunch& a);
 // attn_kv8.hip: attn_decode_kv8_wave_kernel on `workgroups` workgroups of 4 waves (grid and argument rules: launch_attn_decode)
 int launch_attn_decode_kv8(const float* qkv, int ld_qkv, uint8_t* kc, uint8_t* vc, const int* step, float* out, unsigned short* out16,
                            int S, int H, int T, const int* src, int f16, int workgroups, hipStream_t st);

@@ -15,9 +15,6 @@ using namespace rgrg;
 namespace rgrg {
 namespace {
 
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 enum { MASK_ROW_EMPTY = 1, MASK_NOT_LEFT = 2, MASK_HAS_PAD = 4, MASK_NOT_BINARY = 8 };
 
 // One thread per row of attention_mask [S][T]: pad[s] = the zeros in front; flags |= what the host refuses or needs to know

@@ -26,7 +26,6 @@ struct RollRows {
     int *seq, *len, *tok, *pos, *step, *list, *shared;
 };
 constexpr int ROLL_NEXT = 0, ROLL_UNFINISHED = 1, ROLL_REFILLS = 2, ROLL_STEPS = 3;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // a length word of the prompt ring, kept inside 1 .. MP whatever the ring holds (the host has checked it: no kernel indexes by trust)
 __device__ __forceinline__ int roll_prompt_len(int P, int MP) { return min(max(P, 1), MP); }

@@ -20,7 +20,6 @@ namespace rgrg {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr float LN_EPS16 = 1e-5f;   // nn.LayerNorm(eps=1e-5) of GPT-2

@@ -24,10 +24,7 @@
 //     every consumer workgroup re-reads these streams through its CU's 64 B/clk L2 port, 128 KiB each.
 // Request order inside a wave: activation fragments first, the HBM weight stream last (vector loads return in order:
 // a wait on an activation never waits for an HBM miss).
-
-__host__ __device__ inline size_t frag_off(int row, int k, int K) {
-    return ((((size_t)(row >> 5) * 2 + ((row >> 4) & 1)) * (size_t)(K >> 4) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + (row & 15)) * 4 + (k & 3);
-}
+// (frag_off, the offset of one element in the fragment-major layout, and dx_rsrc are in common.h: the decode attention uses them too.)
 
 constexpr int DX_PLAIN = 0, DX_COMBINE4 = 1, DX_EMBED = 2, DX_EMBED_TOK = 3, DX_EMBED_TOKPOS = 4;   // TOKPOS: per-row tokens AND positions
 constexpr int DK_PW = 8;        // one-KiB weight chunks (16 k each) per wave; a workgroup covers 8 * 8 * 16 = 1024 k
@@ -62,9 +59,6 @@ __device__ __forceinline__ f32x4 dx_ldb(__amdgpu_buffer_rsrc_t r, unsigned voff,
 }
 __device__ __forceinline__ f32x4 dx_ldb_nt(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 2));  // aux 2 = nt
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dx_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
 }
 
 // 16-bit-weight variant (round 6, W16 = 1 bf16 / 2 fp16; 33-128 rows under torch.autocast): the packed weights are stored as 16 bit in

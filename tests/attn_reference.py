@@ -9,7 +9,7 @@ The formulas (every function takes ``dt``: torch.float64 for the reference, torc
   against autograd (tests/test_attention_reference.py).
 
 Where the reference rounds to the 16-bit type, because the kernel does:
-  kv16 decode (attn_decode_kv16_wave_kernel): the new token's k / v before they take part as the last key and are stored to the
+  kv16 decode (attn_decode_kv16_wave_kernel, csrc/attn_decode.hip): the new token's k / v before they take part as the last key and are stored to the
       cache; the output when it goes to out16.
   attn16_fwd_kernel: the UNNORMALISED probabilities exp(s - max) times the dropout mask, as the MFMA operand of P V
       (attn_train16.hip:153-163); the output, after the division by the sum of the UNROUNDED exponentials (:136-147, :171-181).
@@ -465,5 +465,6 @@ def decode_inputs(S: int, H: int, nkeys: int, slots: int, seed: int, with_src: b
 
 
 def frag_off(row: int, k: int, Kdim: int) -> int:
-    """Offset of element (row, k) in the fragment-major activation layout of the fused decode plan (csrc/skinny_direct.inc)."""
+    """Offset of element (row, k) in the fragment-major activation layout of the fused decode plan (frag_off of csrc/common.h; the layout is
+    stated in csrc/skinny_direct.inc), which attn_decode_kernel (csrc/attn_decode.hip) writes with frag_out."""
     return ((((row >> 5) * 2 + ((row >> 4) & 1)) * (Kdim >> 4) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + (row & 15)) * 4 + (k & 3)
